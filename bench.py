@@ -17,7 +17,12 @@ workload are sharded over the N ranks (K / N per GPU, STRONG scaling: the global
 unit of the metric at every N) and the per-iteration exchanges run over RCCL inside the engine;
 value = global iterations per second.  cfg5 runs replicas (problems split over the ranks).
 
-Also reported:
+A plain run sets up, warms up, times --steps steps and prints the result line (value,
+ms_per_step; the fields below are null).  --dump-outputs DIR writes what the last timed step left
+for a caller (theta, the noiseless trajectory, the rollouts' state costs) as DIR/<name>.npy; the
+inputs are seeded, so two builds given the same arguments can be compared array for array.
+
+With --full also reported (each takes runs of its own after the timed steps):
   roofline      the dominant kernel k_rollout (noise phase + Task::execute of the K_loc noisy
                 rollouts and the deferred noiseless one): achieved = SURVEY.md 8(d) algorithmic
                 bytes per unit (4 S + 16 J + 8) x (K_loc + 1) N units / its HIP-event average
@@ -76,11 +81,22 @@ def parse():
     ap.add_argument("--group", type=int, default=-1,
                     help="cfg5: problems per engine group (shared launches; -1 = all of a GPU's problems, "
                          "0 = one stream per problem)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget (0 = skip)")
-    ap.add_argument("--no-timing", action="store_true", help="skip the HIP-event pass (no roofline)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the HIP-event pass (roofline, per-kernel times), the "
+                         "device optimize loop and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0,
+                    help="--full: CPU baseline sample budget (0 = skip)")
+    ap.add_argument("--no-timing", action="store_true", help="--full: skip the HIP-event pass (no roofline)")
     ap.add_argument("--optimize-steps", type=int, default=200,
-                    help="also time StompOptimizer::optimize (device-resident loop) for this many iterations (0 = skip)")
+                    help="--full: also time StompOptimizer::optimize (device-resident loop) for this many "
+                         "iterations (0 = skip)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not a.full:
+        a.no_timing, a.cpu_seconds, a.optimize_steps = True, 0.0, 0
     w = WORKLOADS[a.workload]
     for k, v in w.items():
         if getattr(a, k) is None:
@@ -287,6 +303,22 @@ def max_over_ranks(dist, x: float) -> float:
     return float(t.item())
 
 
+DUMP_ARRAY_BYTES = 16 << 20   # per array; three arrays stay under 64 MB in all
+
+
+def dump_outputs(path: str, rank: int, arrays: dict):
+    """--dump-outputs: the arrays as float64 path/<name>.npy (rank r > 0 of a sharded run:
+    <name>.rank<r>.npy, its own rows).  An array over DUMP_ARRAY_BYTES is written as a fixed
+    seeded sample of its elements (ascending flat index), the same sample in every run."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float64)
+        if a.nbytes > DUMP_ARRAY_BYTES:
+            pick = np.sort(np.random.default_rng(2011).choice(a.size, DUMP_ARRAY_BYTES // 8, replace=False))
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(path, name + (f".rank{rank}" if rank else "") + ".npy"), a)
+
+
 def bench_problems(args, world, rank, local_rank, dist):
     """cfg5: the batch of independent planning problems split over the ranks (replicas, no
     communication), distinct start / goal / seed, one shared device-built SDF per GPU, one engine
@@ -359,6 +391,12 @@ def bench_problems(args, world, rank, local_rank, dist):
         dist.barrier()
     elapsed = max_over_ranks(dist, elapsed)
     value = P_all * args.steps / elapsed
+    if args.dump_outputs:
+        # this rank's problems, stacked in problem order
+        dump_outputs(args.dump_outputs, rank,
+                     {"theta": np.stack([e.theta() for e in engines]),
+                      "last_trajectory": np.stack([e.last_trajectory() for e in engines]),
+                      "state_costs": np.stack([e.rollouts("state_costs") for e in engines])})
 
     # the roofline of the dominant kernel, the grouped rollout launch (every engine of a group:
     # k_rollout_group), timed with HIP events on the group's stream in a second pass of the same
@@ -485,8 +523,12 @@ def main():
     elapsed = max_over_ranks(dist, t1 - t0)
     ms_per_step = 1000.0 * elapsed / args.steps
     value = args.steps / elapsed   # global iterations (of the whole K) per second
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank,
+                     {"theta": e.theta(), "last_trajectory": e.last_trajectory(),
+                      "state_costs": e.rollouts("state_costs")})
 
-    # Kernel durations: the same K steps again with HIP events recorded around every stage
+    # --full: kernel durations: the same K steps again with HIP events recorded around every stage
     # on the engine stream.  The events themselves cost ~10 us of dispatch gap per stage,
     # which is why `value` comes from the event-free pass above.
     timing = {}

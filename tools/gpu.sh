@@ -33,7 +33,7 @@ show() {  # one-line summary of a bench JSON
 }
 bench_to() {  # bench_to OUT LIMIT ARGS...
   local out=$1 lim=$2; shift 2
-  timeout -k 10 $lim python3 bench.py "$@" > $out 2> ${out%.json}.err || { tail -20 ${out%.json}.err; return 1; }
+  timeout -k 10 $lim python3 bench.py --full "$@" > $out 2> ${out%.json}.err || { tail -20 ${out%.json}.err; return 1; }
 }
 case "$cmd" in
 tests)
@@ -54,7 +54,7 @@ ab)
     for shape in "200 20" "20 5"; do
       set -- $shape
       out=gpurun_out/ab/$label.$1.json
-      env $(echo "$envs" | tr ',' ' ') timeout -k 10 300 python3 bench.py --steps $1 --warmup $2 --cpu-seconds 0 --optimize-steps 0 $(echo "$args" | tr ',' ' ') > $out 2> ${out%.json}.err || { tail -5 ${out%.json}.err; exit 1; }
+      env $(echo "$envs" | tr ',' ' ') timeout -k 10 300 python3 bench.py --full --steps $1 --warmup $2 --cpu-seconds 0 --optimize-steps 0 $(echo "$args" | tr ',' ' ') > $out 2> ${out%.json}.err || { tail -5 ${out%.json}.err; exit 1; }
       show $out "$label $1/$2"
     done
   done ;;
@@ -75,6 +75,7 @@ prof)
   tag=$1; shift
   mkdir -p gpurun_out/$tag
   [ $# -eq 0 ] && set -- --steps 200 --warmup 20
+  set -- --full "$@"   # the trace covers the event pass too, as the committed kernel stats do
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/$tag -o run -- python3 bench.py --cpu-seconds 0 --optimize-steps 0 "$@" > gpurun_out/$tag/bench.json 2> gpurun_out/$tag/bench.err || { tail -30 gpurun_out/$tag/bench.err; exit 1; }
   find gpurun_out/$tag -name "*kernel_stats.csv" | head -1 | xargs cat | cut -d, -f1-8 | head -20 ;;
 pmc)
