@@ -135,8 +135,8 @@ class so_shape(C.Structure):
 
 def sdf_build_objects(grid, objects, points=None, with_field: bool = True):
     """so_sdf_build_objects (oracle/sdf_oracle.c) for problem.Grid `grid`: (field n^3 uint16 squared cell distances or None,
-    marks n^3 uint8, number of points marked)."""
-    n = grid.n
+    marks n^3 uint8, number of points marked); n^3 reads nx*ny*nz for a non-cubic grid."""
+    dims = tuple(grid.dims)
     arr = (so_shape * max(len(objects), 1))()
     keep = []
     for i, o in enumerate(objects):
@@ -151,11 +151,11 @@ def sdf_build_objects(grid, objects, points=None, with_field: bool = True):
             arr[i].vertices = _dp(v)
             arr[i].num_vertices = len(v)
     pts = np.ascontiguousarray(points if points is not None else np.zeros((0, 3)), np.float64).reshape(-1, 3)
-    occ = np.zeros((n, n, n), np.uint8)
-    field = np.zeros((n, n, n), np.uint16) if with_field else None
+    occ = np.zeros(dims, np.uint8)
+    field = np.zeros(dims, np.uint16) if with_field else None
     origin = np.array(grid.origin, np.float64)
     marked = lib().so_sdf_build_objects(
-        n, n, n, _dp(origin), grid.resolution, grid.max_expansion, arr, len(objects),
+        dims[0], dims[1], dims[2], _dp(origin), grid.resolution, grid.max_expansion, arr, len(objects),
         _dp(pts if pts.size else np.zeros(3)), len(pts), occ.ctypes.data_as(C.POINTER(C.c_ubyte)),
         field.ctypes.data_as(C.POINTER(C.c_uint16)) if field is not None else None)
     if marked < 0:
@@ -214,6 +214,8 @@ class Oracle:
                          so_sphere)
         self._joints = _arr([so_joint(int(j.has_limits), j.min, j.max, j.joint_cost) for j in p.robot.joints], so_joint)
         self._sdf = np.ascontiguousarray(p.sdf, dtype=np.uint16)
+        if self._sdf.shape != tuple(p.grid.dims):
+            raise ValueError(f"problem.sdf has shape {self._sdf.shape}, the grid is {tuple(p.grid.dims)}")
         pr = p.params
         self._sig = pr.per_joint("noise_stddev", self.J)
         self._dec = pr.per_joint("noise_decay", self.J)
@@ -228,7 +230,7 @@ class Oracle:
         cfg.num_spheres = self.S
         cfg.spheres = self._sph
         cfg.joints = self._joints
-        cfg.sdf = so_sdf(g.n, g.n, g.n, (C.c_double * 3)(*g.origin), g.resolution,
+        cfg.sdf = so_sdf(g.nx, g.ny, g.nz, (C.c_double * 3)(*g.origin), g.resolution,
                          self._sdf.ctypes.data_as(C.POINTER(C.c_uint16)))
         cfg.discretization = pr.trajectory_discretization
         cfg.smoothness_costs = (C.c_double * 3)(pr.smoothness_cost_velocity, pr.smoothness_cost_acceleration,
@@ -253,8 +255,7 @@ class Oracle:
                                          (C.c_double * 6)(*s.inertia.inertia)) if s.inertia else so_inertia()
                               for s in p.robot.segments], so_inertia)
         cfg.inertias = self._inertia
-        cfg.torque_root = p.robot.index(p.torque_root)
-        cfg.torque_tip = p.robot.index(p.torque_tip)
+        cfg.torque_root, cfg.torque_tip = p.torque_segments()
         cfg.gravity = (C.c_double * 3)(*p.gravity)
         self._oc = _arr([so_orientation_constraint(p.robot.index(c.link_name), (C.c_double * 4)(*c.orientation),
                                                    0 if c.header_frame else 1, c.absolute_roll_tolerance,

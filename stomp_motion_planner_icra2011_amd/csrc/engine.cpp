@@ -1771,6 +1771,18 @@ int stomp_engine_create(const stomp_engine_desc* d, stomp_engine** out)
         const char* xi = std::getenv("STOMP_DEBUG_XCTL_INLINE");
         m.x_ctl_inline = xi && std::strcmp(xi, "1") == 0 ? 1 : 0;
     }
+    if (getenv("STOMP_DEBUG_LEAN_PRINT")) {
+        // what creation chose for this model, and the body launch_cost takes for an iteration's
+        // K_loc rollouts + the noiseless one beside the pregen blocks (read-only: tests and tables)
+        const int nro = e->K_loc + 1, extra = e->pre_on ? e->rows : 0;
+        const int P = rollout_split_pieces(m, nro, extra, false);
+        const char* body = P ? "split" : nro <= m.cus ? (m.phased_lds > 0 ? "phased" : "wide")
+                                                      : (m.lean ? "lean slot loop" : "slot loop");
+        fprintf(stderr, "stomp: model J %d N %d S %d nseg %d nops %d nsaves %d sincos_pre %d sph_chunk %d lean %d "
+                        "pregen %d fused_noise %d brick %d, launch of %d rollouts: %s, %d pieces\n",
+                J, N, e->S, m.nseg, m.nops, m.nsaves, m.sincos_pre, m.sph_chunk, m.lean, e->pre_on ? 1 : 0,
+                J <= 16 ? 1 : 0, m.brick, nro, body, P);
+    }
     m.pad_collision = 0;
     launch_pad_fk(m, e->d_start, e->d_goal, e->d_pad_pos, e->d_pad_cf, e->stream);
     int pad_cf = 0;

@@ -189,7 +189,7 @@ def _check(rc: int, handle=None):
 
 
 def sdf_build_device(problem, device_tensor_ptr: int, stream: int = 0):
-    """Builds problem.grid's distance field directly into a device buffer of n^3 uint16 squared cell
+    """Builds problem.grid's distance field directly into a device buffer of nx*ny*nz uint16 squared cell
     distances (stomp_grid's representation; problem.build_sdf is the host twin)."""
     l = load_library()
     g = problem.grid
@@ -198,7 +198,7 @@ def sdf_build_device(problem, device_tensor_ptr: int, stream: int = 0):
     origin = np.array(g.origin, np.float64)
     boxes = boxes if boxes.size else np.zeros(1)
     cyl = cyl if cyl.size else np.zeros(1)
-    _check(l.stomp_sdf_build(g.n, g.n, g.n, _dp(origin), g.resolution, g.max_expansion, _dp(boxes),
+    _check(l.stomp_sdf_build(g.nx, g.ny, g.nz, _dp(origin), g.resolution, g.max_expansion, _dp(boxes),
                              len(problem.boxes), _dp(cyl), len(problem.cylinders), C.c_void_p(device_tensor_ptr),
                              C.c_void_p(stream)))
 
@@ -225,12 +225,12 @@ def shape_array(objects):
 def sdf_build_objects_device(grid, objects, device_ptr: int, points=None, stream: int = 0) -> int:
     """The reference's distance-field fill (stomp_sdf_build_objects) of problem.Grid `grid` from
     collision objects (problem.SceneObject) and collision-map points (P x 3) into a device buffer
-    of n^3 uint16 squared cell distances.  Returns the number of points that landed in the grid."""
+    of nx*ny*nz uint16 squared cell distances.  Returns the number of points that landed in the grid."""
     l = load_library()
     origin = np.array(grid.origin, np.float64)
     pts = np.ascontiguousarray(points if points is not None else np.zeros((0, 3)), np.float64).reshape(-1, 3)
     marked = C.c_int64(0)
-    _check(l.stomp_sdf_build_objects(grid.n, grid.n, grid.n, _dp(origin), grid.resolution, grid.max_expansion,
+    _check(l.stomp_sdf_build_objects(grid.nx, grid.ny, grid.nz, _dp(origin), grid.resolution, grid.max_expansion,
                                      shape_array(objects), len(objects), _dp(pts if pts.size else np.zeros(3)),
                                      len(pts), C.c_void_p(device_ptr), C.byref(marked), C.c_void_p(stream)))
     return marked.value
@@ -278,9 +278,11 @@ class Engine:
                 raise TypeError(f"problem.sdf must hold integer squared cell distances (uint16), got {sdf.dtype}")
             if sdf.size and (int(sdf.min()) < 0 or int(sdf.max()) > 65535):
                 raise ValueError("problem.sdf squared cell distances must lie in [0, 65535]")
+            if sdf.shape != tuple(g.dims):
+                raise ValueError(f"problem.sdf has shape {sdf.shape}, the grid is {tuple(g.dims)}")
             self._sdf = np.ascontiguousarray(sdf, np.uint16)
             grid_ptr, on_dev = self._sdf.ctypes.data, 0
-        d.grid = stomp_grid(g.n, g.n, g.n, (C.c_double * 3)(*g.origin), g.resolution, C.c_void_p(grid_ptr), on_dev)
+        d.grid = stomp_grid(g.nx, g.ny, g.nz, (C.c_double * 3)(*g.origin), g.resolution, C.c_void_p(grid_ptr), on_dev)
         d.discretization = pr.trajectory_discretization
         d.smoothness_costs = (C.c_double * 3)(pr.smoothness_cost_velocity, pr.smoothness_cost_acceleration,
                                               pr.smoothness_cost_jerk)
@@ -308,8 +310,7 @@ class Engine:
             stomp_inertia(s.inertia.mass, (C.c_double * 3)(*s.inertia.com), (C.c_double * 6)(*s.inertia.inertia))
             if s.inertia else stomp_inertia() for s in p.robot.segments])
         d.inertias = self._inertia
-        d.torque_root = p.robot.index(p.torque_root)
-        d.torque_tip = p.robot.index(p.torque_tip)
+        d.torque_root, d.torque_tip = p.torque_segments()
         d.gravity = (C.c_double * 3)(*p.gravity)
         oc = p.orientation_constraints
         self._oc = (stomp_orientation_constraint * max(len(oc), 1))(*[

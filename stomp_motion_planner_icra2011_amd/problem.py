@@ -288,10 +288,39 @@ def mesh_object(vertices, triangles=None, position=(0.0, 0.0, 0.0), rpy=(0.0, 0.
 
 @dataclasses.dataclass
 class Grid:
-    n: int                    # cells per axis (cube)
+    n: int                    # cells per axis of a cube; with `shape` the longest axis, max(shape)
     origin: Sequence[float]
     resolution: float
     max_expansion: float
+    shape: Optional[Sequence[int]] = None   # (nx, ny, nz) of a non-cubic grid; None: (n, n, n)
+
+    def __post_init__(self):
+        if self.shape is not None:
+            self.shape = tuple(int(v) for v in self.shape)
+            if len(self.shape) != 3 or min(self.shape) < 1:
+                raise ValueError("Grid.shape must be three positive cell counts (nx, ny, nz)")
+            self.n = max(self.shape)
+
+    @property
+    def dims(self) -> tuple:
+        """(nx, ny, nz): the field is indexed [x, y, z], z fastest."""
+        return self.shape if self.shape is not None else (self.n, self.n, self.n)
+
+    @property
+    def nx(self) -> int:
+        return self.dims[0]
+
+    @property
+    def ny(self) -> int:
+        return self.dims[1]
+
+    @property
+    def nz(self) -> int:
+        return self.dims[2]
+
+    @property
+    def cells(self) -> int:
+        return self.nx * self.ny * self.nz
 
     @property
     def max_dist_int(self) -> int:
@@ -317,51 +346,52 @@ def _axis_d2(i0: int, i1: int, n: int) -> np.ndarray:
 def cylinder_disc_d2(c: Cylinder, grid: Grid) -> np.ndarray:
     """Integer squared distance (in the xy plane) from every cell column to the
     nearest cell column whose centre lies inside the disc; -1 rows if empty."""
-    n, res = grid.n, grid.resolution
+    nx, ny, res = grid.nx, grid.ny, grid.resolution
     ox, oy = grid.origin[0], grid.origin[1]
-    xs = ox + np.arange(n, dtype=np.float64) * res - c.center[0]
-    ys = oy + np.arange(n, dtype=np.float64) * res - c.center[1]
+    xs = ox + np.arange(nx, dtype=np.float64) * res - c.center[0]
+    ys = oy + np.arange(ny, dtype=np.float64) * res - c.center[1]
     inside = (xs[:, None] * xs[:, None] + ys[None, :] * ys[None, :]) <= c.radius * c.radius
     pi, pj = np.nonzero(inside)
     big = np.int64(1) << 40
-    out = np.full((n, n), big, dtype=np.int64)
+    out = np.full((nx, ny), big, dtype=np.int64)
     if len(pi) == 0:
         return out
-    ii = np.arange(n, dtype=np.int64)
+    ix = np.arange(nx, dtype=np.int64)
+    iy = np.arange(ny, dtype=np.int64)
     for a, b in zip(pi, pj):
-        dx = (ii - a) ** 2
-        dy = (ii - b) ** 2
+        dx = (ix - a) ** 2
+        dy = (iy - b) ** 2
         np.minimum(out, dx[:, None] + dy[None, :], out=out)
     return out
 
 
 def build_sdf(grid: Grid, boxes, cylinders) -> np.ndarray:
-    """Capped distance field as squared cell distances: uint16 d2 = min(d2, cap^2), shape (n, n, n),
-    index [x, y, z] (z fastest).  The distance of a cell is sqrt(d2) * res (sdf_metres): the
+    """Capped distance field as squared cell distances: uint16 d2 = min(d2, cap^2), shape
+    (nx, ny, nz), index [x, y, z] (z fastest).  The distance of a cell is sqrt(d2) * res (sdf_metres): the
     integer distance_square_ and sqrt_table_ of PropagationDistanceField."""
-    n, res = grid.n, grid.resolution
+    dims, res = grid.dims, grid.resolution
     cap = grid.max_dist_int
     cap2 = cap * cap
-    d2 = np.full((n, n, n), cap2, dtype=np.int64)
+    d2 = np.full(dims, cap2, dtype=np.int64)
     o = grid.origin
     for b in boxes:
         rngs = []
         for a in range(3):
             lo = b.center[a] - b.dims[a] / 2.0
             hi = b.center[a] + b.dims[a] / 2.0
-            rngs.append(_box_range(lo, hi, o[a], res, n))
+            rngs.append(_box_range(lo, hi, o[a], res, dims[a]))
         if any(r[0] > r[1] for r in rngs):
             continue
-        dx, dy, dz = (_axis_d2(r[0], r[1], n) for r in rngs)
+        dx, dy, dz = (_axis_d2(r[0], r[1], dims[a]) for a, r in enumerate(rngs))
         np.minimum(d2, dx[:, None, None] + dy[None, :, None] + dz[None, None, :], out=d2)
     for c in cylinders:
-        z0, z1 = _box_range(c.center[2] - c.length / 2.0, c.center[2] + c.length / 2.0, o[2], res, n)
+        z0, z1 = _box_range(c.center[2] - c.length / 2.0, c.center[2] + c.length / 2.0, o[2], res, dims[2])
         if z0 > z1:
             continue
         dxy = cylinder_disc_d2(c, grid)
         if dxy.min() >= (np.int64(1) << 40):
             continue
-        dz = _axis_d2(z0, z1, n)
+        dz = _axis_d2(z0, z1, dims[2])
         np.minimum(d2, np.minimum(dxy[:, :, None] + dz[None, None, :], cap2), out=d2)
     if cap2 > 65535:
         raise ValueError("max_expansion / resolution above 255 cells: d2 does not fit 16 bits")
@@ -435,14 +465,18 @@ class Problem:
     sdf: Optional[np.ndarray] = None
     # inverse-dynamics chain of the torque term: KDL getChain("torso_lift_link",
     # "r_gripper_tool_frame") with gravity (0, 0, -9.8) (stomp_robot_model.cpp:185-189)
-    torque_root: str = "torso_lift_link"
-    torque_tip: str = "r_gripper_tool_frame"
+    # (segment names; a model without them sets its own, or None: no inverse-dynamics chain,
+    # which only a problem with torque_cost_weight = 0 may leave unset)
+    torque_root: Optional[str] = "torso_lift_link"
+    torque_tip: Optional[str] = "r_gripper_tool_frame"
     gravity: Sequence[float] = (0.0, 0.0, -9.8)
     orientation_constraints: List[OrientationConstraint] = dataclasses.field(default_factory=list)
 
     def torque_chain(self) -> List[int]:
         """Segment indices of the chain root (exclusive) -> tip (inclusive), root side first."""
-        r, s = self.robot.index(self.torque_root), self.robot.index(self.torque_tip)
+        r, s = self.torque_segments()
+        if r < 0 or s < 0:
+            raise ValueError("the problem names no torque chain")
         out = []
         while s != r:
             if s < 0:
@@ -450,6 +484,14 @@ class Problem:
             out.append(s)
             s = self.robot.segments[s].parent
         return out[::-1]
+
+    def torque_segments(self) -> tuple:
+        """(root, tip) segment indices of the torque chain as the engine and the oracle take
+        them; (-1, -1) when the problem names none (both sides then build no chain, and refuse
+        torque_cost_weight > 0)."""
+        if self.torque_root is None or self.torque_tip is None:
+            return -1, -1
+        return self.robot.index(self.torque_root), self.robot.index(self.torque_tip)
 
     @property
     def J(self) -> int:
@@ -541,7 +583,7 @@ def c_round(x):
 def sdf_lookup(p: Problem, pos: np.ndarray) -> np.ndarray:
     g = p.grid
     f = c_round((pos - np.array(g.origin)) * (1.0 / g.resolution))
-    ok = np.all((f >= 1) & (f < g.n - 1), axis=-1)
+    ok = np.all((f >= 1) & (f < np.array(g.dims, np.float64) - 1), axis=-1)
     idx = np.where(ok[..., None], f, 0).astype(np.int64)
     d = sdf_metres(g, p.sdf[idx[..., 0], idx[..., 1], idx[..., 2]])
     return np.where(ok, d, 0.0)

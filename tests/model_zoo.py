@@ -1,0 +1,466 @@
+"""TEST INFRASTRUCTURE: a zoo of small planning problems beyond the PR2 shelf fixture.
+
+Every parity test used to build its problem with problem.make_problem: two robots, unit joint
+axes, identity fixed rotations, one cubic grid, one set of cost weights.  The builders here are
+deterministic (seeded, no files) and each returns a problem.Problem that reaches device code the
+PR2 fixture cannot (stomp_engine_create's plan_fk choices, engine.cpp: nsaves, sincos_pre, split
+sphere runs, pruned segments; the joint-count branches of the noise kernels):
+
+    stick1    J = 1, serial, one sphere link: nsaves = 0
+    chain5    J = 5, serial, nsaves = 0; a link of 22 spheres (a run longer than run_max(N) = 16);
+              joint 4 on a segment below every sphere (pruned), joint 1 used by no segment;
+              joints 0-1 limited, 2 unlimited, 3 with min == max, 4 limited
+    hand9     J = 9: 5-joint arm, a palm forking into two 2-joint fingers (the branch is above
+              the last joint: nsaves = 1, sincos_pre = 0)
+    fork12/13 serial chain of 12 / 13 joints, a fixed two-way fork at the tip: sincos_pre = 1 / 0
+              at the J = 12 nsaves boundary
+    chain17   J = 17, serial: the unfused noise path, noise_jp = 20
+    fork24    J = 24, two nested fixed forks after the last joint: nsaves = 2, sincos_pre = 1
+    chain32   J = kMaxJoints
+
+Every segment that carries a joint has a non-identity fixed rotation and a skew unit axis; fixed
+segments mix identity and non-identity rotations.  Radii, clearances and joint costs vary per
+sphere and per joint.  The robots stand near the low corner of the grid, so perturbed rows leave
+the field, and each scene is a few boxes put where the default trajectory passes (collision and
+hinge zone).  `census` counts what the rows handed to execute actually reach; the tests assert it
+before they compare anything.
+"""
+import numpy as np
+
+from stomp_motion_planner_icra2011_amd import problem as pb
+
+ORIGIN = (-0.5, -1.0, -0.3)
+RES = 2.0 / 64
+BASE = (-0.37, -0.80, -0.02)     # robot base: 0.08 / 0.15 / 0.23 m inside the three low faces
+BASE_LONG = (-0.2, -0.7, 0.1)    # for the robots with long links (J < 12)
+NONCUBIC = (40, 52, 66)          # distinct sizes; 52 is a multiple of 4, 40 too, 66 is not
+NONCUBIC_PERM = (66, 40, 52)
+ALT_PARAMS = dict(smoothness_cost_velocity=0.3, smoothness_cost_jerk=0.05, ridge_factor=1e-5,
+                  obstacle_cost_weight=2.5)
+IDENTITY = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0)
+
+
+def _rot(rng):
+    """A random proper rotation (from a unit quaternion), row-major."""
+    q = rng.standard_normal(4)
+    x, y, z, w = q / np.linalg.norm(q)
+    return (1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+            2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+            2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y))
+
+
+def _axis(rng):
+    """A unit axis with no small component (no term of Rot2 multiplies an exact zero)."""
+    while True:
+        a = rng.standard_normal(3)
+        a = a / np.linalg.norm(a)
+        if np.abs(a).min() > 0.2:
+            return tuple(float(v) for v in a)
+
+
+def _dir(rng, length):
+    d = rng.standard_normal(3)
+    return tuple(float(v) for v in d / np.linalg.norm(d) * length)
+
+
+class _Builder:
+    def __init__(self, seed, J):
+        self.rng = np.random.default_rng(seed)
+        self.segs, self.spheres = [], []
+        self.J = J
+        self.add("base", -1, -1, BASE if J >= 12 else BASE_LONG, rot=_rot(self.rng))
+
+    def add(self, name, parent, q, trans, rot=None, axis=(0.0, 0.0, 1.0)):
+        self.segs.append(pb.Segment(name, parent, q, tuple(trans), tuple(axis), tuple(rot or IDENTITY)))
+        return len(self.segs) - 1
+
+    def joint(self, name, parent, q, length):
+        """A joint segment: non-identity rot, skew axis, offset `length` from its parent."""
+        return self.add(name, parent, q, _dir(self.rng, length), rot=_rot(self.rng), axis=_axis(self.rng))
+
+    def fixed(self, name, parent, length, rotated=True):
+        return self.add(name, parent, -1, _dir(self.rng, length), rot=_rot(self.rng) if rotated else None)
+
+    def balls(self, seg, toward, count, radius=(0.03, 0.06)):
+        """`count` spheres on segment `seg`, from its origin toward the offset `toward`."""
+        for i in range(count):
+            f = i / max(count - 1, 1)
+            self.spheres.append(pb.Sphere(seg, float(self.rng.uniform(*radius)), float(self.rng.uniform(0.03, 0.07)),
+                                          tuple(float(v) * f for v in toward), self.segs[seg].name))
+
+    def chain(self, parent, q0, n, length, prefix="l"):
+        """n joint segments in a row (joints q0 .. q0 + n - 1); returns their indices."""
+        return [self.joint(f"{prefix}{q0 + i}", parent if i == 0 else len(self.segs) - 1, q0 + i, length)
+                for i in range(n)]
+
+    def robot(self, limits):
+        """limits[j]: None (unlimited) or (min, max)."""
+        joints = []
+        for j in range(self.J):
+            cost = float(self.rng.uniform(0.5, 2.0))
+            if limits[j] is None:
+                joints.append(pb.Joint(f"j{j}", False, joint_cost=cost))
+            else:
+                joints.append(pb.Joint(f"j{j}", True, float(limits[j][0]), float(limits[j][1]), cost))
+        return pb.Robot(self.segs, joints, [])
+
+
+def _limits(rng, start, goal, unlimited=()):
+    """Limits 0.25 rad outside the start / goal interval (the 0.05 rad random walks of the execute
+    rows cross them), except the joints listed in `unlimited`."""
+    out = []
+    for j in range(len(start)):
+        if j in unlimited:
+            out.append(None)
+        else:
+            out.append((min(start[j], goal[j]) - 0.25, max(start[j], goal[j]) + 0.25))
+    return out
+
+
+def _scene(robot, spheres, start, goal):
+    """A few boxes where the default trajectory passes: one whose face lies inside the hinge zone
+    of the last sphere at the middle waypoint, one overlapping the middle sphere's sweep, a slab."""
+    mid = 0.5 * (np.asarray(start) + np.asarray(goal))
+    pos = pb.sphere_positions(robot, spheres, mid)
+    tip, s_tip = pos[-1], spheres[-1]
+    gap = s_tip.radius + 0.5 * s_tip.clearance
+    boxes = [pb.Box(tuple(tip + np.array([gap + 0.05, 0.0, 0.0])), (0.1, 0.12, 0.12)),
+             pb.Box(tuple(pos[len(pos) // 2] + np.array([0.0, 0.04, 0.03])), (0.08, 0.08, 0.08)),
+             pb.Box((0.1, -0.4, 0.45), (0.5, 0.5, 0.06))]
+    return boxes
+
+
+def _grid(spheres, shape):
+    max_exp = max(s.radius + s.clearance for s in spheres)
+    if shape is None:
+        return pb.Grid(64, ORIGIN, RES, max_exp)
+    return pb.Grid(max(shape), ORIGIN, RES, max_exp, shape=tuple(shape))
+
+
+def _problem(b, start, goal, limits, alt, K, Kr, waypoints, shape, overrides, seed=None):
+    robot = b.robot(limits)
+    kw = dict(ALT_PARAMS) if alt else {}
+    kw.update(overrides)
+    params = pb.StompParameters(trajectory_duration=waypoints * 0.05, num_rollouts=K, num_reused_rollouts=Kr, **kw)
+    boxes = _scene(robot, b.spheres, start, goal)
+    grid = _grid(b.spheres, shape)
+    p = pb.Problem(robot, b.spheres, grid, boxes, [], params, np.array(start, np.float64), np.array(goal, np.float64),
+                   torque_root=None, torque_tip=None)
+    if seed is not None:
+        p.seed = seed
+    p.sdf = pb.build_sdf(grid, boxes, [])
+    return p
+
+
+def _start_goal(rng, J, span=1.0):
+    return rng.uniform(-span, span, J), rng.uniform(-span, span, J)
+
+
+def stick1(K=12, Kr=5, waypoints=40, shape=None, **overrides):
+    b = _Builder(101, 1)
+    s = b.joint("wand", 0, 0, 0.05)
+    tip = _dir(b.rng, 0.5)
+    b.add("wand_tip", s, -1, tip)
+    b.balls(s, tip, 6, radius=(0.04, 0.07))
+    start, goal = np.array([-0.9]), np.array([0.8])
+    return _problem(b, start, goal, _limits(b.rng, start, goal), False, K, Kr, waypoints, shape, overrides)
+
+
+def chain5(K=12, Kr=5, waypoints=40, shape=None, terms=False, **overrides):
+    """terms=True: the variant of the state-terms tests -- joint 1 drives a segment too (the torque
+    chain must hold the group's joints in order), every link has a synthetic inertia, and the
+    torque chain runs from the base to the tip."""
+    b = _Builder(105, 5)
+    rng = b.rng
+    s0 = b.joint("l0", 0, 0, 0.08)
+    t1 = _dir(rng, 0.22)
+    b.balls(s0, t1, 3)
+    parent = s0
+    if terms:
+        parent = b.joint("l1", s0, 1, 0.22)
+        s2 = b.joint("l2", parent, 2, 0.05)
+    else:
+        s2 = b.add("l2", s0, 2, t1, rot=_rot(rng), axis=_axis(rng))
+    t3 = _dir(rng, 0.3)
+    b.balls(s2, t3, 22, radius=(0.025, 0.045))         # one run of 16 and one of 6
+    s3 = b.add("l3", s2, 3, t3, rot=_rot(rng), axis=_axis(rng))
+    t4 = _dir(rng, 0.18)
+    b.balls(s3, t4, 4)
+    s4 = b.add("l4", s3, 4, t4, rot=_rot(rng), axis=_axis(rng))   # below every sphere: pruned
+    b.fixed("tip", s4, 0.1)
+    start, goal = _start_goal(rng, 5)
+    start[3] = goal[3] = 0.4
+    lim = _limits(rng, start, goal, unlimited=(2,))
+    lim[3] = (0.4, 0.4)
+    if terms:
+        for g in b.segs[1:]:
+            c = rng.uniform(-0.05, 0.05, 3)
+            d = rng.uniform(0.002, 0.02, 3)
+            o = rng.uniform(-0.001, 0.001, 3)
+            g.inertia = pb.Inertia(float(rng.uniform(0.3, 2.5)), tuple(c), (d[0], d[1], d[2], o[0], o[1], o[2]))
+    p = _problem(b, start, goal, lim, True, K, Kr, waypoints, shape, overrides)
+    if terms:
+        p.torque_root, p.torque_tip = "base", "tip"
+    return p
+
+
+def hand9(K=12, Kr=5, waypoints=40, shape=None, **overrides):
+    b = _Builder(109, 9)
+    rng = b.rng
+    arm = b.chain(0, 0, 5, 0.14)
+    for i, s in enumerate(arm):
+        nxt = b.segs[arm[i + 1]].trans if i + 1 < len(arm) else (0.05, 0.02, 0.03)
+        b.balls(s, nxt, 2)
+    palm = b.fixed("palm", arm[-1], 0.06)
+    b.balls(palm, (0.03, 0.0, 0.02), 2)
+    for f, q0 in (("a", 5), ("b", 7)):
+        f1 = b.joint(f + "1", palm, q0, 0.05)
+        t = _dir(rng, 0.07)
+        b.balls(f1, t, 2, radius=(0.02, 0.03))
+        f2 = b.add(f + "2", f1, q0 + 1, t, rot=_rot(rng), axis=_axis(rng))
+        b.balls(f2, _dir(rng, 0.06), 3, radius=(0.02, 0.03))
+    start, goal = _start_goal(rng, 9)
+    return _problem(b, start, goal, _limits(rng, start, goal, unlimited=(2, 6)), False, K, Kr, waypoints, shape,
+                    overrides)
+
+
+def _fork(J, seed, alt, nested, K, Kr, waypoints, shape, overrides):
+    """A serial chain of J joints, then a fixed palm that forks into two fixed prongs (nested: the
+    first prong forks again): every save comes after the last joint."""
+    b = _Builder(seed, J)
+    rng = b.rng
+    length = 0.9 / J
+    arm = b.chain(0, 0, J, length)
+    every = 1 if J <= 13 else 2
+    for i, s in enumerate(arm):
+        if i % every == 0 and i + 1 < len(arm):
+            b.balls(s, b.segs[arm[i + 1]].trans, 2)
+    palm = b.fixed("palm", arm[-1], 0.05, rotated=False)
+    b.balls(palm, (0.02, 0.01, 0.0), 2)
+    pa = b.fixed("prong_a", palm, 0.05)
+    b.balls(pa, _dir(rng, 0.05), 2, radius=(0.02, 0.035))
+    if nested:
+        for k in ("a1", "a2"):
+            s = b.fixed("prong_" + k, pa, 0.04, rotated=(k == "a1"))
+            b.balls(s, _dir(rng, 0.04), 2, radius=(0.02, 0.03))
+    pb_ = b.fixed("prong_b", palm, 0.05, rotated=False)
+    b.balls(pb_, _dir(rng, 0.05), 2, radius=(0.02, 0.035))
+    start, goal = _start_goal(rng, J, 0.8)
+    return _problem(b, start, goal, _limits(rng, start, goal, unlimited=tuple(range(2, J, 3))), alt, K, Kr, waypoints,
+                    shape, overrides)
+
+
+def fork12(K=12, Kr=5, waypoints=40, shape=None, **overrides):
+    return _fork(12, 112, True, False, K, Kr, waypoints, shape, overrides)
+
+
+def fork13(K=12, Kr=5, waypoints=40, shape=None, **overrides):
+    return _fork(13, 113, False, False, K, Kr, waypoints, shape, overrides)
+
+
+def fork24(K=12, Kr=5, waypoints=40, shape=None, **overrides):
+    return _fork(24, 124, False, True, K, Kr, waypoints, shape, overrides)
+
+
+def _serial(J, seed, alt, K, Kr, waypoints, shape, overrides):
+    b = _Builder(seed, J)
+    rng = b.rng
+    arm = b.chain(0, 0, J, 0.9 / J)
+    for i, s in enumerate(arm):
+        if i % 2 == 0:
+            nxt = b.segs[arm[i + 1]].trans if i + 1 < len(arm) else _dir(rng, 0.05)
+            b.balls(s, nxt, 2)
+    start, goal = _start_goal(rng, J, 0.8)
+    return _problem(b, start, goal, _limits(rng, start, goal, unlimited=tuple(range(2, J, 3))), alt, K, Kr, waypoints,
+                    shape, overrides)
+
+
+def chain17(K=12, Kr=5, waypoints=40, shape=None, **overrides):
+    return _serial(17, 117, True, K, Kr, waypoints, shape, overrides)
+
+
+def chain32(K=12, Kr=5, waypoints=40, shape=None, **overrides):
+    return _serial(32, 132, True, K, Kr, waypoints, shape, overrides)
+
+
+ZOO = dict(stick1=stick1, chain5=chain5, hand9=hand9, fork12=fork12, fork13=fork13, chain17=chain17, fork24=fork24,
+           chain32=chain32)
+
+
+def three_saves():
+    """A tree the engine refuses: three nested forks need three saved frames (kSaves = 2)."""
+    b = _Builder(203, 2)
+    rng = b.rng
+    arm = b.chain(0, 0, 2, 0.2)
+    b.balls(arm[0], b.segs[arm[1]].trans, 2)
+    forks = []
+    parent = arm[1]
+    for level in range(3):        # DFS order: fork0, fork1, fork2, leaf, then the side branches
+        parent = b.fixed(f"fork{level}", parent, 0.05)
+        b.balls(parent, (0.02, 0.0, 0.0), 1)
+        forks.append(parent)
+    leaf = b.fixed("leaf", parent, 0.05)
+    b.balls(leaf, (0.02, 0.0, 0.0), 1)
+    for level in (2, 1, 0):
+        s = b.fixed(f"side{level}", forks[level], 0.04)
+        b.balls(s, (0.01, 0.0, 0.0), 1)
+    start, goal = _start_goal(rng, 2)
+    return _problem(b, start, goal, _limits(rng, start, goal), False, 12, 0, 40, None, {})
+
+
+def unordered_spheres():
+    """chain5 with two spheres of different segments swapped: the list is not ordered by segment."""
+    p = chain5()
+    i = next(k for k in range(len(p.spheres) - 1) if p.spheres[k].segment != p.spheres[k + 1].segment)
+    p.spheres[i], p.spheres[i + 1] = p.spheres[i + 1], p.spheres[i]
+    return p
+
+
+def wand(face, shape=NONCUBIC, waypoints=40):
+    """A one-joint wand whose single sphere sweeps across one face of the grid in about a cell per
+    waypoint.  face = (axis, side): side 0 the low face (indices 1, 0, -1 ...), side 1 the high one
+    (n - 2, n - 1 ...).  The arm lies along a second axis and swings about the third, so at q = 0
+    the sphere sits on the face's threshold (cell index 0.5 or n - 1.5) and q moves it along
+    `axis` by arm sin(q): +-0.4 rad is +-7.5 cells over the 39 waypoints (0.65 cells per waypoint
+    at the middle of the minimum-control-cost trajectory).  The joint axis is a
+    unit axis on purpose: the sweep stays in one plane and crosses one face only."""
+    axis, side = face
+    rot_axis, arm_axis = [a for a in range(3) if a != axis]
+    arm, span = 0.6, 0.4
+    centre = [ORIGIN[a] + 0.5 * shape[a] * RES for a in range(3)]
+    edge = ORIGIN[axis] + (shape[axis] - 1.5 if side else 0.5) * RES
+    pivot = list(centre)
+    pivot[axis] = edge
+    pivot[arm_axis] = centre[arm_axis] - arm
+    tip = tuple(_unit(arm_axis, arm))
+    segs = [pb.Segment("base", -1, -1, tuple(pivot)),
+            pb.Segment("wand", 0, 0, (0.0, 0.0, 0.0), tuple(_unit(rot_axis, 1.0))),
+            pb.Segment("wand_tip", 1, -1, tip)]
+    spheres = [pb.Sphere(1, 0.04, 0.05, tip, "wand")]
+    robot = pb.Robot(segs, [pb.Joint("swing", False)], [])
+    sign = _swing_sign(axis, rot_axis, arm_axis, side)
+    start, goal = np.array([-sign * span]), np.array([sign * span])    # from inside the field to outside
+    params = pb.StompParameters(trajectory_duration=waypoints * 0.05, num_rollouts=12, num_reused_rollouts=0)
+    grid = pb.Grid(max(shape), ORIGIN, RES, 0.09, shape=tuple(shape))
+    slab_c, slab_d = list(centre), [0.3, 0.3, 0.3]      # a slab three cells inside the face
+    slab_c[axis] = edge + (-3.5 * RES if side else 3.5 * RES)
+    slab_d[axis] = RES
+    boxes = [pb.Box(tuple(slab_c), tuple(slab_d))]
+    p = pb.Problem(robot, spheres, grid, boxes, [], params, start, goal, torque_root=None, torque_tip=None)
+    p.sdf = pb.build_sdf(grid, boxes, [])
+    return p
+
+
+def _unit(a, length):
+    v = [0.0, 0.0, 0.0]
+    v[a] = length
+    return v
+
+
+def _swing_sign(axis, rot_axis, arm_axis, side):
+    """Sign of q that moves a point on +arm_axis toward +axis (side 1) or -axis (side 0) when
+    rotating about +rot_axis: d/dq (e_rot x e_arm) = +-e_axis."""
+    e = np.cross(np.eye(3)[rot_axis], np.eye(3)[arm_axis])[axis]
+    return (1.0 if e > 0 else -1.0) * (1.0 if side else -1.0)
+
+
+FACES = [(a, s) for a in range(3) for s in (0, 1)]
+
+
+# ----------------------------------------------------------------- census (numpy only)
+
+def census(problem, rows):
+    """What the rows handed to execute reach, by the numpy restatement alone (problem.py's FK and
+    cell rule, numpy_oracle's joint limits): a condition on a test's inputs, not a measurement.
+
+    rows_limited: rows in which joint limits changed the trajectory; and counts of sphere-waypoint
+    lookups: out_lo / out_hi [axis] (past each of the six faces), at_1 / at_n2 [axis] (in bounds
+    at index 1 / n - 2), collision (d <= radius), hinge (radius < d < radius + clearance), free."""
+    from oracle import numpy_oracle as npo
+    p = problem
+    n = npo.NumpyStomp(p)
+    rows = np.asarray(rows, np.float64).reshape(-1, p.J, p.N)
+    g = p.grid
+    dims = np.array(g.dims, np.float64)
+    out = dict(rows=len(rows), rows_limited=0, out_lo=[0, 0, 0], out_hi=[0, 0, 0], at_1=[0, 0, 0], at_n2=[0, 0, 0],
+               collision=0, hinge=0, free=0, out=0)
+    radius = np.array([s.radius for s in p.spheres])
+    clear = np.array([s.clearance for s in p.spheres])
+    for r in rows:
+        traj = n.joint_limits(r)
+        if not np.array_equal(traj, r):
+            out["rows_limited"] += 1
+        pos = np.stack([pb.sphere_positions(p.robot, p.spheres, traj[:, t]) for t in range(p.N)])
+        f = pb.c_round((pos - np.array(g.origin)) * (1.0 / g.resolution))
+        inb = np.all((f >= 1) & (f < dims - 1), axis=-1)
+        for a in range(3):
+            out["out_lo"][a] += int(np.sum(f[..., a] < 1))
+            out["out_hi"][a] += int(np.sum(f[..., a] >= dims[a] - 1))
+            out["at_1"][a] += int(np.sum(inb & (f[..., a] == 1)))
+            out["at_n2"][a] += int(np.sum(inb & (f[..., a] == dims[a] - 2)))
+        d = pb.sdf_lookup(p, pos)
+        out["out"] += int(np.sum(~inb))
+        col = d <= radius[None, :]
+        hinge = ~col & (d - radius[None, :] < clear[None, :])
+        out["collision"] += int(np.sum(col & inb))
+        out["hinge"] += int(np.sum(hinge))
+        out["free"] += int(np.sum(~col & ~hinge))
+    return out
+
+
+def execute_rows(problem, theta, rows=6, seed=3, scale=0.05):
+    """The perturbations of tests/test_gpu_parity.py::test_execute_bitwise: random walks of 0.05
+    rad per waypoint around theta, row 0 theta itself, the last row shifted by +3.0 rad."""
+    rng = np.random.default_rng(seed)
+    params = theta[None] + rng.standard_normal((rows, problem.J, problem.N)).cumsum(axis=2) * scale
+    params[0] = theta
+    params[rows - 1] += 3.0
+    return params
+
+
+def fk_plan(problem):
+    """plan_fk's choices (engine.cpp) restated on the host: (nsaves, sincos_pre, sph_chunk, pruned
+    segment count).  The CPU tests assert the zoo reaches what its table says."""
+    p = problem
+    segs = p.robot.segments
+    ns = len(segs)
+    needed = [False] * ns
+    for s in p.spheres:
+        a = s.segment
+        while a >= 0 and not needed[a]:
+            needed[a] = True
+            a = segs[a].parent
+    remaining = [0] * ns
+    for s in range(ns):
+        if needed[s] and segs[s].parent >= 0:
+            remaining[segs[s].parent] += 1
+    runmax = 16 if p.N <= 128 else 8
+    used, slot_of = [False, False], [-1] * ns
+    nsaves, last_joint, first_save, op, chunk = 0, -1, None, 0, 1
+    for s in range(ns):
+        if not needed[s]:
+            continue
+        par = segs[s].parent
+        if par >= 0:
+            remaining[par] -= 1
+            if remaining[par] == 0 and slot_of[par] >= 0:
+                used[slot_of[par]] = False
+                slot_of[par] = -1
+        if remaining[s] >= 2:
+            free = [k for k in range(2) if not used[k]]
+            if not free:
+                return None
+            used[free[0]] = True
+            slot_of[s] = free[0]
+            nsaves = max(nsaves, free[0] + 1)
+            if first_save is None:
+                first_save = op
+        if segs[s].q_index >= 0:
+            last_joint = op
+        cnt = sum(1 for q in p.spheres if q.segment == s)
+        chunk = max(chunk, min(cnt, runmax))
+        op += max(1, -(-cnt // runmax))
+    if first_save is None:
+        first_save = op
+    pre = int(nsaves >= 1 and p.J <= 12 * nsaves and first_save > last_joint)
+    return dict(nsaves=nsaves, sincos_pre=pre, sph_chunk=chunk, pruned=ns - sum(needed), nops=op)
