@@ -138,7 +138,7 @@ static double dotcol(const double* v, const double* B, int k)
  *      side.  Facets are emitted in the order of their triples, a plane equal to one already
  *      emitted (same normal and offset test) skipped.
  * eps = 1e-9 (1 + max |coordinate|).  O(V log V + V F) instead of the O(V^4) triple scan.  The
- * engine (csrc/engine.cpp hull_planes) implements the same steps in C++. */
+ * engine (csrc/sdf_build.cpp hull_planes) implements the same steps in C++. */
 typedef struct {
     int v[3];
     double n[3], d;

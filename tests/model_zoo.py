@@ -3,7 +3,7 @@
 Every parity test used to build its problem with problem.make_problem: two robots, unit joint
 axes, identity fixed rotations, one cubic grid, one set of cost weights.  The builders here are
 deterministic (seeded, no files) and each returns a problem.Problem that reaches device code the
-PR2 fixture cannot (stomp_engine_create's plan_fk choices, engine.cpp: nsaves, sincos_pre, split
+PR2 fixture cannot (stomp_engine_create's plan_fk choices, engine_create.cpp: nsaves, sincos_pre, split
 sphere runs, pruned segments; the joint-count branches of the noise kernels):
 
     stick1    J = 1, serial, one sphere link: nsaves = 0
@@ -419,7 +419,7 @@ def execute_rows(problem, theta, rows=6, seed=3, scale=0.05):
 
 
 def fk_plan(problem):
-    """plan_fk's choices (engine.cpp) restated on the host: (nsaves, sincos_pre, sph_chunk, pruned
+    """plan_fk's choices (engine_create.cpp) restated on the host: (nsaves, sincos_pre, sph_chunk, pruned
     segment count).  The CPU tests assert the zoo reaches what its table says."""
     p = problem
     segs = p.robot.segments

@@ -115,7 +115,7 @@ def test_two_rank_reduction_is_bitwise_single_rank():
         np.testing.assert_array_equal(theta, ref["theta1"])
 
 
-# ---- gather mode (STOMP_SHARD_MODE=gather, engine.cpp exchange_state): every rank makes and prices
+# ---- gather mode (STOMP_SHARD_MODE=gather, engine_exchange.cpp exchange_state): every rank makes and prices
 # the noise rows of all K rollouts (counter-based noise: the full noise / control rows here stand
 # for that regeneration), evaluates only its own rows' state costs, and ONE all-gather of the
 # state-cost rows gives every rank the whole cost matrix; the weights and the update then run
@@ -177,7 +177,7 @@ def test_two_rank_gather_mode_is_bitwise_single_rank():
         np.testing.assert_array_equal(theta, ref["theta1"])
 
 
-# ---- rollout reuse across ranks (K_r > 0; engine.cpp begin_generate, k_misc.hip k_reuse_*):
+# ---- rollout reuse across ranks (K_r > 0; engine.cpp run_reuse, k_misc.hip k_reuse_*):
 # every rank prices its own rows (Rollout::getCost, policy_improvement.cpp:149-156), the totals
 # are all-gathered, every rank ranks all K + 1 candidates the way std::sort orders the
 # (cost, index) pairs (the extra rollout at index -1, :176-205), the owners pack the chosen rows
