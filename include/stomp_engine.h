@@ -125,7 +125,11 @@ typedef struct stomp_orientation_constraint {
 typedef struct stomp_engine_desc {
     int32_t abi_version;        /* STOMP_ENGINE_ABI_VERSION */
     int32_t num_joints;         /* J (planning group joints) */
-    int32_t num_time_steps;     /* N free waypoints (params.yaml num_time_steps) */
+    int32_t num_time_steps;     /* N free waypoints (params.yaml num_time_steps), at most 256; the
+                                 * lower bound comes from the discretization: the reference's integer
+                                 * movement duration int((N + 11) * discretization) must be >= 1
+                                 * (N >= 9 at 0.05), else the control cost matrix is not positive
+                                 * definite and creation is refused */
     int32_t num_rollouts;       /* K (params.yaml num_rollouts), whole job */
     int32_t num_reused_rollouts;/* K_r (params.yaml num_reused_rollouts) */
     int32_t num_segments;
@@ -390,6 +394,8 @@ int stomp_comm_local_id(int32_t world_size, void* out128);
 /* deterministic math + RNG primitives evaluated on the device (parity tests) */
 int stomp_device_selftest(const double* x, int32_t n, double* out_exp, double* out_log, double* out_sin,
                           double* out_cos, double* out_sqrt);
+/* atan2(y[i], x[i]) and asin(y[i]) as the orientation-constraint term evaluates them on the device */
+int stomp_device_selftest_trig(const double* y, const double* x, int32_t n, double* out_atan2, double* out_asin);
 int stomp_device_normals(uint64_t seed, int32_t iteration, int32_t joint, int32_t rollout, int32_t n, double* z);
 
 #ifdef __cplusplus

@@ -775,9 +775,9 @@ int finish_model(stomp_engine* e, const stomp_engine_desc* d)
         const char* body = P ? "split" : nro <= m.cus ? (m.phased_lds > 0 ? "phased" : "wide")
                                                       : (m.lean ? "lean slot loop" : "slot loop");
         fprintf(stderr, "stomp: model J %d N %d S %d nseg %d nops %d nsaves %d sincos_pre %d sph_chunk %d lean %d "
-                        "pregen %d fused_noise %d brick %d, launch of %d rollouts: %s, %d pieces\n",
+                        "pregen %d fused_noise %d brick %d, launch of %d rollouts: %s, %d pieces, weights %s\n",
                 J, N, e->S, m.nseg, m.nops, m.nsaves, m.sincos_pre, m.sph_chunk, m.lean, e->pre_on ? 1 : 0,
-                J <= 16 ? 1 : 0, m.brick, nro, body, P);
+                J <= 16 ? 1 : 0, m.brick, nro, body, P, weights_kernel_name(e->K_loc, !e->split_modes, false));
     }
     return 0;
 }

@@ -85,6 +85,10 @@ int stomp_group_create(stomp_engine* const* engines, int32_t n, stomp_group** ou
         stomp_group_destroy(g);
         return gfail(nullptr, STOMP_E_DEVICE, "group allocation failed");
     }
+    if (getenv("STOMP_DEBUG_LEAN_PRINT"))   // the group's own choices (read-only: tests and tables)
+        fprintf(stderr, "stomp: group of %d engines J %d N %d K %d brick %d, %d weights tiles per engine, "
+                        "weights %s\n", (int)n, e0->J, e0->N, e0->K_loc, e0->model.brick, nt,
+                weights_kernel_name(e0->K_loc, true, true));
     *out = g;
     return 0;
 }

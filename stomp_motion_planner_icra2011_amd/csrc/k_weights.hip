@@ -704,27 +704,74 @@ static void launch_rows_t(const WeightArgs& a, hipStream_t s)
     hipLaunchKernelGGL((k_weights_rows<BLOCK, TCW, EPT>), dim3(nw), dim3(BLOCK), lds, s, a);
 }
 
+// columns per tile of the grouped weights launch: eight while K_loc <= 128 (a group's launch has
+// engines x tiles workgroups, many rounds of them: wider tiles halve the rounds at the same per-lane
+// work, since a tile's time is its dependent phases, not its columns; cfg5 65 -> 44 us,
+// profiles/ab/r6_group_weights_fk.txt), else four
+static int group_tcw(int K_loc)
+{
+    return K_loc <= 128 && (K_loc + kSumBlock - 1) / kSumBlock * 8 <= 256 ? 8 : 4;
+}
+
+// The one choice of weights kernel, for launch_weights (group = false) and launch_weights_group
+// (group = true: the rows path at every K_loc, its own tile width up to 128 rollouts); the
+// launchers switch on it and weights_kernel_name prints it, so the name an engine reports is the
+// instantiation it launches.
+enum WeightsKernel {
+    WK_NONE, WK_WAVE, WK_ROWS_256_8_4, WK_ROWS_256_4_4, WK_ROWS_512_4_4, WK_ROWS_512_4_8, WK_ROWS_256_4_32,
+    WK_ROWS_256_2_32, WK_COLS_8, WK_COLS_16
+};
+
+static WeightsKernel weights_kernel(int K, bool fused, bool group)
+{
+    if (!group && fused && K <= kSumBlock) return WK_WAVE;   // one canonical block: a wave per column
+    const int tcw = rows_tcw(K);
+    if (tcw == 4) {
+        if (group && group_tcw(K) == 8) return WK_ROWS_256_8_4;   // 32 rows a pass
+        if (K <= 4 * 64) return WK_ROWS_256_4_4;   // few rows: the wider tile only waits longer
+        if (K <= 4 * 128) return WK_ROWS_512_4_4;
+        if (K <= 8 * 128) return WK_ROWS_512_4_8;
+        return WK_ROWS_256_4_32;
+    }
+    if (group) return WK_NONE;   // a group takes the four-column row tiles or nothing
+    // (512 lanes with 16 rows each: 159 VGPRs, one workgroup per CU, 96.5 against 81 us at
+    // cfg3, profiles/ab/r6_weights_512.txt)
+    if (tcw == 2) return WK_ROWS_256_2_32;
+    return (size_t)K * weights_tile(K) <= 2048 ? WK_COLS_8 : WK_COLS_16;
+}
+
+const char* weights_kernel_name(int K_loc, bool fused, bool group)
+{
+    switch (weights_kernel(K_loc, fused, group)) {
+    case WK_WAVE: return "wave";
+    case WK_ROWS_256_8_4: return "rows<256,8,4>";
+    case WK_ROWS_256_4_4: return "rows<256,4,4>";
+    case WK_ROWS_512_4_4: return "rows<512,4,4>";
+    case WK_ROWS_512_4_8: return "rows<512,4,8>";
+    case WK_ROWS_256_4_32: return "rows<256,4,32>";
+    case WK_ROWS_256_2_32: return "rows<256,2,32>";
+    case WK_COLS_8: return "columns<8>";
+    case WK_COLS_16: return "columns<16>";
+    default: return "none";
+    }
+}
+
 void launch_weights(const WeightArgs& a, hipStream_t s)
 {
-    const int K = a.K_loc;
-    if (a.mode == W_FUSED && K <= kSumBlock) {   // one canonical block: a wave per column
+    switch (weights_kernel(a.K_loc, a.mode == W_FUSED, false)) {
+    case WK_WAVE:
         hipLaunchKernelGGL(k_weights_wave, dim3((a.J * a.N + 3) / 4), dim3(256), 0, s, a);
         return;
-    }
-    switch (rows_tcw(K)) {
-    case 4:
-        if (K <= 4 * 64) return launch_rows_t<256, 4, 4>(a, s);   // few rows: the wider tile only waits longer
-        if (K <= 4 * 128) return launch_rows_t<512, 4, 4>(a, s);
-        if (K <= 8 * 128) return launch_rows_t<512, 4, 8>(a, s);
-        if (K <= 16 * 64) return launch_rows_t<256, 4, 16>(a, s);
-        return launch_rows_t<256, 4, 32>(a, s);
-    case 2:
-        // (512 lanes with 16 rows each: 159 VGPRs, one workgroup per CU, 96.5 against 81 us at
-        // cfg3, profiles/ab/r6_weights_512.txt)
-        return launch_rows_t<256, 2, 32>(a, s);
+    case WK_ROWS_256_4_4: return launch_rows_t<256, 4, 4>(a, s);
+    case WK_ROWS_512_4_4: return launch_rows_t<512, 4, 4>(a, s);
+    case WK_ROWS_512_4_8: return launch_rows_t<512, 4, 8>(a, s);
+    case WK_ROWS_256_4_32: return launch_rows_t<256, 4, 32>(a, s);
+    case WK_ROWS_256_2_32: return launch_rows_t<256, 2, 32>(a, s);
     default:
         break;
     }
+    // the column tiles: EPT from the tile width the caller set (a.tc = weights_tile(K_loc), which is
+    // what weights_kernel assumes), since the kernel's bound K_loc * tc <= EPT * 256 is on that one
     dim3 grid((a.N + a.tc - 1) / a.tc, a.J);
     const size_t lds = (size_t)a.K_loc * a.tc * sizeof(double);
     if ((size_t)a.K_loc * a.tc <= 2048)
@@ -831,15 +878,6 @@ void launch_update_group(int J, int N, const UpdateArgs* as, int engines, hipStr
 }
 
 // the rows path of launch_weights for a group (the engine checks weights_group_tiles() > 0)
-// columns per tile of the grouped weights launch: eight while K_loc <= 128 (a group's launch has
-// engines x tiles workgroups, many rounds of them: wider tiles halve the rounds at the same per-lane
-// work, since a tile's time is its dependent phases, not its columns; cfg5 65 -> 44 us,
-// profiles/ab/r6_group_weights_fk.txt), else four
-static int group_tcw(int K_loc)
-{
-    return K_loc <= 128 && (K_loc + kSumBlock - 1) / kSumBlock * 8 <= 256 ? 8 : 4;
-}
-
 int weights_group_tiles(int J, int N, int K_loc)
 {
     if (rows_tcw(K_loc) != 4) return 0;
@@ -859,12 +897,14 @@ void launch_weights_group(const WeightArgs* as, int engines, int J, int N, int K
 {
     const int nt = weights_group_tiles(J, N, K_loc);
     if (nt <= 0 || engines <= 0) return;
-    if (group_tcw(K_loc) == 8) return launch_rows_group_t<256, 8, 4>(as, engines, nt, K_loc, s);   // 32 rows a pass
-    if (K_loc <= 4 * 64) return launch_rows_group_t<256, 4, 4>(as, engines, nt, K_loc, s);
-    if (K_loc <= 4 * 128) return launch_rows_group_t<512, 4, 4>(as, engines, nt, K_loc, s);
-    if (K_loc <= 8 * 128) return launch_rows_group_t<512, 4, 8>(as, engines, nt, K_loc, s);
-    if (K_loc <= 16 * 64) return launch_rows_group_t<256, 4, 16>(as, engines, nt, K_loc, s);
-    return launch_rows_group_t<256, 4, 32>(as, engines, nt, K_loc, s);
+    switch (weights_kernel(K_loc, true, true)) {
+    case WK_ROWS_256_8_4: return launch_rows_group_t<256, 8, 4>(as, engines, nt, K_loc, s);
+    case WK_ROWS_256_4_4: return launch_rows_group_t<256, 4, 4>(as, engines, nt, K_loc, s);
+    case WK_ROWS_512_4_4: return launch_rows_group_t<512, 4, 4>(as, engines, nt, K_loc, s);
+    case WK_ROWS_512_4_8: return launch_rows_group_t<512, 4, 8>(as, engines, nt, K_loc, s);
+    case WK_ROWS_256_4_32: return launch_rows_group_t<256, 4, 32>(as, engines, nt, K_loc, s);
+    default: return;   // weights_group_tiles() > 0 leaves the five above
+    }
 }
 
 void launch_update(int J, int N, const double* MT, const double* u, const double* u_all, int nb_total, double* theta,

@@ -405,6 +405,9 @@ constexpr size_t kRolloutLdsMax = 156 * 1024;                // dynamic + static
 void launch_cumulative(const WeightArgs& a, double* cum, hipStream_t s);
 void launch_weights(const WeightArgs& a, hipStream_t s);
 int weights_tile(int K_loc);
+// the kernel launch_weights (group = false; fused: mode W_FUSED) or launch_weights_group takes for
+// K_loc rollouts, as "wave", "rows<BLOCK,TCW,EPT>", "columns<EPT>" or "none" (debug prints)
+const char* weights_kernel_name(int K_loc, bool fused, bool group);
 // theta += M u; with delta: delta = M u and theta untouched
 void launch_update(int J, int N, const double* MT, const double* u, const double* u_all, int nb_total,
                    double* theta, const int* stop, hipStream_t s, double* delta = nullptr);

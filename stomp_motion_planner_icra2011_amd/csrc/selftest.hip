@@ -20,6 +20,14 @@ __global__ void k_math(const double* x, int n, double* e, double* l, double* s, 
     q[i] = v >= 0.0 ? sqrt(v) : 0.0;
 }
 
+__global__ void k_trig(const double* y, const double* x, int n, double* a, double* s)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    a[i] = stomp::det_atan2(y[i], x[i]);
+    s[i] = stomp::det_asin(y[i]);
+}
+
 __global__ void k_normals(uint64_t seed, int it, int joint, int rollout, int n, double* z)
 {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -48,6 +56,23 @@ extern "C" int stomp_device_selftest(const double* x, int32_t n, double* oe, dou
         hipMemcpy(os, d + 3 * n, sizeof(double) * n, hipMemcpyDeviceToHost);
         hipMemcpy(oc, d + 4 * n, sizeof(double) * n, hipMemcpyDeviceToHost);
         hipMemcpy(oq, d + 5 * n, sizeof(double) * n, hipMemcpyDeviceToHost);
+    }
+    hipFree(d);
+    return st == hipSuccess ? 0 : STOMP_E_DEVICE;
+}
+
+extern "C" int stomp_device_selftest_trig(const double* y, const double* x, int32_t n, double* oa, double* os)
+{
+    if (n <= 0) return 0;
+    double* d = nullptr;
+    if (hipMalloc(&d, sizeof(double) * n * 4) != hipSuccess) return STOMP_E_DEVICE;
+    hipMemcpy(d, y, sizeof(double) * n, hipMemcpyHostToDevice);
+    hipMemcpy(d + n, x, sizeof(double) * n, hipMemcpyHostToDevice);
+    hipLaunchKernelGGL(k_trig, dim3((n + 255) / 256), dim3(256), 0, 0, d, d + n, n, d + 2 * n, d + 3 * n);
+    hipError_t st = hipDeviceSynchronize();
+    if (st == hipSuccess) {
+        hipMemcpy(oa, d + 2 * n, sizeof(double) * n, hipMemcpyDeviceToHost);
+        hipMemcpy(os, d + 3 * n, sizeof(double) * n, hipMemcpyDeviceToHost);
     }
     hipFree(d);
     return st == hipSuccess ? 0 : STOMP_E_DEVICE;

@@ -101,7 +101,11 @@ std::string compute_setup(const SetupInput& in, SetupOutput& out)
     // (stomp_trajectory.cpp:86, stomp_trajectory.h:141,255-258)
     int duration = (int)((double)(Nall - 1) * in.discretization);
     out.dt = (double)duration / (double)(N + 1);
-    if (!(out.dt > 0.0)) return "trajectory duration truncates to zero (getDuration() returns int)";
+    // (the reference goes on with infinite differentiation matrices; its control cost matrix is then
+    // not positive definite, which is what the oracle reports)
+    if (!(out.dt > 0.0))
+        return "trajectory duration truncates to zero (getDuration() returns int): the control cost matrix is "
+               "not positive definite";
 
     double mult = 1.0;
     for (int d = 0; d < kNumDiffRules; ++d) {

@@ -93,7 +93,7 @@ EXPORTED = ["stomp_engine_create", "stomp_engine_destroy", "stomp_engine_last_er
             "stomp_stream_create", "stomp_stream_destroy", "stomp_group_create", "stomp_group_run",
             "stomp_group_synchronize", "stomp_group_last_error", "stomp_group_destroy", "stomp_engine_shard_mode",
             "stomp_engine_shard_info", "stomp_shard_decide", "stomp_engine_source_hash",
-            "stomp_engine_refresh_field"]
+            "stomp_engine_refresh_field", "stomp_device_selftest_trig"]
 
 _lib = None
 
@@ -172,6 +172,7 @@ def load_library(path: Optional[str] = None):
     l.stomp_device_count.argtypes = [C.POINTER(C.c_int32)]
     l.stomp_diff_rules.argtypes = [dp]
     l.stomp_device_selftest.argtypes = [dp, C.c_int32, dp, dp, dp, dp, dp]
+    l.stomp_device_selftest_trig.argtypes = [dp, dp, C.c_int32, dp, dp]
     l.stomp_device_normals.argtypes = [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp]
     _lib = l
     return l
@@ -581,6 +582,16 @@ def device_math(x: np.ndarray):
     outs = [np.zeros(n) for _ in range(5)]
     _check(load_library().stomp_device_selftest(_dp(x), n, *[_dp(o) for o in outs]))
     return outs
+
+
+def device_trig(y: np.ndarray, x: np.ndarray):
+    """(atan2(y, x), asin(y)) elementwise by the device's det_atan2 / det_asin."""
+    y = np.ascontiguousarray(y, np.float64)
+    x = np.ascontiguousarray(x, np.float64)
+    assert y.shape == x.shape and y.ndim == 1
+    a, s = np.zeros(len(y)), np.zeros(len(y))
+    _check(load_library().stomp_device_selftest_trig(_dp(y), _dp(x), len(y), _dp(a), _dp(s)))
+    return a, s
 
 
 def device_normals(seed: int, iteration: int, joint: int, rollout: int, n: int) -> np.ndarray:

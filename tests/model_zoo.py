@@ -166,11 +166,13 @@ def stick1(K=12, Kr=5, waypoints=40, shape=None, **overrides):
     return _problem(b, start, goal, _limits(b.rng, start, goal), False, K, Kr, waypoints, shape, overrides)
 
 
-def chain5(K=12, Kr=5, waypoints=40, shape=None, terms=False, **overrides):
-    """terms=True: the variant of the state-terms tests -- joint 1 drives a segment too (the torque
+def chain5(K=12, Kr=5, waypoints=40, shape=None, terms=False, robot_seed=105, **overrides):
+    """robot_seed: another seed gives a robot of the same structure (segments, joints, sphere counts)
+    with other rotations, axes, offsets, radii, limits, start and goal, and its own scene.
+    terms=True: the variant of the state-terms tests -- joint 1 drives a segment too (the torque
     chain must hold the group's joints in order), every link has a synthetic inertia, and the
     torque chain runs from the base to the tip."""
-    b = _Builder(105, 5)
+    b = _Builder(robot_seed, 5)
     rng = b.rng
     s0 = b.joint("l0", 0, 0, 0.08)
     t1 = _dir(rng, 0.22)

@@ -18,7 +18,8 @@ from stomp_motion_planner_icra2011_amd import engine as eng
 from stomp_motion_planner_icra2011_amd import problem as pb
 from tests import model_zoo as mz
 from tests.test_gpu_parity import _compare_iteration
-from tests.test_model_space import NONCUBIC_CASES, PLAN, _noncubic_scene, assert_execute_census
+from tests.test_model_space import (N_EXTREME_MODELS, N_EXTREMES, NONCUBIC_CASES, PLAN, _noncubic_scene,
+                                    assert_execute_census)
 
 pytestmark = pytest.mark.gpu
 
@@ -287,6 +288,97 @@ def test_degenerate_weights_bitwise():
         assert not o.rollouts("noise").any()
         np.testing.assert_array_equal(e.rollouts("probabilities"), np.full((K, p.J, p.N), 1.0 / K))
     np.testing.assert_array_equal(e.theta(), o.theta())
+
+
+# ---------------------------------------------------------------------------- N extremes
+# stomp_engine_create takes N in [1, 256]; N <= 256 is the one-lane-per-waypoint limit of every
+# rollout body, and the 0.05 discretization gives no positive definite control cost below N = 9.
+# tests/test_model_space.py holds the oracle to the numpy restatement at the same four N.
+N_CASES = [(m, n) for m in sorted(N_EXTREME_MODELS) for n in sorted(N_EXTREMES)]
+# the body launch_cost takes (the engine's own account, STOMP_DEBUG_LEAN_PRINT).  At N >= 255 the
+# phased body's LDS does not fit and the one-workgroup launch is the wide body; the PR2 fixture's
+# full layout (104 KB) leaves one workgroup per compute unit there, so creation picks the lean
+# slot loop for 261 rollouts
+N_BODIES = {(m, n, b): {"split": "split", "phased": "phased" if n < 255 else "wide",
+                        "slot": "lean slot loop" if (m == "pr2" and n >= 255) else "slot loop"}[b]
+            for m, n in N_CASES for b in ("split", "phased", "slot")}
+
+
+@pytest.mark.parametrize("model,N", N_CASES)
+def test_n_extremes_setup_bitwise(model, N):
+    p = N_EXTREME_MODELS[model](N_EXTREMES[N])
+    assert p.N == N
+    o, e = pair(p)
+    for m in ("Rinv", "L", "M"):
+        np.testing.assert_array_equal(e.matrix(m), o.matrix(m), err_msg=m)
+    for j in range(p.J):
+        np.testing.assert_array_equal(e.matrix("Qinv", j), o.matrix("Qinv", j), err_msg=f"Qinv {j}")
+    np.testing.assert_array_equal(e.theta(), o.theta())
+    np.testing.assert_array_equal(e.pad_positions(), o.pad_positions())
+
+
+@pytest.mark.parametrize("body", ["split", "phased"])
+@pytest.mark.parametrize("model,N", N_CASES)
+def test_n_extremes_rollout_bodies_bitwise(monkeypatch, capfd, model, N, body):
+    # K = 12, K_r = 5 as test_rollout_bodies_bitwise: the waypoint-split launch where the shape
+    # allows one (N_BODIES), and the one-workgroup body (STOMP_DEBUG_SPLIT_MAX=1)
+    monkeypatch.setenv("STOMP_DEBUG_LEAN_PRINT", "1")
+    if body == "phased":
+        monkeypatch.setenv("STOMP_DEBUG_SPLIT_MAX", "1")
+    p = N_EXTREME_MODELS[model](N_EXTREMES[N], K=12, Kr=5)
+    o, e = pair(p)
+    assert f"launch of 13 rollouts: {N_BODIES[model, N, body]}," in model_line(capfd)
+    for it in range(1, 4):
+        _compare_iteration(o, e, it)
+
+
+@pytest.mark.parametrize("model,N", N_CASES)
+def test_n_extremes_slot_loop_bitwise(monkeypatch, capfd, model, N):
+    monkeypatch.setenv("STOMP_DEBUG_LEAN_PRINT", "1")
+    p = N_EXTREME_MODELS[model](N_EXTREMES[N], K=260, Kr=0)
+    o, e = pair(p, threads=8)
+    line = model_line(capfd)
+    assert f"launch of 261 rollouts: {N_BODIES[model, N, 'slot']}," in line and line.endswith("weights rows<512,4,4>")
+    for it in range(1, 3):
+        _compare_iteration(o, e, it)
+
+
+@pytest.mark.parametrize("model,N", N_CASES)
+def test_n_extremes_execute_bitwise(model, N):
+    p = N_EXTREME_MODELS[model](N_EXTREMES[N])
+    o, e = pair(p)
+    rows = mz.execute_rows(p, o.theta())
+    c = mz.census(p, rows)
+    assert c["rows_limited"] >= 1 and c["collision"] >= 1 and c["hinge"] >= 1 and c["free"] >= 1, c
+    assert_rows_equal(o, e, rows)
+    assert_rows_equal(o, e, rows[:1], member=0)
+
+
+@pytest.mark.parametrize("model", sorted(N_EXTREME_MODELS))
+def test_n_out_of_range_is_refused(model):
+    usable = N_EXTREME_MODELS[model](10)
+
+    def still_usable(it):      # the library works after each refusal
+        o, e = pair(usable)
+        for i in range(1, it + 1):
+            _compare_iteration(o, e, i)
+        e.close()
+
+    # N = 257: one past the rollout bodies' lane count, STOMP_E_INVALID before any device work
+    with pytest.raises(RuntimeError) as ei:
+        eng.Engine(N_EXTREME_MODELS[model](258))
+    assert "error -1" in str(ei.value) and "num_time_steps must be in [1, 256]" in str(ei.value), str(ei.value)
+    still_usable(1)
+    # N = 8 at the 0.05 discretization: the reference's integer movement duration int((N + 11) *
+    # 0.05) is 0 and R is not positive definite; engine and oracle both say so
+    p = N_EXTREME_MODELS[model](9)
+    assert p.N == 8
+    with pytest.raises(RuntimeError, match="not positive definite") as ei:
+        eng.Engine(p)
+    assert "error -1" in str(ei.value), str(ei.value)
+    with pytest.raises(RuntimeError, match="not positive definite"):
+        po.Oracle(p)
+    still_usable(2)
 
 
 def test_refusals_leave_the_library_usable():

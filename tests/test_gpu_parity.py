@@ -25,16 +25,88 @@ def make(dof=7, waypoints=100, grid_n=64, K=10, Kr=0, **kw):
 def test_device_math_bitwise():
     rng = np.random.default_rng(1)
     x = np.concatenate([rng.uniform(-10, 0, 4000), rng.uniform(-20, 20, 4000), rng.uniform(0, 1, 2000),
-                        [0.0, -0.0, 1.0, 2.0 ** -53, 1e-300, 6.283185307179586, 3.141592653589793]])
+                        [0.0, -0.0, 1.0, 2.0 ** -53, 1e-300, 6.283185307179586, 3.141592653589793],
+                        # the endpoints the pipeline feeds: exp of -10 (the worst rollout's weight) and 0,
+                        # log of the smallest u1 = 2^-53 and of 1.0, sincos of the largest 2 pi u2
+                        [-10.0, 6.283185307179586 * ((2 ** 53 - 1) * 2.0 ** -53)],
+                        # sincos far from the first period (joint angles after many turns)
+                        rng.uniform(-1e5, 1e5, 2000), [1e5, -1e5, 99999.99999999999]])
     e, l, s, c, q = eng.device_math(x)
-    for i in range(0, len(x), 97):
-        v = float(x[i])
-        assert e[i] == po.dexp(v)
-        if v > 0:
-            assert l[i] == po.dlog(v)
-            assert q[i] == np.sqrt(v)
-        ss, cc = po.dsincos(v)
-        assert s[i] == ss and c[i] == cc
+    assert len(x) > 12000
+    in_exp = np.arange(len(x)) < len(x) - 2003    # det_exp's domain: everything but the 1e5 block
+    assert np.abs(x[in_exp]).max() <= 20.0
+    pos = x > 0
+    sc = np.array([po.dsincos(float(v)) for v in x])
+    np.testing.assert_array_equal(e[in_exp], [po.dexp(float(v)) for v in x[in_exp]])
+    np.testing.assert_array_equal(l[pos], [po.dlog(float(v)) for v in x[pos]])
+    np.testing.assert_array_equal(q[pos], np.sqrt(x[pos]))
+    np.testing.assert_array_equal(s, sc[:, 0])
+    np.testing.assert_array_equal(c, sc[:, 1])
+    assert np.array_equal(np.signbit(s), np.signbit(sc[:, 0])) and np.array_equal(np.signbit(c), np.signbit(sc[:, 1]))
+
+
+def _ulps(v):
+    """v and its two neighbours."""
+    return [np.nextafter(v, -np.inf), v, np.nextafter(v, np.inf)]
+
+
+def _trig_inputs():
+    """(y, x) for det_atan2 and s for det_asin: random values, the special cases of e_atan2.c, and
+    both sides of every branch threshold of s_atan.c / e_atan2.c / e_asin.c (stomp_math.h)."""
+    rng = np.random.default_rng(3)
+    inf = np.inf
+    y = list(rng.standard_normal(2000) * 10.0 ** rng.integers(-3, 4, 2000))    # all four quadrants
+    x = list(rng.standard_normal(2000) * 10.0 ** rng.integers(-3, 4, 2000))
+    assert all((((np.array(y) > 0) == sy) & ((np.array(x) > 0) == sx)).sum() > 300 for sy in (0, 1) for sx in (0, 1))
+    # the rotation-matrix entries k_terms.hip feeds: both in [-1, 1]
+    y += list(rng.uniform(-1, 1, 1000)); x += list(rng.uniform(-1, 1, 1000))
+    special = [0.0, -0.0, 1.0, -1.0, inf, -inf, 0.3, -0.3]
+    for a in special:                                                            # signed zeros, infinities, x == 1
+        for b in special:
+            y.append(a); x.append(b)
+    # |y / x| one ulp either side of atan's thresholds 7/16, 11/16, 19/16, 39/16, its tiny-argument
+    # return (2^-27) and its saturation (2^66); x = 1 takes det_atan(y) directly, the other x (powers
+    # of two: y / x is exact) take it through the quotient in every quadrant
+    for t in (7 / 16, 11 / 16, 19 / 16, 39 / 16, 2.0 ** -27, 2.0 ** 66, 0.5, 1.0, 1.5):
+        for q in _ulps(t):
+            for xx in (1.0, 2.0, -2.0, 0.5, -0.5, 2.0 ** -30, -2.0 ** 40):
+                for sy in (1.0, -1.0):
+                    y.append(sy * q * abs(xx)); x.append(xx)
+    # exponent gaps 59 .. 62 of both signs around the |k| > 60 cut, every quadrant, mantissas at
+    # both ends (the gap is taken from the high words)
+    for k in (59, 60, 61, 62):
+        for my in (1.0, 1.9999999999999998, 1.25):
+            for mx in (1.0, 1.9999999999999998, 1.75):
+                for sy in (1.0, -1.0):
+                    for sx in (1.0, -1.0):
+                        y.append(sy * my * 2.0 ** k); x.append(sx * mx)             # y >> x
+                        y.append(sy * my); x.append(sx * mx * 2.0 ** k)             # y << x
+                        y.append(sy * my * 2.0 ** (k - 30)); x.append(sx * mx * 2.0 ** -30)
+    s = list(rng.uniform(-1, 1, 3000)) + list(rng.uniform(-1, 1, 500) * 1e-3)
+    for t in (1.0, 0.5, 0.975, 2.0 ** -27, 0.0):
+        for q in _ulps(t):
+            if abs(q) <= 1.0:
+                s += [q, -q]
+    # the 0.975 branch is cut on the high word (0x3FEF3333): its first and last doubles either side
+    for hi in (0x3FEF3332, 0x3FEF3333, 0x3FDFFFFF, 0x3FE00000, 0x3E3FFFFF, 0x3E400000):
+        for lo in (0x00000000, 0xFFFFFFFF):
+            v = float(np.array([(hi << 32) | lo], np.uint64).view(np.float64)[0])
+            s += [v, -v]
+    return np.array(y), np.array(x), np.array(s)
+
+
+def test_device_trig_bitwise():
+    # det_atan2 / det_asin run on the device in the orientation-constraint term (k_terms.hip)
+    y, x, s = _trig_inputs()
+    a, _ = eng.device_trig(y, x)
+    want = np.array([po.datan2(float(u), float(v)) for u, v in zip(y, x)])
+    np.testing.assert_array_equal(a, want)
+    assert np.array_equal(np.signbit(a), np.signbit(want))       # -0.0 against 0.0
+    _, b = eng.device_trig(s, np.ones_like(s))
+    want = np.array([po.dasin(float(v)) for v in s])
+    np.testing.assert_array_equal(b, want)
+    assert np.array_equal(np.signbit(b), np.signbit(want))
+    assert np.isfinite(want).all() and abs(want).max() == np.pi / 2
 
 
 def test_device_sqrt_correctly_rounded():

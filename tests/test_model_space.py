@@ -102,6 +102,95 @@ def test_oracle_matches_numpy(name):
     compare_with_numpy(mz.ZOO[name](Kr=0))
 
 
+N_EXTREMES = {9: 10, 10: 11, 255: 256, 256: 257}      # N -> waypoints: both ends of the engine's range of N
+N_EXTREME_MODELS = dict(chain5=lambda w, **kw: mz.chain5(waypoints=w, **kw),
+                        pr2=lambda w, K=12, Kr=5, **kw: pb.make_problem(waypoints=w, grid_n=64, num_rollouts=K,
+                                                                        num_reused_rollouts=Kr, **kw))
+
+
+def compare_with_numpy_at_any_n(p, zoo, iterations=2):
+    """compare_with_numpy for any N.  The control cost matrix R of N = 256 has a condition number
+    near 1e10, so two correct inversions differ by far more than the 1e-8 that holds at N = 39, and
+    their Cholesky factors by more again (measured: 7e-7 and 4e-4 of the largest entry on chain5).
+    The oracle's matrices are therefore held to their definitions, with bounds from the conditioning:
+
+      Rinv  against numpy's inverse of the dense R: both carry a forward error of c_n u cond(R) of
+            the largest entry (Higham, Accuracy and Stability, ch. 14) with c_n taken as N, u = eps / 2,
+            so they differ by at most N eps cond(R)
+      L     lower triangular with L L^T = the oracle's Rinv (lower triangle) to N eps of its largest entry (Cholesky
+            is backward stable: |A - L L^T| <= (n + 1) u |L| |L^T|, and (|L| |L^T|)_ij <= max A)
+      M     the oracle's Rinv with column c scaled by 1 / (N max_r Rinv[r, c]): three roundings
+      theta -0.5 Rinv lin from the oracle's Rinv, to the rounding of an N-term sum
+      Qinv  as Rinv, with cond(Q)
+
+    and the numpy restatement then runs execute and the iterations on the oracle's matrices, at
+    the tolerances of compare_with_numpy."""
+    o, n = po.Oracle(p), npo.NumpyStomp(p)
+    N, eps = p.N, np.finfo(np.float64).eps
+    Rf = n.Rall[6:-6, 6:-6]
+    Rinv, L, M = o.matrix("Rinv"), o.matrix("L"), o.matrix("M")
+    assert np.abs(Rinv - n.Rinv).max() <= N * eps * np.linalg.cond(Rf) * np.abs(n.Rinv).max()
+    assert not np.triu(L, 1).any() and (np.diag(L) > 0).all()
+    # the factorization reads the lower triangle (the computed inverse is symmetric only to its own
+    # forward error)
+    assert np.abs(np.tril(L @ L.T - Rinv)).max() <= N * eps * np.abs(Rinv).max()
+    np.testing.assert_allclose(M, Rinv * (1.0 / (N * Rinv.max(axis=0)))[None, :], rtol=4 * eps, atol=0)
+    for j in range(p.J):
+        cond = np.linalg.cond(n.Qinv[j])    # of Q as of its (scaled) inverse
+        assert np.abs(o.matrix("Qinv", j) - n.Qinv[j]).max() <= N * eps * cond * np.abs(n.Qinv[j]).max(), j
+    for d in range(p.J):
+        lin = 2.0 * (p.start[d] * n.Rall[0:6, 6:-6].sum(axis=0) + p.goal[d] * n.Rall[-6:, 6:-6].sum(axis=0))
+        bound = N * eps * (np.abs(Rinv) @ np.abs(lin)).max()
+        np.testing.assert_allclose(o.theta()[d], -0.5 * Rinv @ lin, rtol=0, atol=bound)
+    np.testing.assert_allclose(o.pad_positions(), n.pad, rtol=0, atol=1e-13)
+    n.Rinv, n.L, n.M, n.theta = Rinv, L, M, o.theta()
+    n.Qinv = [o.matrix("Qinv", j) for j in range(p.J)]
+    rows = mz.execute_rows(p, o.theta())
+    c = mz.census(p, rows)
+    if zoo:
+        assert_execute_census(c)
+    else:   # the PR2 shelf fixture stays inside its field
+        assert c["rows_limited"] >= 1 and c["collision"] >= 1 and c["hinge"] >= 1 and c["free"] >= 1, c
+    for r in rows:
+        c1, cf1, t1 = o.execute(r, 1)
+        c2, cf2, t2 = n.execute(r, 1)
+        np.testing.assert_allclose(t1, t2, rtol=0, atol=1e-8)
+        np.testing.assert_allclose(c1, c2, rtol=1e-6, atol=1e-9)
+        assert cf1 == cf2
+    for it in range(1, iterations + 1):
+        c1, cf1 = o.iterate(it)
+        r = n.iterate(it, lambda d, rr: po.normals(p.seed, it, d, rr, p.N))
+        np.testing.assert_allclose(o.rollouts("noise"), r["noise"], rtol=0, atol=1e-8)
+        np.testing.assert_allclose(o.rollouts("state_costs"), r["state"], rtol=1e-6, atol=1e-8)
+        np.testing.assert_allclose(o.rollouts("probabilities"), r["prob"], rtol=1e-5, atol=1e-10)
+        np.testing.assert_allclose(o.theta(), n.theta, rtol=0, atol=1e-7)
+        assert c1 == pytest.approx(r["cost"], rel=1e-6)
+        assert cf1 == r["collision_free"]
+
+
+@pytest.mark.parametrize("N", sorted(N_EXTREMES))
+@pytest.mark.parametrize("model", sorted(N_EXTREME_MODELS))
+def test_oracle_matches_numpy_at_n_extremes(model, N):
+    # the GPU twin (test_gpu_model_space.py::test_n_extremes_*) holds the engine to the oracle at
+    # these N; here the oracle itself is checked there
+    p = N_EXTREME_MODELS[model](N_EXTREMES[N], Kr=0)
+    assert p.N == N
+    compare_with_numpy_at_any_n(p, zoo=model == "chain5")
+
+
+@pytest.mark.parametrize("model", sorted(N_EXTREME_MODELS))
+def test_oracle_refuses_a_zero_movement_duration(model):
+    # nine waypoints at the 0.05 discretization: int((N + 11) * 0.05) = 0, the finite-difference
+    # matrices are infinite and R is not positive definite; the oracle says so, and works afterwards
+    p = N_EXTREME_MODELS[model](9, Kr=0)
+    assert p.N == 8 and int((p.N + 11) * p.params.trajectory_discretization) == 0
+    with pytest.raises(RuntimeError, match="not positive definite"):
+        po.Oracle(p)
+    q = N_EXTREME_MODELS[model](10, Kr=0)
+    assert int((q.N + 11) * q.params.trajectory_discretization) == 1
+    po.Oracle(q).iterate(1)
+
+
 @pytest.mark.parametrize("name,shape", NONCUBIC_CASES)
 def test_noncubic_grid_matches_numpy(name, shape):
     # a mix-up of ny and nz in the oracle's lookup (stomp_oracle.c so_sdf_distance) fails here and
