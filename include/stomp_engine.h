@@ -374,6 +374,27 @@ int stomp_stream_destroy(void* stream);
 int stomp_group_create(stomp_engine* const* engines, int32_t num_engines, stomp_group** out);
 int stomp_group_run(stomp_group* g, int32_t first_iteration, int32_t count);
 int stomp_group_synchronize(stomp_group* g);
+/* StompOptimizer::optimize (stomp_optimizer.cpp:249-401) for every engine of the group at once.
+   stats: [P]; costs_per_iteration: NULL or [P][costs_stride], row p holding engine p's
+   last_trajectory_cost_ per iteration; costs_stride >= every engine's max_iterations.
+   The engines run in lockstep through the grouped launches; the loop's bookkeeping is one more
+   launch per iteration for the whole group, and each engine stops on its own (its collision-free
+   streak reaching its max_iterations_after_collision_free, or its own max_iterations).  The host
+   reads every engine's stop flag once per chunk of STOMP_GROUP_OPTIMIZE_CHUNK iterations, one
+   chunk behind the one it enqueues, and returns once every engine has stopped.  A stopped engine
+   stays in the later launches as a no-op, or, with STOMP_DEBUG_GROUP_COMPACT=1 at
+   stomp_group_create, is left out of every chunk staged after the host has seen it stopped
+   (=0: it stays; the results are the same bit for bit; DESIGN.md 7 has the measurement).
+   Post-conditions, per engine p: exactly the state its own stomp_engine_optimize leaves --
+   stats[p] (durations: device wall clock from the group's start), the cost history,
+   best_trajectory, last_trajectory, theta and the rollout rows; it is not gated and not tracking,
+   holds no pending noiseless rollout and no pregen rows, so its own iterate / run and
+   stomp_group_run with any first iteration continue from there.  Engines may enter in any state
+   stomp_engine_optimize accepts.  NULL stats or a costs_stride below an engine's max_iterations:
+   STOMP_E_INVALID with no engine touched. */
+#define STOMP_GROUP_OPTIMIZE_CHUNK 8
+int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_iteration, int32_t costs_stride);
+int32_t stomp_group_optimize_chunk(void);
 const char* stomp_group_last_error(const stomp_group* g);
 void stomp_group_destroy(stomp_group* g);
 

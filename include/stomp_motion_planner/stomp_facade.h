@@ -418,6 +418,13 @@ public:
     // stomp_optimizer.cpp:249-401: runs the loop, writes best_group_trajectory_ back into
     // the caller's trajectory; false if the engine failed (the reference returns void)
     bool optimize();
+    // optimize() for several optimizers at once, for optimizers constructed on ONE shared stream
+    // (and of one shape: stomp_group_create's rules): their engines run as a group
+    // (stomp_group_optimize), each problem stopping on its own.  Every optimizer ends as after its
+    // own optimize(): getStatistics() (torques included) filled, the best trajectory written back
+    // into its trajectory.  On failure returns false with the reason in the first optimizer's
+    // lastError().
+    static bool optimizeBatch(const std::vector<StompOptimizer*>& optimizers);
     const STOMPStatistics& getStatistics() const { return stats_; }
 
     // Task (stomp_optimizer.cpp:1063-1165, 1167-1182)
@@ -467,6 +474,7 @@ private:
     friend class PolicyImprovement;
     friend class CovariantTrajectoryPolicy;
     bool check(int rc);
+    bool finishOptimize(const stomp_stats& st);
     // an engine of the same problem with other rollout counts / cumulative-cost setting (the
     // device rollout set of a PolicyImprovement that asks for them); nullptr and err on failure
     stomp_engine* createSibling(int num_rollouts, int num_reused_rollouts, bool use_cumulative_costs,

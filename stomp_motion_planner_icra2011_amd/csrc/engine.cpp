@@ -113,14 +113,6 @@ void track_noiseless(stomp_engine* e, const CostArgs& ca)
                  e->d_best_traj, e->J * e->N, e->stream);
 }
 
-// noise / params rows of an iteration that left them in its pregen buffer
-void materialize_rows(stomp_engine* e)
-{
-    if (!e->rows_in_pre) return;
-    launch_materialize_rows(e->rows, e->J * e->N, e->rows_eps, e->d_theta_gen, e->d_noise, e->d_params, e->stream);
-    e->rows_in_pre = false;
-}
-
 }  // namespace
 
 namespace stomp {

@@ -4,8 +4,12 @@
 // update launch (k_rollout_group, k_weights_rows_group, k_update_group), so a batch of independent
 // planning problems costs three dispatches per iteration instead of three per problem.  The
 // per-engine kernel arguments of a whole run are staged in pinned memory and uploaded once; each
-// engine's results are the ones its own stomp_engine_run gives, bit for bit.
+// engine's results are the ones its own stomp_engine_run gives, bit for bit.  stomp_group_optimize
+// runs the whole optimize loop that way, the bookkeeping of every engine in one more launch per
+// iteration (k_track_group), each engine stopping on its own.
 #include "engine_internal.h"
+
+#include <algorithm>
 
 using namespace stomp;
 
@@ -20,6 +24,15 @@ struct stomp_group {
     unsigned char* h_args = nullptr;      // pinned staging of one run's arguments
     size_t h_cap = 0;
     hipEvent_t staged = nullptr;          // the last upload from h_args is done
+    // stomp_group_optimize: two slots of one chunk's arguments each (pinned and device), the
+    // engines' (stop, iterations) mirror with a pinned read-back per slot, all P track arguments
+    bool compact = false;                 // stopped engines leave the launches (STOMP_DEBUG_GROUP_COMPACT=1 / 0)
+    unsigned char *h_opt = nullptr, *d_opt = nullptr;
+    size_t opt_slot = 0;                  // bytes per slot
+    int* d_mirror = nullptr;              // [P][2]
+    int* h_mirror = nullptr;              // [2][P][2]
+    TrackArgs* d_track_all = nullptr;     // [P]
+    hipEvent_t opt_ev[2] = {nullptr, nullptr};
     std::string err;
 };
 
@@ -47,6 +60,13 @@ void stomp_group_destroy(stomp_group* g)
     if (g->d_models) hipFree(g->d_models);
     if (g->d_args) hipFree(g->d_args);
     if (g->h_args) hipHostFree(g->h_args);
+    if (g->d_opt) hipFree(g->d_opt);
+    if (g->h_opt) hipHostFree(g->h_opt);
+    if (g->d_mirror) hipFree(g->d_mirror);
+    if (g->h_mirror) hipHostFree(g->h_mirror);
+    if (g->d_track_all) hipFree(g->d_track_all);
+    for (hipEvent_t ev : g->opt_ev)
+        if (ev) hipEventDestroy(ev);
     delete g;
 }
 
@@ -77,6 +97,7 @@ int stomp_group_create(stomp_engine* const* engines, int32_t n, stomp_group** ou
     g->device = e0->device;
     g->stream = e0->stream;
     g->nt = nt;
+    if (const char* c = getenv("STOMP_DEBUG_GROUP_COMPACT")) g->compact = c[0] == '1';
     std::vector<DevModel> ms(n);
     for (int p = 0; p < n; ++p) ms[p] = engines[p]->model;
     if (hipMalloc(&g->d_models, sizeof(DevModel) * n) != hipSuccess ||
@@ -240,6 +261,282 @@ int stomp_group_synchronize(stomp_group* g)
     }
     for (stomp_engine* e : g->e) flush_noiseless(e);
     if (hipStreamSynchronize(g->stream) != hipSuccess) return gfail(g, STOMP_E_DEVICE, "group synchronize failed");
+    return 0;
+}
+
+int32_t stomp_group_optimize_chunk(void) { return STOMP_GROUP_OPTIMIZE_CHUNK; }
+
+// StompOptimizer::optimize (stomp_optimizer.cpp:249-401) for every engine of the group:
+// stomp_engine_optimize's chunked loop over the grouped launches.  Step `it` (1-based iteration,
+// the engines in lockstep) is
+//   the grouped rollout launch of `it` with the noiseless rollouts of it - 1   (engines with max_it >= it)
+//   a grouped noiseless flush                                                  (engines with max_it == it - 1)
+//   k_track_group(it - 2) over both sets, weights and update of the first set
+// so an engine whose own max_iterations ends the loop gets the flush and the bookkeeping that
+// stomp_engine_optimize ends with, in the step after its last iteration; the last step of all is
+// that flush alone.  The host reads the engines' (stop, iterations) mirror one chunk behind the
+// chunk it stages.  With g->compact it stages no arguments for an engine it has seen stopped;
+// otherwise a stopped engine's blocks stay in the launches and return at its stop flag (the
+// default: DESIGN.md 7 has the measurement).
+int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_iteration, int32_t costs_stride)
+{
+    if (!g) return gfail(nullptr, STOMP_E_INVALID, "null group");
+    if (!stats) return gfail(g, STOMP_E_INVALID, "null stats");
+    const int P = (int)g->e.size();
+    int maxcap = 0;
+    for (stomp_engine* e : g->e) {
+        if (e->tracking) return gfail(g, STOMP_E_INVALID, "an engine of the group is inside its own optimize loop");
+        maxcap = std::max(maxcap, e->max_it);
+    }
+    if (costs_per_iteration && costs_stride < maxcap)
+        return gfail(g, STOMP_E_INVALID, "costs_stride is smaller than an engine's max_iterations");
+    DeviceGuard dg(g->device);
+    hipStream_t s = g->stream;
+    stomp_engine* e0 = g->e[0];
+    const int J = e0->J, N = e0->N, K = e0->K_loc, chunk = STOMP_GROUP_OPTIMIZE_CHUNK;
+    // one step's arguments at most: both rollout launches' CostArgs and DevModel lists, the
+    // weights, update and track arguments
+    const size_t szc = align256(sizeof(CostArgs) * P), szw = align256(sizeof(WeightArgs) * P),
+                 szu = align256(sizeof(UpdateArgs) * P), szt = align256(sizeof(TrackArgs) * P),
+                 szm = align256(sizeof(DevModel) * P);
+    const size_t slot_bytes = (2 * szc + 2 * szm + szw + szu + szt) * (size_t)chunk;
+    auto track_args = [&](int p) {
+        stomp_engine* e = g->e[p];
+        return TrackArgs{e->d_track, e->d_total, e->d_cf, e->d_cs, e->d_opt_costs, e->d_last_traj, e->d_best_traj,
+                         e->max_it_cf, e->max_it, g->d_mirror + 2 * p};
+    };
+    if (!g->d_mirror) {
+        if (hipMalloc((void**)&g->d_mirror, sizeof(int) * 2 * P) != hipSuccess ||
+            hipHostMalloc((void**)&g->h_mirror, sizeof(int) * 4 * P) != hipSuccess ||
+            hipMalloc((void**)&g->d_track_all, sizeof(TrackArgs) * P) != hipSuccess ||
+            hipMalloc((void**)&g->d_opt, 2 * slot_bytes) != hipSuccess ||
+            hipHostMalloc((void**)&g->h_opt, 2 * slot_bytes) != hipSuccess ||
+            hipEventCreateWithFlags(&g->opt_ev[0], hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&g->opt_ev[1], hipEventDisableTiming) != hipSuccess)
+            return gfail(g, STOMP_E_DEVICE, "group optimize allocation failed");
+        g->opt_slot = slot_bytes;
+        // every engine's track arguments, for the start and clear launches
+        std::vector<TrackArgs> ta(P);
+        for (int p = 0; p < P; ++p) ta[p] = track_args(p);
+        if (hipMemcpy(g->d_track_all, ta.data(), sizeof(TrackArgs) * P, hipMemcpyHostToDevice) != hipSuccess)
+            return gfail(g, STOMP_E_DEVICE, "group argument upload failed");
+    }
+    // the engines enter in any state: rows out of the pregen buffers, pending noiseless rollouts
+    // evaluated, the pregen rows of iteration 1 made where another iteration's are held
+    for (stomp_engine* e : g->e) {
+        materialize_rows(e);
+        flush_noiseless(e);
+        if (e->max_it > 0 && e->pre_it != 1) {
+            launch_pregen(pregen_args(e, 1), e->K_loc, s);
+            e->pre_it = 1;
+        }
+    }
+    launch_track_start_group(g->d_track_all, P, false, s);   // stomp_optimizer.cpp:251 start_time
+
+    std::vector<int> live;
+    for (int p = 0; p < P; ++p)
+        if (!g->compact || g->e[p]->max_it > 0) live.push_back(p);
+    const int last_step = maxcap > 0 ? maxcap + 1 : 0;   // the flush of the engines that ran maxcap iterations
+    int next = 1;
+    // one chunk of steps staged into `slot`, uploaded and enqueued, then the mirror's read-back
+    auto enqueue_chunk = [&](int slot) -> int {
+        unsigned char* hb = g->h_opt + (size_t)slot * g->opt_slot;
+        unsigned char* db = g->d_opt + (size_t)slot * g->opt_slot;
+        size_t used = 0;
+        auto take = [&](size_t bytes) {
+            const size_t o = used;
+            used += align256(bytes);
+            return o;
+        };
+        struct Step {
+            int it, nm, nc, nro;
+            size_t cas, was, uas, tas, ccs, mms, cms;
+            const DevModel* m0;
+        };
+        std::vector<Step> steps;
+        std::vector<int> prev_main;
+        size_t prev_mms = 0;
+        const int end = std::min(next + chunk, last_step + 1);
+        for (int it = next; it < end; ++it) {
+            Step st{};
+            st.it = it;
+            std::vector<int> main, cohort;
+            for (int p : live) {
+                if (g->e[p]->max_it >= it) main.push_back(p);
+                else if (g->e[p]->max_it == it - 1 && it >= 2) cohort.push_back(p);
+            }
+            st.nm = (int)main.size();
+            st.nc = (int)cohort.size();
+            st.cas = take(sizeof(CostArgs) * st.nm);
+            st.was = take(sizeof(WeightArgs) * st.nm);
+            st.uas = take(sizeof(UpdateArgs) * st.nm);
+            st.tas = take(sizeof(TrackArgs) * (st.nm + st.nc));
+            st.ccs = take(sizeof(CostArgs) * st.nc);
+            st.cms = take(sizeof(DevModel) * st.nc);
+            // the DevModel list of the rollout launch: once per chunk, again where an engine's
+            // max_iterations takes it out within the chunk
+            if (st.nm > 0 && main != prev_main) {
+                prev_mms = take(sizeof(DevModel) * st.nm);
+                DevModel* ms = (DevModel*)(hb + prev_mms);
+                for (int k = 0; k < st.nm; ++k) ms[k] = g->e[main[k]]->model;
+                prev_main = main;
+            }
+            st.mms = prev_mms;
+            if (st.nm > 0) st.m0 = &g->e[main[0]]->model;
+            CostArgs* cas = (CostArgs*)(hb + st.cas);
+            WeightArgs* was = (WeightArgs*)(hb + st.was);
+            UpdateArgs* uas = (UpdateArgs*)(hb + st.uas);
+            TrackArgs* tas = (TrackArgs*)(hb + st.tas);
+            for (int k = 0; k < st.nm; ++k) {
+                stomp_engine* e = g->e[main[k]];
+                // enqueue_iteration's pipelined path inside the optimize loop, arguments only: the
+                // noise / params rows are copied out of the pregen buffer (pregen blocks enqueued
+                // past a stop overwrite the ping-pong buffers), the weights read d_noise
+                int rc = begin_generate(e);   // K_r = 0: every row generated
+                if (rc) return rc;
+                NoiseArgs na = noise_args(e, it);
+                na.K_gen_global = e->K_gen;
+                na.row_begin = e->K_loc;
+                na.rows_in_pre = 0;
+                if (e->pre_it != it) return gfail(g, STOMP_E_INVALID, "group pregen rows out of step");
+                CostArgs ca{};
+                ca.stop = e->d_stop;
+                ca.fused_noise = 2;
+                ca.nz = na;
+                ca.params = e->d_params; ca.stride = (long long)e->J * e->N; ca.num_noisy = e->K_loc;
+                ca.member = it - 1; ca.state_out = e->d_state;
+                ca.pre_rows = e->K_loc;
+                ca.pre_next = pregen_args(e, it + 1);
+                ca.ctl_by_pre = 0;   // as stomp_group_run: the rollout workgroups price their own rows
+                e->pre_it = it + 1;
+                if (e->pending_member >= 0) {
+                    set_noiseless(e, ca, e->pending_member, true, false);
+                    e->pending_member = -1;
+                }
+                const int n_ro = ca.num_noisy + (ca.x_params ? 1 : 0);
+                if (k == 0) st.nro = n_ro;
+                else if (n_ro != st.nro) return gfail(g, STOMP_E_INVALID, "group engines out of step");
+                cas[k] = ca;
+                WeightArgs wa = weight_args(e, e->K_loc, e->d_noise);
+                wa.mode = W_FUSED;
+                was[k] = wa;
+                uas[k] = UpdateArgs{e->d_MT, e->d_u, e->d_theta, e->d_stop};
+                e->pending_member = it - 1;
+                tas[k] = track_args(main[k]);
+            }
+            CostArgs* ccs = (CostArgs*)(hb + st.ccs);
+            DevModel* cms = (DevModel*)(hb + st.cms);
+            for (int k = 0; k < st.nc; ++k) {
+                stomp_engine* e = g->e[cohort[k]];
+                CostArgs ca{};
+                ca.stop = e->d_stop;
+                ca.num_noisy = 0;
+                set_noiseless(e, ca, e->pending_member, true, false);
+                e->pending_member = -1;
+                ccs[k] = ca;
+                cms[k] = e->model;
+                tas[st.nm + k] = track_args(cohort[k]);
+            }
+            steps.push_back(st);
+        }
+        next = end;
+        if (used > g->opt_slot) return gfail(g, STOMP_E_INVALID, "group optimize staging overflow");
+        if (used && hipMemcpyAsync(db, hb, used, hipMemcpyHostToDevice, s) != hipSuccess)
+            return gfail(g, STOMP_E_DEVICE, "group argument upload failed");
+        for (const Step& st : steps) {
+            // with timing on for the group's first engine, its timers hold the group's launches
+            if (st.nc > 0) {
+                Timed tm(e0, T_NOISELESS, s);
+                launch_cost_group(g->e[0]->model, (const DevModel*)(db + st.cms), (const CostArgs*)(db + st.ccs), st.nc,
+                                  1, 0, s);
+            }
+            if (st.nm > 0) {
+                Timed tm(e0, T_COST, s);
+                launch_cost_group(*st.m0, (const DevModel*)(db + st.mms), (const CostArgs*)(db + st.cas), st.nm, st.nro,
+                                  K, s);
+            }
+            // before this step's weights / update: a break decided on the previous iteration's
+            // noiseless rollout leaves theta where the reference leaves it
+            if (st.it >= 2) launch_track_group((const TrackArgs*)(db + st.tas), st.nm + st.nc, st.it - 2, J * N, s);
+            if (st.nm > 0) {
+                {
+                    Timed tm(e0, T_WEIGHTS, s);
+                    launch_weights_group((const WeightArgs*)(db + st.was), st.nm, J, N, K, s);
+                }
+                {
+                    Timed tm(e0, T_UPDATE, s);
+                    launch_update_group(J, N, (const UpdateArgs*)(db + st.uas), st.nm, s);
+                }
+            }
+        }
+        if (hipMemcpyAsync(g->h_mirror + (size_t)slot * 2 * P, g->d_mirror, sizeof(int) * 2 * P, hipMemcpyDeviceToHost,
+                           s) != hipSuccess ||
+            hipEventRecord(g->opt_ev[slot], s) != hipSuccess)
+            return gfail(g, STOMP_E_DEVICE, "group read-back failed");
+        return 0;
+    };
+    int rc = 0, inflight = 0, head = 0;
+    bool all_stopped = false;
+    while (!all_stopped) {
+        while (inflight < 2 && next <= last_step) {
+            if ((rc = enqueue_chunk((head + inflight) & 1))) break;
+            ++inflight;
+        }
+        if (rc || inflight == 0) break;
+        if (hipEventSynchronize(g->opt_ev[head]) != hipSuccess) {
+            rc = gfail(g, STOMP_E_DEVICE, "group read-back wait failed");
+            break;
+        }
+        const int* hm = g->h_mirror + (size_t)head * 2 * P;
+        all_stopped = true;
+        for (int p = 0; p < P; ++p) all_stopped = all_stopped && hm[2 * p] != 0;
+        if (g->compact) {
+            // the engines seen stopped leave every chunk staged from here on
+            std::vector<int> keep;
+            for (int p : live)
+                if (!hm[2 * p]) keep.push_back(p);
+            live.swap(keep);
+        }
+        head ^= 1;
+        --inflight;
+    }
+    // the steps enqueued past an engine's stop were no-ops; the engines stopped at different
+    // iterations, so every engine leaves with no pregen rows held and nothing pending (the next
+    // run, the group's or the engine's own, makes its rows with a standalone pregen launch)
+    for (stomp_engine* e : g->e) {
+        e->pending_member = -1;
+        e->pre_it = -1;
+        e->rows_in_pre = false;
+    }
+    hipError_t err = hipGetLastError();
+    if (!rc && err != hipSuccess) rc = gfail(g, STOMP_E_DEVICE, hipGetErrorString(err));
+    for (int p = 0; p < P && !rc; ++p)
+        if (hipMemcpyAsync(&g->e[p]->h_track[2], g->e[p]->d_track, sizeof(DevTrack), hipMemcpyDeviceToHost, s) != hipSuccess)
+            rc = gfail(g, STOMP_E_DEVICE, "group read-back failed");
+    // later launches (iterate / run / eval) are not gated
+    launch_track_start_group(g->d_track_all, P, true, s);
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = gfail(g, STOMP_E_DEVICE, "group synchronize failed");
+    if (rc) return rc;
+    for (int p = 0; p < P; ++p) {
+        stomp_engine* e = g->e[p];
+        const DevTrack& t = e->h_track[2];
+        if (costs_per_iteration && t.iterations > 0 &&
+            hipMemcpy(costs_per_iteration + (size_t)p * costs_stride, e->d_opt_costs, sizeof(double) * t.iterations,
+                      hipMemcpyDeviceToHost) != hipSuccess)
+            return gfail(g, STOMP_E_DEVICE, "group cost history read-back failed");
+        stomp_stats st;
+        st.iterations = t.iterations;
+        st.success = t.success;
+        st.success_iteration = t.success_iteration;
+        st.collision_success_iteration = t.collision_success_iteration;
+        st.last_improvement_iteration = t.last_improvement_iteration;
+        st.best_cost = t.best;
+        const double tick_s = e->wall_khz > 0 ? 1.0 / (1000.0 * e->wall_khz) : 0.0;
+        st.success_duration = t.success_iteration >= 0 ? (double)(t.t_success - t.t0) * tick_s : 0.0;
+        st.collision_success_duration =
+            t.collision_success_iteration >= 0 ? (double)(t.t_collision_success - t.t0) * tick_s : 0.0;
+        stats[p] = st;
+    }
     return 0;
 }
 

@@ -378,6 +378,14 @@ inline WeightArgs weight_args(const stomp_engine* e, int rows, const double* noi
     return wa;
 }
 
+// noise / params rows of an iteration that left them in its pregen buffer
+inline void materialize_rows(stomp_engine* e)
+{
+    if (!e->rows_in_pre) return;
+    launch_materialize_rows(e->rows, e->J * e->N, e->rows_eps, e->d_theta_gen, e->d_noise, e->d_params, e->stream);
+    e->rows_in_pre = false;
+}
+
 inline int flush_noiseless(stomp_engine* e)
 {
     if (e->pending_member >= 0) {

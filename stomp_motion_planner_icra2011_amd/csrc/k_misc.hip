@@ -450,10 +450,13 @@ void launch_materialize_rows(int K_loc, int JN, const double* eps, const double*
 // StompOptimizer::optimize bookkeeping (stomp_optimizer.cpp:301-344) for iteration index `it`
 // (iteration_), after its noiseless rollout: collision-free streak, success / collision-success
 // iterations, the cost history, best_group_trajectory_ (copied by the whole block) and the
-// break condition, which turns every later launch of the loop into a no-op.
-__global__ __launch_bounds__(256) void k_track(DevTrack* tr, int it, int max_it_cf, const double* total,
-                                               const uint8_t* cf, const uint8_t* cs, double* costs,
-                                               const double* last_traj, double* best_traj, int JN)
+// break condition, which turns every later launch of the loop into a no-op.  One body for the
+// single-engine loop (k_track) and the group's (k_track_group).  max_it > 0 (the group): the loop's
+// own end at it + 1 == max_it sets the stop flag too; mirror (the group): (stop, iterations) copied
+// to the group's read-back array.
+__device__ __forceinline__ void track_body(DevTrack* tr, int it, int max_it_cf, int max_it, const double* total,
+                                           const uint8_t* cf, const uint8_t* cs, double* costs,
+                                           const double* last_traj, double* best_traj, int JN, int* mirror)
 {
     __shared__ int copy;
     if (tr->stop) return;   // uniform: every thread reads the same flag before any write
@@ -480,16 +483,63 @@ __global__ __launch_bounds__(256) void k_track(DevTrack* tr, int it, int max_it_
             copy = 1;
         }
         tr->iterations = it + 1;
-        if (tr->cfi >= max_it_cf) tr->stop = 1;
+        const int stop = (tr->cfi >= max_it_cf || (max_it > 0 && it + 1 >= max_it)) ? 1 : 0;
+        if (stop) tr->stop = 1;
+        if (mirror) {
+            mirror[0] = stop;
+            mirror[1] = it + 1;
+        }
     }
     __syncthreads();
     if (copy)
         for (int i = threadIdx.x; i < JN; i += blockDim.x) best_traj[i] = last_traj[i];
 }
 
+__global__ __launch_bounds__(256) void k_track(DevTrack* tr, int it, int max_it_cf, const double* total,
+                                               const uint8_t* cf, const uint8_t* cs, double* costs,
+                                               const double* last_traj, double* best_traj, int JN)
+{
+    track_body(tr, it, max_it_cf, 0, total, cf, cs, costs, last_traj, best_traj, JN, nullptr);
+}
+
+// the bookkeeping of a group's engines in one launch: one workgroup per engine, `it` the launch's
+// (the engines run in lockstep)
+__global__ __launch_bounds__(256) void k_track_group(const TrackArgs* as, int it, int JN)
+{
+    using CArgs = const __attribute__((address_space(4))) TrackArgs;   // scalar loads, as a kernel argument
+    const TrackArgs& a = *(const TrackArgs*)((CArgs*)as + blockIdx.x);
+    track_body(a.tr, it, a.max_it_cf, a.max_it, a.total, a.cf, a.cs, a.costs, a.last_traj, a.best_traj, JN, a.mirror);
+}
+
 __global__ void k_track_start(DevTrack* tr)
 {
     if (threadIdx.x == 0) tr->t0 = wall_clock64();
+}
+
+// a group's optimize loop, one workgroup per engine.  clear = 0: the loop's initial state and its
+// start stamp (an engine with no iterations to run starts stopped); clear = 1: the stop flag
+// lowered after the loop, so that later launches are not gated
+__global__ void k_track_start_group(const TrackArgs* as, int clear)
+{
+    if (threadIdx.x != 0) return;
+    const TrackArgs a = as[blockIdx.x];
+    DevTrack* tr = a.tr;
+    if (clear) {
+        tr->stop = 0;
+        return;
+    }
+    const int stop = a.max_it <= 0 ? 1 : 0;
+    tr->stop = stop;
+    tr->cfi = 0;
+    tr->iterations = 0;
+    tr->success = 0;
+    tr->success_iteration = -1;
+    tr->collision_success_iteration = -1;
+    tr->last_improvement_iteration = -1;
+    tr->best = 0.0;
+    a.mirror[0] = stop;
+    a.mirror[1] = 0;
+    tr->t0 = wall_clock64();
 }
 
 void launch_track_start(DevTrack* tr, hipStream_t s)
@@ -502,6 +552,16 @@ void launch_track(DevTrack* tr, int it, int max_it_cf, const double* total, cons
 {
     hipLaunchKernelGGL(k_track, dim3(1), dim3(256), 0, s, tr, it, max_it_cf, total, cf, cs, costs, last_traj,
                        best_traj, JN);
+}
+
+void launch_track_start_group(const TrackArgs* as, int engines, bool clear, hipStream_t s)
+{
+    if (engines > 0) hipLaunchKernelGGL(k_track_start_group, dim3(engines), dim3(64), 0, s, as, clear ? 1 : 0);
+}
+
+void launch_track_group(const TrackArgs* as, int engines, int it, int JN, hipStream_t s)
+{
+    if (engines > 0) hipLaunchKernelGGL(k_track_group, dim3(engines), dim3(256), 0, s, as, it, JN);
 }
 
 // ============================================================== distance field construction

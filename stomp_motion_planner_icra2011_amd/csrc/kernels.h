@@ -390,6 +390,24 @@ struct DevTrack {
 void launch_track_start(DevTrack* tr, hipStream_t s);
 void launch_track(DevTrack* tr, int it, int max_it_cf, const double* total, const uint8_t* cf, const uint8_t* cs,
                   double* costs, const double* last_traj, double* best_traj, int JN, hipStream_t s);
+// the bookkeeping of a group of engines in lockstep (stomp_group_optimize): per-engine arguments
+// in device memory, one entry and one workgroup per engine.  The grouped k_track also stops an
+// engine when its own max_iterations is reached and mirrors (stop, iterations) into the group's
+// read-back array (mirror: the engine's two ints of it).
+struct TrackArgs {
+    DevTrack* tr;
+    const double* total;        // the noiseless rollout's costs.sum()
+    const uint8_t* cf;          // its collision-free flag
+    const uint8_t* cs;          // its constraints-satisfied flag
+    double* costs;              // [max_it] cost history
+    const double* last_traj;    // [J][N]
+    double* best_traj;          // [J][N]
+    int max_it_cf, max_it;
+    int* mirror;                // [2] (stop, iterations)
+};
+// clear = false: every engine's initial DevTrack and start stamp; true: the stop flags lowered
+void launch_track_start_group(const TrackArgs* as, int engines, bool clear, hipStream_t s);
+void launch_track_group(const TrackArgs* as, int engines, int it, int JN, hipStream_t s);
 void launch_cost(const DevModel& m, const CostArgs& a, hipStream_t s);
 bool cost_supported(const DevModel& m);
 size_t rollout_lds_bytes(const DevModel& m, int pad_lds, int lean = 0);   // dynamic LDS of the rollout kernel

@@ -92,6 +92,7 @@ EXPORTED = ["stomp_engine_create", "stomp_engine_destroy", "stomp_engine_last_er
             "stomp_pi_improve_policy", "stomp_pi_add_extra_rollouts", "stomp_pi_reset", "stomp_sdf_build_objects",
             "stomp_stream_create", "stomp_stream_destroy", "stomp_group_create", "stomp_group_run",
             "stomp_group_synchronize", "stomp_group_last_error", "stomp_group_destroy", "stomp_engine_shard_mode",
+            "stomp_group_optimize", "stomp_group_optimize_chunk",
             "stomp_engine_shard_info", "stomp_shard_decide", "stomp_engine_source_hash",
             "stomp_engine_refresh_field", "stomp_device_selftest_trig"]
 
@@ -161,6 +162,9 @@ def load_library(path: Optional[str] = None):
     l.stomp_group_create.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]
     l.stomp_group_run.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     l.stomp_group_synchronize.argtypes = [C.c_void_p]
+    l.stomp_group_optimize.argtypes = [C.c_void_p, C.POINTER(stomp_stats), dp, C.c_int32]
+    l.stomp_group_optimize_chunk.restype = C.c_int32
+    l.stomp_group_optimize_chunk.argtypes = []
     l.stomp_group_last_error.restype = C.c_char_p
     l.stomp_group_last_error.argtypes = [C.c_void_p]
     l.stomp_group_destroy.argtypes = [C.c_void_p]
@@ -508,6 +512,30 @@ class EngineGroup:
 
     def synchronize(self):
         self._check(load_library().stomp_group_synchronize(self._h))
+
+    @staticmethod
+    def optimize_chunk() -> int:
+        """Iterations per chunk of optimize() (STOMP_GROUP_OPTIMIZE_CHUNK): the host reads the
+        engines' stop flags once per chunk, one chunk behind the one it enqueues."""
+        return int(load_library().stomp_group_optimize_chunk())
+
+    def optimize(self, costs_stride: Optional[int] = None):
+        """StompOptimizer::optimize for every engine at once (stomp_group_optimize): the engines
+        advance in lockstep through the grouped launches and each stops on its own, by its
+        collision-free streak or its own max_iterations; the call returns once all have stopped
+        (STOMP_DEBUG_GROUP_COMPACT=1 when the group is created: a stopped engine also leaves the
+        later launches; same results).  Returns one (stomp_stats, costs[:iterations]) per engine, as Engine.optimize()
+        does.  Afterwards every engine is where its own optimize() leaves it (theta, best and last
+        trajectory, rollout rows), not gated, with nothing pending: its own iterate / run and
+        group.run(first, count) with any first continue from there.  costs_stride: the row length
+        of the cost histories (default: the largest max_iterations; smaller is refused)."""
+        n = len(self.engines)
+        if costs_stride is None:
+            costs_stride = max([e.problem.params.max_iterations for e in self.engines] + [1])
+        st = (stomp_stats * n)()
+        costs = np.zeros((n, max(costs_stride, 1)))
+        self._check(load_library().stomp_group_optimize(self._h, st, _dp(costs), costs_stride))
+        return [(st[i], costs[i, : st[i].iterations].copy()) for i in range(n)]
 
     def close(self):
         if self._h is not None and self._h.value:

@@ -155,6 +155,12 @@ bool StompOptimizer::optimize()
     stats_.costs.assign(parameters_->max_iterations > 0 ? parameters_->max_iterations : 1, 0.0);
     stomp_stats st{};
     if (!check(stomp_engine_optimize(engine_, &st, stats_.costs.data()))) return false;
+    return finishOptimize(st);
+}
+
+// the statistics of a finished loop (stats_.costs holds the cost history) and the best trajectory
+bool StompOptimizer::finishOptimize(const stomp_stats& st)
+{
     stats_.iterations = st.iterations;
     stats_.success = st.success != 0;
     stats_.success_iteration = st.success_iteration;
@@ -174,6 +180,46 @@ bool StompOptimizer::optimize()
     trajectory_->free.assign(J_, VectorXd(N_));
     for (int j = 0; j < J_; ++j)
         for (int t = 0; t < N_; ++t) trajectory_->free[j][t] = best[(size_t)j * N_ + t];
+    return true;
+}
+
+// optimize() for several optimizers at once: their engines as one group (stomp_group_optimize),
+// every problem stopping on its own
+bool StompOptimizer::optimizeBatch(const std::vector<StompOptimizer*>& optimizers)
+{
+    if (optimizers.empty()) return true;
+    StompOptimizer* first = optimizers[0];
+    if (!first) return false;
+    std::vector<stomp_engine*> engines;
+    int stride = 1;
+    for (StompOptimizer* o : optimizers) {
+        if (!o || !o->engine_) {
+            first->error_ = "optimizeBatch: an optimizer without an engine";
+            return false;
+        }
+        engines.push_back(o->engine_);
+        stride = std::max(stride, o->parameters_->max_iterations);
+    }
+    stomp_group* g = nullptr;
+    if (stomp_group_create(engines.data(), (int32_t)engines.size(), &g) != 0) {
+        first->error_ = stomp_last_error();
+        return false;
+    }
+    std::vector<stomp_stats> st(engines.size());
+    std::vector<double> costs(engines.size() * (size_t)stride, 0.0);
+    const int rc = stomp_group_optimize(g, st.data(), costs.data(), stride);
+    if (rc != 0) first->error_ = stomp_group_last_error(g);
+    stomp_group_destroy(g);
+    if (rc != 0) return false;
+    for (size_t p = 0; p < optimizers.size(); ++p) {
+        StompOptimizer* o = optimizers[p];
+        o->stats_ = STOMPStatistics();
+        o->stats_.costs.assign(costs.begin() + p * (size_t)stride, costs.begin() + (p + 1) * (size_t)stride);
+        if (!o->finishOptimize(st[p])) {
+            if (o != first) first->error_ = o->error_;
+            return false;
+        }
+    }
     return true;
 }
 

@@ -1,0 +1,113 @@
+"""A/B of optimizing a batch of planning problems: one stomp_engine_optimize per problem against
+stomp_group_optimize of the whole batch, without and with the compaction that takes stopped
+problems out of the group's launches.
+
+The batch is bench.py's cfg5: 64 problems of K = 128 rollouts at 256^3 on one shared device-built
+field, distinct start / goal / seed, with max_iterations = 200 and
+max_iterations_after_collision_free = 2.  Every way optimizes the same engines from the same
+initial trajectories, five repeats each; the three must agree on every statistic and best
+trajectory.
+
+    python tools/group_optimize_ab.py [--out FILE] [--problems 64] [--repeats 5]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from stomp_motion_planner_icra2011_amd import engine as eng   # noqa: E402
+from stomp_motion_planner_icra2011_amd import problem as pb   # noqa: E402
+
+INT_STATS = ("iterations", "success", "success_iteration", "collision_success_iteration",
+             "last_improvement_iteration")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--problems", type=int, default=64)
+    ap.add_argument("--rollouts", type=int, default=128)
+    ap.add_argument("--grid", type=int, default=256)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--max-iterations", type=int, default=200)
+    args = ap.parse_args()
+    P = args.problems
+    base = pb.make_problem(dof=7, waypoints=100, grid_n=args.grid, num_rollouts=args.rollouts, num_reused_rollouts=0,
+                           build_grid=False)
+    sdf = eng.DeviceBuffer(2 * args.grid ** 3, device=0)
+    eng.sdf_build_device(base, sdf.ptr)
+    offsets = np.random.default_rng(1234).uniform(-0.15, 0.15, (P, 2, base.J))
+    stream = eng.Stream(0)
+    engines = []
+    for i in range(P):
+        p = pb.make_problem(dof=7, waypoints=100, grid_n=args.grid, num_rollouts=args.rollouts, num_reused_rollouts=0,
+                            build_grid=False, seed=base.seed + 1 + i, start=list(base.start + offsets[i, 0]),
+                            goal=list(base.goal + offsets[i, 1]), max_iterations=args.max_iterations,
+                            max_iterations_after_collision_free=2)
+        engines.append(eng.Engine(p, device=0, sdf_device_ptr=sdf.ptr, stream=stream.ptr))
+    # the switch is read when a group is created
+    os.environ["STOMP_DEBUG_GROUP_COMPACT"] = "0"
+    group_all = eng.EngineGroup(engines)
+    os.environ["STOMP_DEBUG_GROUP_COMPACT"] = "1"
+    group_compact = eng.EngineGroup(engines)
+    theta0 = [e.theta() for e in engines]
+
+    def reset():
+        for e, th in zip(engines, theta0):
+            e.set_theta(th)
+        for e in engines:
+            e.synchronize()
+
+    ways = [("a: one stomp_engine_optimize per problem", lambda: [e.optimize() for e in engines]),
+            ("b: stomp_group_optimize, compaction off", group_all.optimize),
+            ("c: stomp_group_optimize, compaction on", group_compact.optimize)]
+    lines = [f"group_optimize_ab: {P} problems, K = {args.rollouts}, {args.grid}^3, max_iterations = "
+             f"{args.max_iterations}, max_iterations_after_collision_free = 2, {args.repeats} repeats after one warm-up"]
+    reference = None
+    medians = {}
+    for name, run in ways:
+        times = []
+        for rep in range(args.repeats + 1):   # the first is a warm-up
+            reset()
+            t0 = time.perf_counter()
+            res = run()
+            dt = time.perf_counter() - t0
+            if rep:
+                times.append(dt * 1e3)
+            got = ([tuple(int(getattr(st, k)) for k in INT_STATS) + (float(st.best_cost),) for st, _ in res],
+                   [np.array(c) for _, c in res], [e.best_trajectory() for e in engines])
+            if reference is None:
+                reference = got
+            else:
+                assert got[0] == reference[0], f"{name}: statistics differ"
+                for a, b in zip(got[1] + got[2], reference[1] + reference[2]):
+                    np.testing.assert_array_equal(a, b, err_msg=name)
+        times.sort()
+        medians[name[0]] = times[len(times) // 2]
+        lines.append(f"{name:48s} median {times[len(times) // 2]:9.2f} ms  min {times[0]:9.2f}  max {times[-1]:9.2f}")
+    stops = sorted(s[0] for s in reference[0])
+    total = sum(stops)
+    lines.append("statistics, cost histories and best trajectories identical across a, b, c and all repeats")
+    lines.append(f"stop iterations (sorted): {stops}")
+    lines.append(f"problem-iterations run: {total} of {P * args.max_iterations} "
+                 f"(lockstep without compaction: {P} x {max(stops)} = {P * max(stops)})")
+    lines.append(f"speed-up of c over a: {medians['a'] / medians['c']:.2f}x, of c over b: {medians['b'] / medians['c']:.2f}x")
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text)
+    group_all.close()
+    group_compact.close()
+    for e in engines:
+        e.close()
+    stream.close()
+
+
+if __name__ == "__main__":
+    main()
