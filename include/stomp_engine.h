@@ -361,13 +361,19 @@ int stomp_sdf_build_objects(int32_t nx, int32_t ny, int32_t nz, const double* or
  * velocity, acceleration, jerk; 3 x 7 doubles, row-major).  Host only, no device needed. */
 int stomp_diff_rules(double* out);
 
-/* Groups: several engines of one shape (same J, N, K, spheres and model layout; single device,
- * no reuse, no state-cost terms), created on ONE shared stream, advanced in lockstep by shared
- * launches -- one rollout, one weights and one update launch per iteration for the whole group
- * instead of three per engine (a batch of independent planning problems, BASELINE cfg5).  Each
- * engine ends in exactly the state its own stomp_engine_run(first, count) leaves: its θ, rollouts
- * and pending noiseless rollout; the engines' own calls keep working between group runs.
- * stomp_group_synchronize flushes every engine's pending noiseless rollout and waits. */
+/* Groups: several engines of one shape (same J, N, K, K_r, spheres and model layout; single
+ * device, at most 16 joints, no state-cost terms, no cumulative costs), created on ONE shared
+ * stream, advanced in lockstep by shared launches -- one rollout, one weights and one update launch
+ * per iteration for the whole group instead of three per engine (a batch of independent planning
+ * problems, BASELINE cfg5).  With reused rollouts (K_r > 0, the same for every engine; engines of
+ * different K_r are STOMP_E_INVALID) the iterations that reuse add one launch for the reused rows
+ * of every engine; such a group takes K <= 1023 rollouts and shapes whose reused row fits the
+ * reuse kernel's LDS (otherwise STOMP_E_UNSUPPORTED).  Each engine ends in exactly the state its
+ * own stomp_engine_run(first, count) leaves: its θ, rollouts (both row sets, the extra rollout's
+ * rows) and pending noiseless rollout; the engines' own calls keep working between group runs.
+ * The engines enter a run at one iteration state (STOMP_E_INVALID with no engine touched
+ * otherwise).  stomp_group_synchronize flushes every engine's pending noiseless rollout and
+ * waits. */
 typedef struct stomp_group stomp_group;
 int stomp_stream_create(int32_t device, void** out_stream);
 int stomp_stream_destroy(void* stream);
@@ -387,7 +393,8 @@ int stomp_group_synchronize(stomp_group* g);
    (=0: it stays; the results are the same bit for bit; DESIGN.md 7 has the measurement).
    Post-conditions, per engine p: exactly the state its own stomp_engine_optimize leaves --
    stats[p] (durations: device wall clock from the group's start), the cost history,
-   best_trajectory, last_trajectory, theta and the rollout rows; it is not gated and not tracking,
+   best_trajectory, last_trajectory, theta and the rollout rows (with K_r > 0 also the extra
+   rollout's rows and the reuse state of the iteration it stopped at); it is not gated and not tracking,
    holds no pending noiseless rollout and no pregen rows, so its own iterate / run and
    stomp_group_run with any first iteration continue from there.  Engines may enter in any state
    stomp_engine_optimize accepts.  NULL stats or a costs_stride below an engine's max_iterations:

@@ -419,7 +419,8 @@ public:
     // the caller's trajectory; false if the engine failed (the reference returns void)
     bool optimize();
     // optimize() for several optimizers at once, for optimizers constructed on ONE shared stream
-    // (and of one shape: stomp_group_create's rules): their engines run as a group
+    // (and of one shape: stomp_group_create's rules; reused rollouts are fine when every optimizer
+    // has the same num_reused_rollouts): their engines run as a group
     // (stomp_group_optimize), each problem stopping on its own.  Every optimizer ends as after its
     // own optimize(): getStatistics() (torques included) filled, the best trajectory written back
     // into its trajectory.  On failure returns false with the reason in the first optimizer's

@@ -7,6 +7,11 @@
 // engine's results are the ones its own stomp_engine_run gives, bit for bit.  stomp_group_optimize
 // runs the whole optimize loop that way, the bookkeeping of every engine in one more launch per
 // iteration (k_track_group), each engine stopping on its own.
+// Engines with reused rollouts (one K_r for the group) add the reuse candidates' totals blocks to
+// the rollout launch and one launch for every engine's reused rows (k_reuse_rows_group) on the
+// reusing iterations; the host keeps every engine's generateRollouts state (reused_next,
+// extra_added, the row-set swap) in step with the staged iterations and, after an optimize loop,
+// puts back the state of the iteration each engine stopped at.
 #include "engine_internal.h"
 
 #include <algorithm>
@@ -19,7 +24,7 @@ struct stomp_group {
     hipStream_t stream = nullptr;
     int nt = 0;                           // weights tiles per engine
     DevModel* d_models = nullptr;         // [P]
-    unsigned char* d_args = nullptr;      // [iterations][P] CostArgs, then WeightArgs, then UpdateArgs
+    unsigned char* d_args = nullptr;      // [iterations][P] CostArgs, WeightArgs, UpdateArgs, (K_r > 0) ReuseRowArgs
     size_t d_cap = 0;
     unsigned char* h_args = nullptr;      // pinned staging of one run's arguments
     size_t h_cap = 0;
@@ -44,6 +49,94 @@ int gfail(stomp_group* g, int code, const char* msg)
     g_last_error = msg;
     if (g) g->err = msg;
     return code;
+}
+
+// what one engine's staged iteration adds to the step's launches
+struct StagedIteration {
+    int nro;      // rollout workgroups (the generated rows and the pending noiseless rollout)
+    int ntot;     // totals blocks (K on a reusing iteration)
+    bool reuse;   // the grouped reuse launch has an entry of this engine
+};
+
+// One engine's arguments of iteration `it` in a group's step: enqueue_iteration's pipelined
+// one-device path with pregen rows, arguments only.  The engine's generateRollouts state
+// (plan_generate: K_gen, reused_next, the row-set swap; extra_added) advances as its own
+// iteration advances it.  keep_in_pre: without reuse the rows stay in the pregen buffer (a run
+// outside the optimize loop); with K_r > 0 they are written, the next reuse step ranks and copies
+// them.  On a reusing iteration the rollout launch carries the K totals blocks of the previous
+// rows and `rr` is the engine's entry of the grouped reuse launch (between the rollout and the
+// weights launches); no candidates are priced ahead and no launch splits, the rows are the same
+// bit for bit.
+StagedIteration stage_iteration(stomp_engine* e, int it, bool keep_in_pre, CostArgs& ca_out, WeightArgs& wa_out,
+                                UpdateArgs& ua_out, ReuseRowArgs* rr)
+{
+    const bool reuse = plan_generate(e);   // K_r = 0: every row generated
+    NoiseArgs na = noise_args(e, it);
+    na.K_gen_global = e->K_gen;
+    na.row_begin = e->K_gen;   // the rows after the generated ones are the reuse launch's
+    const bool rows_pre = keep_in_pre && e->Kr == 0;
+    na.rows_in_pre = rows_pre ? 1 : 0;
+    CostArgs ca{};
+    ca.stop = e->d_stop;
+    ca.fused_noise = 2;
+    ca.nz = na;
+    ca.params = e->d_params; ca.stride = (long long)e->J * e->N; ca.num_noisy = e->K_gen;
+    ca.member = it - 1; ca.state_out = e->d_state;
+    ca.pre_rows = e->K_loc;
+    ca.pre_next = pregen_args(e, it + 1);
+    // the grouped launch is throughput-bound: its rollout workgroups price their own rows
+    // (pricing in the pregen blocks re-reads theta and eps: cfg5 55.7k vs 53.9-54.5k
+    // problem-it/s)
+    ca.ctl_by_pre = 0;
+    e->pre_it = it + 1;
+    if (reuse) {
+        // the reuse candidates' totals (the previous rows, complete) made beside the rollouts
+        ca.tot_rows = e->K;
+        ca.tot_state = e->d_state_b; ca.tot_control = e->d_control_b; ca.tot_out = e->d_reuse_costs;
+    }
+    if (e->pending_member >= 0) {
+        // with K_r > 0 it is also the extra rollout of this iteration's ranking (priced with ca.nz)
+        set_noiseless(e, ca, e->pending_member, true, e->Kr > 0);
+        e->pending_member = -1;
+    }
+    if (rows_pre) {
+        e->rows_in_pre = true;
+        e->rows_eps = na.pre_eps;
+    } else {
+        e->rows_in_pre = false;
+    }
+    ca_out = ca;
+    if (reuse) {
+        ReuseArgs ra{};
+        ra.K = e->K; ra.Kr = e->Kr; ra.K_gen = e->K_gen; ra.with_extra = e->extra_added ? 1 : 0;
+        e->extra_added = false;
+        ra.costs = e->d_reuse_costs;
+        ra.src_params = e->d_params_b; ra.src_state = e->d_state_b;
+        ra.x_params = e->d_x_params; ra.x_state = e->d_x_state; ra.x_control = e->d_x_control;
+        ra.state = e->d_state;
+        rr->nz = na;
+        rr->ra = ra;
+    }
+    WeightArgs wa = weight_args(e, e->K_loc, rows_pre ? na.pre_eps : e->d_noise);
+    wa.mode = W_FUSED;
+    wa_out = wa;
+    ua_out = UpdateArgs{e->d_MT, e->d_u, e->d_theta, e->d_stop};
+    e->pending_member = it - 1;
+    if (e->Kr > 0) e->extra_added = true;   // addExtraRollouts: the noiseless rollout pending now
+    return StagedIteration{ca.num_noisy + (ca.x_params ? 1 : 0), ca.tot_rows, reuse};
+}
+
+// an engine's pending noiseless rollout alone in a grouped launch (launch_noiseless' arguments):
+// with K_r > 0 its workgroup also writes the extra rollout's rows of the next reuse ranking
+CostArgs noiseless_args(stomp_engine* e)
+{
+    CostArgs ca{};
+    ca.stop = e->d_stop;
+    ca.num_noisy = 0;
+    set_noiseless(e, ca, e->pending_member, true, e->Kr > 0);
+    if (e->Kr > 0) ca.nz = noise_args(e, e->pending_member + 1);
+    e->pending_member = -1;
+    return ca;
 }
 }  // namespace
 
@@ -81,13 +174,25 @@ int stomp_group_create(stomp_engine* const* engines, int32_t n, stomp_group** ou
         if (!e) return gfail(nullptr, STOMP_E_INVALID, "null engine");
         if (e->device != e0->device || e->stream != e0->stream)
             return gfail(nullptr, STOMP_E_INVALID, "the engines of a group share one device and one stream");
-        if (e->J != e0->J || e->N != e0->N || e->K != e0->K || e->S != e0->S ||
+        if (e->J != e0->J || e->N != e0->N || e->K != e0->K || e->Kr != e0->Kr || e->S != e0->S ||
             rollout_lds_bytes(e->model, e->model.pad_lds) != lds0 || e->model.brick != e0->model.brick)
-            return gfail(nullptr, STOMP_E_INVALID, "the engines of a group have one shape (J, N, K, spheres, model, field layout)");
-        if (e->world != 1 || e->Kr != 0 || !e->pre_on || e->terms_on ||
-            e->split_modes || e->gather || e->use_cum || e->J > 16)
+            return gfail(nullptr, STOMP_E_INVALID,
+                         "the engines of a group have one shape (J, N, K, K_r, spheres, model, field layout)");
+        if (e->world != 1 || !e->pre_on || e->terms_on || e->split_modes || e->gather || e->use_cum || e->J > 16)
             return gfail(nullptr, STOMP_E_UNSUPPORTED,
-                         "groups run single-device engines without reuse, state-cost terms or cumulative costs");
+                         "groups run single-device engines of at most 16 joints without state-cost terms or "
+                         "cumulative costs");
+        if (e->Kr > 0) {
+            // the reuse step is the reused rows' kernel (launch_reuse_rows_ok: K + 1 candidates
+            // ranked by a workgroup, J <= 16, the row kernel's LDS)
+            NoiseArgs na = noise_args(e, 1);
+            na.K_gen_global = e->K - e->Kr;
+            na.row_begin = e->K - e->Kr;
+            if (!launch_reuse_rows_ok(na, e->K, e->Kr))
+                return gfail(nullptr, STOMP_E_UNSUPPORTED,
+                             "groups with reused rollouts take at most 1023 rollouts and a reused row's kernel "
+                             "that fits the LDS");
+        }
     }
     const int nt = weights_group_tiles(e0->J, e0->N, e0->K_loc);
     if (nt <= 0) return gfail(nullptr, STOMP_E_UNSUPPORTED, "rollouts per engine beyond the weights tiles");
@@ -124,12 +229,16 @@ int stomp_group_run(stomp_group* g, int32_t first, int32_t count)
     const int P = (int)g->e.size();
     stomp_engine* e0 = g->e[0];
     for (stomp_engine* e : g->e) {
-        // lockstep: the engines enter the run in one pipeline state
-        if (e->pending_member != e0->pending_member || e->pre_it != e0->pre_it || e->tracking)
+        // lockstep: the engines enter the run in one pipeline state, and with reuse in one
+        // generateRollouts state (which row set an engine writes next is its own: the engines of
+        // a group leave stomp_group_optimize at either parity of the swap)
+        if (e->pending_member != e0->pending_member || e->pre_it != e0->pre_it || e->tracking ||
+            (e->Kr > 0 && (e->reused_next != e0->reused_next || e->extra_added != e0->extra_added)))
             return gfail(g, STOMP_E_INVALID, "the engines of a group are not at the same iteration state");
     }
     const size_t szc = align256(sizeof(CostArgs) * P), szw = align256(sizeof(WeightArgs) * P),
-                 szu = align256(sizeof(UpdateArgs) * P), per = szc + szw + szu;
+                 szu = align256(sizeof(UpdateArgs) * P),
+                 szr = e0->Kr > 0 ? align256(sizeof(ReuseRowArgs) * P) : 0, per = szc + szw + szu + szr;
     const size_t bytes = per * (size_t)count;
     if (g->staged && hipEventSynchronize(g->staged) != hipSuccess)   // h_args free again
         return gfail(g, STOMP_E_DEVICE, "group staging wait failed");
@@ -150,54 +259,24 @@ int stomp_group_run(stomp_group* g, int32_t first, int32_t count)
         if (hipMalloc(&g->d_args, bytes) != hipSuccess) return gfail(g, STOMP_E_DEVICE, "hipMalloc failed");
         g->d_cap = bytes;
     }
-    std::vector<int> nro(count);
+    std::vector<StagedIteration> steps(count);
     std::vector<char> pregen_first(P, 0);
     for (int i = 0; i < count; ++i) {
-        const int it = first + i, member = it - 1;
+        const int it = first + i;
         CostArgs* cas = (CostArgs*)(g->h_args + per * i);
         WeightArgs* was = (WeightArgs*)(g->h_args + per * i + szc);
         UpdateArgs* uas = (UpdateArgs*)(g->h_args + per * i + szc + szw);
+        ReuseRowArgs* ras = (ReuseRowArgs*)(g->h_args + per * i + szc + szw + szu);
         for (int p = 0; p < P; ++p) {
             stomp_engine* e = g->e[p];
-            // enqueue_iteration's pipelined path with pregen rows, arguments only
-            int rc = begin_generate(e);   // K_r = 0: every row generated
-            if (rc) return rc;
-            NoiseArgs na = noise_args(e, it);
-            na.K_gen_global = e->K_gen;
-            na.row_begin = e->K_loc;
-            na.rows_in_pre = 1;
             if (e->pre_it != it) {
                 if (i > 0) return gfail(g, STOMP_E_INVALID, "group pregen rows out of step");
                 pregen_first[p] = 1;
             }
-            CostArgs ca{};
-            ca.stop = e->d_stop;
-            ca.fused_noise = 2;
-            ca.nz = na;
-            ca.params = e->d_params; ca.stride = (long long)e->J * e->N; ca.num_noisy = e->K_loc;
-            ca.member = member; ca.state_out = e->d_state;
-            ca.pre_rows = e->K_loc;
-            ca.pre_next = pregen_args(e, it + 1);
-            // the grouped launch is throughput-bound: its rollout workgroups price their own rows
-            // (pricing in the pregen blocks re-reads theta and eps: cfg5 55.7k vs 53.9-54.5k
-            // problem-it/s)
-            ca.ctl_by_pre = 0;
-            e->pre_it = it + 1;
-            if (e->pending_member >= 0) {
-                set_noiseless(e, ca, e->pending_member, true, false);
-                e->pending_member = -1;
-            }
-            const int n_ro = ca.num_noisy + (ca.x_params ? 1 : 0);
-            if (p == 0) nro[i] = n_ro;
-            else if (n_ro != nro[i]) return gfail(g, STOMP_E_INVALID, "group engines out of step");
-            e->rows_in_pre = true;
-            e->rows_eps = na.pre_eps;
-            cas[p] = ca;
-            WeightArgs wa = weight_args(e, e->K_loc, na.pre_eps);
-            wa.mode = W_FUSED;
-            was[p] = wa;
-            uas[p] = UpdateArgs{e->d_MT, e->d_u, e->d_theta, e->d_stop};
-            e->pending_member = member;
+            const StagedIteration st = stage_iteration(e, it, true, cas[p], was[p], uas[p], ras + p);
+            if (p == 0) steps[i] = st;
+            else if (st.nro != steps[i].nro || st.ntot != steps[i].ntot || st.reuse != steps[i].reuse)
+                return gfail(g, STOMP_E_INVALID, "group engines out of step");
         }
     }
     hipStream_t s = g->stream;
@@ -207,12 +286,19 @@ int stomp_group_run(stomp_group* g, int32_t first, int32_t count)
     if (err == hipSuccess) err = hipEventRecord(g->staged, s);
     if (err != hipSuccess) return gfail(g, STOMP_E_DEVICE, "group argument upload failed");
     const int J = e0->J, N = e0->N, K = e0->K_loc;
+    const NoiseArgs shape = noise_args(e0, first);   // J, N, Nall of the reuse launches
     for (int i = 0; i < count; ++i) {
         unsigned char* base = g->d_args + per * i;
         // with timing on for the group's first engine, its timers hold the group's launches
         {
             Timed tm(e0, T_COST, s);
-            launch_cost_group(e0->model, g->d_models, (const CostArgs*)base, P, nro[i], K, s);
+            launch_cost_group(e0->model, g->d_models, (const CostArgs*)base, P, steps[i].nro, K + steps[i].ntot, s);
+        }
+        if (steps[i].reuse) {
+            // every engine's reuse step (an engine on its own records its reused rows' launch on
+            // this timer too)
+            Timed tm(e0, T_NOISE, s);
+            launch_reuse_rows_group(shape, (const ReuseRowArgs*)(base + szc + szw + szu), P, e0->K, e0->Kr, s);
         }
         {
             Timed tm(e0, T_WEIGHTS, s);
@@ -244,15 +330,7 @@ int stomp_group_synchronize(stomp_group* g)
             all = false;   // the arrays of a run are larger; no run yet: per-engine flushes
         } else {
             CostArgs* cas = (CostArgs*)g->h_args;
-            for (int p = 0; p < P; ++p) {
-                stomp_engine* e = g->e[p];
-                CostArgs ca{};
-                ca.stop = e->d_stop;
-                ca.num_noisy = 0;
-                set_noiseless(e, ca, e->pending_member, true, false);
-                cas[p] = ca;
-                e->pending_member = -1;
-            }
+            for (int p = 0; p < P; ++p) cas[p] = noiseless_args(g->e[p]);
             hipError_t err = hipMemcpyAsync(g->d_args, g->h_args, bytes, hipMemcpyHostToDevice, g->stream);
             if (err == hipSuccess) err = hipEventRecord(g->staged, g->stream);
             if (err != hipSuccess) return gfail(g, STOMP_E_DEVICE, "group argument upload failed");
@@ -298,8 +376,8 @@ int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_i
     // weights, update and track arguments
     const size_t szc = align256(sizeof(CostArgs) * P), szw = align256(sizeof(WeightArgs) * P),
                  szu = align256(sizeof(UpdateArgs) * P), szt = align256(sizeof(TrackArgs) * P),
-                 szm = align256(sizeof(DevModel) * P);
-    const size_t slot_bytes = (2 * szc + 2 * szm + szw + szu + szt) * (size_t)chunk;
+                 szm = align256(sizeof(DevModel) * P), szr = e0->Kr > 0 ? align256(sizeof(ReuseRowArgs) * P) : 0;
+    const size_t slot_bytes = (2 * szc + 2 * szm + szw + szu + szt + szr) * (size_t)chunk;
     auto track_args = [&](int p) {
         stomp_engine* e = g->e[p];
         return TrackArgs{e->d_track, e->d_total, e->d_cf, e->d_cs, e->d_opt_costs, e->d_last_traj, e->d_best_traj,
@@ -322,7 +400,18 @@ int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_i
             return gfail(g, STOMP_E_DEVICE, "group argument upload failed");
     }
     // the engines enter in any state: rows out of the pregen buffers, pending noiseless rollouts
-    // evaluated, the pregen rows of iteration 1 made where another iteration's are held
+    // evaluated, the pregen rows of iteration 1 made where another iteration's are held.  With
+    // reuse they are at one point of generateRollouts (all reuse in iteration 1, or none does)
+    for (stomp_engine* e : g->e)
+        if (e->Kr > 0 && e->reused_next != e0->reused_next)
+            return gfail(g, STOMP_E_INVALID, "the engines of a group are not at the same iteration state");
+    // host-side generateRollouts state after each staged iteration, to restore for every engine
+    // the one of the iteration the device stopped it at (stomp_engine_optimize's)
+    struct HostState { bool reused_next, extra_added; int row_set; };
+    std::vector<std::vector<HostState>> after(P);
+    if (e0->Kr > 0)
+        for (int p = 0; p < P; ++p) after[p].resize((size_t)std::max(g->e[p]->max_it, 0));
+    const NoiseArgs shape = noise_args(e0, 1);   // J, N, Nall of the reuse launches
     for (stomp_engine* e : g->e) {
         materialize_rows(e);
         flush_noiseless(e);
@@ -349,8 +438,9 @@ int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_i
             return o;
         };
         struct Step {
-            int it, nm, nc, nro;
-            size_t cas, was, uas, tas, ccs, mms, cms;
+            int it, nm, nc, nro, ntot;
+            bool reuse;
+            size_t cas, was, uas, tas, ccs, mms, cms, ras;
             const DevModel* m0;
         };
         std::vector<Step> steps;
@@ -373,6 +463,7 @@ int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_i
             st.tas = take(sizeof(TrackArgs) * (st.nm + st.nc));
             st.ccs = take(sizeof(CostArgs) * st.nc);
             st.cms = take(sizeof(DevModel) * st.nc);
+            st.ras = e0->Kr > 0 ? take(sizeof(ReuseRowArgs) * st.nm) : 0;
             // the DevModel list of the rollout launch: once per chunk, again where an engine's
             // max_iterations takes it out within the chunk
             if (st.nm > 0 && main != prev_main) {
@@ -387,53 +478,29 @@ int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_i
             WeightArgs* was = (WeightArgs*)(hb + st.was);
             UpdateArgs* uas = (UpdateArgs*)(hb + st.uas);
             TrackArgs* tas = (TrackArgs*)(hb + st.tas);
+            ReuseRowArgs* ras = (ReuseRowArgs*)(hb + st.ras);
             for (int k = 0; k < st.nm; ++k) {
                 stomp_engine* e = g->e[main[k]];
-                // enqueue_iteration's pipelined path inside the optimize loop, arguments only: the
-                // noise / params rows are copied out of the pregen buffer (pregen blocks enqueued
-                // past a stop overwrite the ping-pong buffers), the weights read d_noise
-                int rc = begin_generate(e);   // K_r = 0: every row generated
-                if (rc) return rc;
-                NoiseArgs na = noise_args(e, it);
-                na.K_gen_global = e->K_gen;
-                na.row_begin = e->K_loc;
-                na.rows_in_pre = 0;
+                // inside the optimize loop the noise / params rows are copied out of the pregen
+                // buffer (pregen blocks enqueued past a stop overwrite the ping-pong buffers), the
+                // weights read d_noise
                 if (e->pre_it != it) return gfail(g, STOMP_E_INVALID, "group pregen rows out of step");
-                CostArgs ca{};
-                ca.stop = e->d_stop;
-                ca.fused_noise = 2;
-                ca.nz = na;
-                ca.params = e->d_params; ca.stride = (long long)e->J * e->N; ca.num_noisy = e->K_loc;
-                ca.member = it - 1; ca.state_out = e->d_state;
-                ca.pre_rows = e->K_loc;
-                ca.pre_next = pregen_args(e, it + 1);
-                ca.ctl_by_pre = 0;   // as stomp_group_run: the rollout workgroups price their own rows
-                e->pre_it = it + 1;
-                if (e->pending_member >= 0) {
-                    set_noiseless(e, ca, e->pending_member, true, false);
-                    e->pending_member = -1;
+                const StagedIteration si = stage_iteration(e, it, false, cas[k], was[k], uas[k], ras + k);
+                if (k == 0) {
+                    st.nro = si.nro;
+                    st.ntot = si.ntot;
+                    st.reuse = si.reuse;
+                } else if (si.nro != st.nro || si.ntot != st.ntot || si.reuse != st.reuse) {
+                    return gfail(g, STOMP_E_INVALID, "group engines out of step");
                 }
-                const int n_ro = ca.num_noisy + (ca.x_params ? 1 : 0);
-                if (k == 0) st.nro = n_ro;
-                else if (n_ro != st.nro) return gfail(g, STOMP_E_INVALID, "group engines out of step");
-                cas[k] = ca;
-                WeightArgs wa = weight_args(e, e->K_loc, e->d_noise);
-                wa.mode = W_FUSED;
-                was[k] = wa;
-                uas[k] = UpdateArgs{e->d_MT, e->d_u, e->d_theta, e->d_stop};
-                e->pending_member = it - 1;
+                if (e->Kr > 0) after[main[k]][it - 1] = {e->reused_next, e->extra_added, e->row_set};
                 tas[k] = track_args(main[k]);
             }
             CostArgs* ccs = (CostArgs*)(hb + st.ccs);
             DevModel* cms = (DevModel*)(hb + st.cms);
             for (int k = 0; k < st.nc; ++k) {
                 stomp_engine* e = g->e[cohort[k]];
-                CostArgs ca{};
-                ca.stop = e->d_stop;
-                ca.num_noisy = 0;
-                set_noiseless(e, ca, e->pending_member, true, false);
-                e->pending_member = -1;
-                ccs[k] = ca;
+                ccs[k] = noiseless_args(e);   // with K_r > 0 the extra rollout's rows too
                 cms[k] = e->model;
                 tas[st.nm + k] = track_args(cohort[k]);
             }
@@ -453,12 +520,18 @@ int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_i
             if (st.nm > 0) {
                 Timed tm(e0, T_COST, s);
                 launch_cost_group(*st.m0, (const DevModel*)(db + st.mms), (const CostArgs*)(db + st.cas), st.nm, st.nro,
-                                  K, s);
+                                  K + st.ntot, s);
             }
             // before this step's weights / update: a break decided on the previous iteration's
             // noiseless rollout leaves theta where the reference leaves it
             if (st.it >= 2) launch_track_group((const TrackArgs*)(db + st.tas), st.nm + st.nc, st.it - 2, J * N, s);
             if (st.nm > 0) {
+                if (st.reuse) {
+                    // after the bookkeeping, as the engine's own loop: a stopped engine's reused
+                    // rows stay the ones of the iteration it stopped at
+                    Timed tm(e0, T_NOISE, s);
+                    launch_reuse_rows_group(shape, (const ReuseRowArgs*)(db + st.ras), st.nm, e0->K, e0->Kr, s);
+                }
                 {
                     Timed tm(e0, T_WEIGHTS, s);
                     launch_weights_group((const WeightArgs*)(db + st.was), st.nm, J, N, K, s);
@@ -520,6 +593,13 @@ int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_i
     for (int p = 0; p < P; ++p) {
         stomp_engine* e = g->e[p];
         const DevTrack& t = e->h_track[2];
+        if (e->Kr > 0 && t.iterations > 0) {
+            // the steps staged past the engine's stop were no-ops on the device
+            const HostState& h = after[p][t.iterations - 1];
+            e->reused_next = h.reused_next;
+            e->extra_added = h.extra_added;
+            if (e->row_set != h.row_set) swap_row_sets(e);
+        }
         if (costs_per_iteration && t.iterations > 0 &&
             hipMemcpy(costs_per_iteration + (size_t)p * costs_stride, e->d_opt_costs, sizeof(double) * t.iterations,
                       hipMemcpyDeviceToHost) != hipSuccess)

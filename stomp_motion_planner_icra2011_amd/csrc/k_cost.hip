@@ -926,8 +926,9 @@ __global__ __launch_bounds__(kWideBlock, kWideBlock > 512 ? 4 : 2) void k_rollou
 
 // one launch for the rollouts of a group of engines of one shape (stomp_group_run): every
 // engine's rollout workgroups first (engine p's nro of them at p nro), then every engine's
-// pregen blocks (npre each, at the default priority behind them all); models and arguments
-// live in device memory, one entry per engine
+// pregen blocks and, on a reusing iteration, its reuse candidates' totals blocks after them (npre
+// = pre_rows + tot_rows each, at the default priority behind the rollouts of all); models and
+// arguments live in device memory, one entry per engine
 template <int BLOCK, bool BRICK>
 __global__ __launch_bounds__(BLOCK, rollout_min_waves<BLOCK>()) void k_rollout_group(const DevModel* ms, const CostArgs* as,
                                                                            int engines, int nro, int npre)

@@ -282,13 +282,15 @@ __device__ __forceinline__ int reuse_choice(const ReuseArgs& ra, int J, int N, i
 // registers and LDS.  The K previous rows' totals come from the rollout launch's totals blocks;
 // the extra rollout's is made here (candidate_total's stage and sums), overlapped with the loads
 // of the two rows rank rr can be besides the extra rollout's (see the prologue).
+// rb: the workgroup's row after a.row_begin (k_noise_rows: blockIdx.x; k_reuse_rows_group: the
+// engines of a group share one launch)
 template <int BLOCK, int NG, bool REUSE>
-__global__ __launch_bounds__(BLOCK) void k_noise_rows(NoiseArgs a, ReuseArgs ra)
+__device__ __forceinline__ void noise_rows_body(const NoiseArgs& a, const ReuseArgs& ra, const int rb)
 {
     extern __shared__ __attribute__((aligned(16))) double lds_nr[];
     if (a.stop && *a.stop) return;
     const int J = a.J, N = a.N, Nall = a.Nall, JP = noise_jp(J), NB = N + kBandBatch;
-    const int r = a.row_begin + blockIdx.x;
+    const int r = a.row_begin + rb;
     const size_t row = (size_t)r * J * N;
     double* eps = lds_nr;              // [NB][JP], zero rows past N and zero columns past J
     double* xs = eps + NB * JP;        // [J][Nall]
@@ -411,6 +413,26 @@ __global__ __launch_bounds__(BLOCK) void k_noise_rows(NoiseArgs a, ReuseArgs ra)
     STAMP(2);
     rollout_control<BLOCK>(a, row, xs, cs, tid);
     STAMP(5);
+}
+
+template <int BLOCK, int NG, bool REUSE>
+__global__ __launch_bounds__(BLOCK) void k_noise_rows(NoiseArgs a, ReuseArgs ra)
+{
+    noise_rows_body<BLOCK, NG, REUSE>(a, ra, blockIdx.x);
+}
+
+// the reuse step of a group of engines of one shape in one launch (stomp_group_run): engine p's
+// Kr reused rows are workgroups [p Kr, (p + 1) Kr); the arguments live in device memory, one entry
+// per engine
+template <int BLOCK, int NG>
+__global__ __launch_bounds__(BLOCK) void k_reuse_rows_group(const ReuseRowArgs* as, int Kr)
+{
+    const int p = blockIdx.x / Kr, rb = blockIdx.x - p * Kr;
+    // read through the constant address space: wave-uniform scalar loads the compiler may repeat,
+    // as it does for a kernel argument (k_rollout_group)
+    using CArgs = const __attribute__((address_space(4))) ReuseRowArgs;
+    const ReuseRowArgs& g = *(const ReuseRowArgs*)((CArgs*)as + p);
+    noise_rows_body<BLOCK, NG, true>(g.nz, g.ra, rb);
 }
 
 
@@ -538,6 +560,29 @@ void launch_reuse_rows(const NoiseArgs& a, const ReuseArgs& ra, hipStream_t s)
     const int rows = a.K_loc - a.row_begin;
     if (rows <= 0) return;
     launch_noise_rows<true>(a, ra, rows, noise_rows_lds(a, ra.K + 8), s);   // the totals + inf padding
+}
+
+namespace {
+template <int BLOCK, int NG>
+void launch_reuse_rows_group_t(const ReuseRowArgs* as, int engines, int Kr, size_t lds, hipStream_t s)
+{
+    if (lds > 64 * 1024) lds_opt_in((const void*)k_reuse_rows_group<BLOCK, NG>, lds);
+    hipLaunchKernelGGL((k_reuse_rows_group<BLOCK, NG>), dim3(engines * Kr), dim3(BLOCK), lds, s, as, Kr);
+}
+}  // namespace
+
+void launch_reuse_rows_group(const NoiseArgs& a0, const ReuseRowArgs* as, int engines, int K, int Kr, hipStream_t s)
+{
+    if (engines <= 0 || Kr <= 0) return;
+    const size_t lds = noise_rows_lds(a0, K + 8);   // as launch_reuse_rows
+    // launch_noise_rows' cases
+    if (a0.N <= 128) {
+        if (a0.J <= 2 * kNoiseJT) launch_reuse_rows_group_t<512, 2>(as, engines, Kr, lds, s);
+        else launch_reuse_rows_group_t<512, 4>(as, engines, Kr, lds, s);
+    } else {
+        if (a0.J <= 2 * kNoiseJT) launch_reuse_rows_group_t<1024, 2>(as, engines, Kr, lds, s);
+        else launch_reuse_rows_group_t<1024, 4>(as, engines, Kr, lds, s);
+    }
 }
 
 size_t price_candidate_lds_bytes(int J, int N)

@@ -437,8 +437,19 @@ struct UpdateArgs {
     double* theta;
     const int* stop;
 };
+// npre: the blocks after an engine's rollouts, its pregen blocks and then its totals blocks
+// (CostArgs::pre_rows + tot_rows, the same for every engine of the launch)
 void launch_cost_group(const DevModel& m0, const DevModel* ms, const CostArgs* as, int engines, int nro, int npre,
                        hipStream_t s);
+// the reuse step of every engine of a group in one launch (launch_reuse_rows' kernel body, one
+// workgroup per engine and reused row); as: [engines] in device memory, every entry of a0's shape
+// (J, N, Nall) with ra.K = K and ra.Kr = Kr rows from nz.row_begin.  Only when launch_reuse_rows_ok
+// holds for the entries.
+struct ReuseRowArgs {
+    NoiseArgs nz;
+    ReuseArgs ra;
+};
+void launch_reuse_rows_group(const NoiseArgs& a0, const ReuseRowArgs* as, int engines, int K, int Kr, hipStream_t s);
 int weights_group_tiles(int J, int N, int K_loc);
 void launch_weights_group(const WeightArgs* as, int engines, int J, int N, int K_loc, hipStream_t s);
 void launch_update_group(int J, int N, const UpdateArgs* as, int engines, hipStream_t s);

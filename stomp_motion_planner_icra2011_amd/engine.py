@@ -441,6 +441,10 @@ class Engine:
         c = np.ascontiguousarray(costs, np.float64)
         _check(load_library().stomp_pi_add_extra_rollouts(self.h, 1, _dp(p), _dp(c)), self.h)
 
+    def pi_reset(self):
+        """setNumRollouts with the engine's counts: the next iteration generates every rollout."""
+        _check(load_library().stomp_pi_reset(self.h), self.h)
+
     def rollouts(self, which: str) -> np.ndarray:
         if which.startswith("x_"):
             shape = (self.N,) if which == "x_state_costs" else (self.J, self.N)
@@ -490,7 +494,10 @@ class Stream:
 
 class EngineGroup:
     """Engines of one shape on one shared stream, advanced in lockstep by shared launches
-    (stomp_group_run: three dispatches per iteration for the whole group)."""
+    (stomp_group_run: three dispatches per iteration for the whole group, four on the iterations
+    that reuse rollouts).  One shape: J, N, K, num_reused_rollouts, spheres, model and field layout
+    agree; at most 16 joints, no cumulative costs, no state-cost terms, one device per engine, and
+    with reused rollouts at most 1023 rollouts."""
 
     def __init__(self, engines):
         self._h = None   # set before the call that may raise, so __del__ has nothing to free
@@ -526,7 +533,8 @@ class EngineGroup:
         (STOMP_DEBUG_GROUP_COMPACT=1 when the group is created: a stopped engine also leaves the
         later launches; same results).  Returns one (stomp_stats, costs[:iterations]) per engine, as Engine.optimize()
         does.  Afterwards every engine is where its own optimize() leaves it (theta, best and last
-        trajectory, rollout rows), not gated, with nothing pending: its own iterate / run and
+        trajectory, rollout rows, with reused rollouts also the extra rollout's rows and the row
+        set of the iteration it stopped at), not gated, with nothing pending: its own iterate / run and
         group.run(first, count) with any first continue from there.  costs_stride: the row length
         of the cost histories (default: the largest max_iterations; smaller is refused)."""
         n = len(self.engines)

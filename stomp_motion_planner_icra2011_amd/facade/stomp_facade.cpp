@@ -184,7 +184,7 @@ bool StompOptimizer::finishOptimize(const stomp_stats& st)
 }
 
 // optimize() for several optimizers at once: their engines as one group (stomp_group_optimize),
-// every problem stopping on its own
+// every problem stopping on its own (with or without reused rollouts: one count for the batch)
 bool StompOptimizer::optimizeBatch(const std::vector<StompOptimizer*>& optimizers)
 {
     if (optimizers.empty()) return true;

@@ -1,0 +1,343 @@
+"""GPU: engine groups with reused rollouts (K_r > 0) -- stomp_group_run, stomp_group_synchronize
+and stomp_group_optimize over engines that rank and keep rollouts of the previous iteration
+(generateRollouts, policy_improvement.cpp:167-225): the reference's own configuration and the
+default of every robot of tests/model_zoo.py.  Every engine of a group must end exactly where its
+own stomp_engine_run / stomp_engine_optimize leaves it and where the CPU oracle of its problem is,
+bit for bit: theta, the visible rows of the current row set, the extra rollout's rows, the
+trajectories, the statistics and the cost history; and its own calls and further group calls must
+continue from there.
+
+Without K_r > 0 in groups stomp_group_create refuses every group made here (error -3)."""
+import functools
+
+import numpy as np
+import pytest
+
+from stomp_motion_planner_icra2011_amd import engine as eng
+from stomp_motion_planner_icra2011_amd import problem as pb
+from oracle import pyoracle as po
+from tests import model_zoo as mz
+from tests.test_gpu_group import FIELDS, Group, advance, variants
+from tests.test_gpu_group_optimize import (INT_STATS, assert_group, assert_results_equal, assert_spread, assert_twin,
+                                           iterations, optimize_oracles, twins_of)
+
+pytestmark = pytest.mark.gpu
+
+ROWS = dict(theta=None, last=None, prob="probabilities", state="state_costs", noise="noise", params="params",
+            control="control_costs", x_params="x_params", x_noise="x_noise", x_control="x_control_costs",
+            x_state="x_state_costs")
+assert set(FIELDS) <= set(ROWS)
+
+
+def state(x):
+    """The six FIELDS of tests/test_gpu_group.py, the control costs and the extra rollout's rows, of
+    an engine or an oracle."""
+    out = dict(theta=x.theta(), last=x.last_trajectory())
+    for k, which in ROWS.items():
+        if which is not None:
+            out[k] = x.rollouts(which)
+    return out
+
+
+def assert_same(a, b, tag):
+    for k in ROWS:
+        np.testing.assert_array_equal(a[k], b[k], err_msg=f"{tag} {k}")
+
+
+def problems(P, K, Kr, grid=64):
+    """tests/test_gpu_group.py's `problems`, with reuse."""
+    base = pb.make_problem(grid_n=grid, num_rollouts=K, num_reused_rollouts=Kr)
+    d = np.random.default_rng(5).uniform(-0.15, 0.15, (P, 2, base.J))
+    return [pb.make_problem(grid_n=grid, num_rollouts=K, num_reused_rollouts=Kr, seed=base.seed + 1 + i,
+                            start=list(base.start + d[i, 0]), goal=list(base.goal + d[i, 1])) for i in range(P)]
+
+
+CHUNKS = [(1, 1), (2, 2), (4, 3)]   # the generate-all iteration alone; the second starts with a reusing one
+
+
+def run_in_chunks(ps, chunks=CHUNKS, threads=1):
+    """After each chunk and a synchronize: every engine against a twin that made the same run calls
+    on its own and against its oracle after the same iterations."""
+    g = Group(ps)
+    twins = [eng.Engine(p) for p in ps]
+    oracles = [po.Oracle(p, threads=threads) for p in ps]
+    for first, count in chunks:
+        g.group.run(first, count)
+        g.group.synchronize()
+        advance(oracles, first, count)
+        for i, (ge, te, o) in enumerate(zip(g.engines, twins, oracles)):
+            te.run(first, count)
+            te.synchronize()
+            a = state(ge)
+            assert_same(a, state(te), f"after ({first}, {count}): engine {i} against its own run,")
+            assert_same(a, state(o), f"after ({first}, {count}): engine {i} against its oracle,")
+    for t in twins:
+        t.close()
+    g.close()
+
+
+@pytest.mark.parametrize("K,Kr", [(20, 10), (10, 5), (12, 11), (12, 1), (65, 8)])
+def test_run_matches_single_engines_and_oracles(K, Kr):
+    run_in_chunks(problems(3, K, Kr), threads=8 if K > 20 else 1)
+
+
+@pytest.mark.parametrize("name,waypoints", [("chain5", 40), ("fork12", 40), ("hand9", 40), ("chain5", 10),
+                                            ("chain5", 66), ("chain5", 129), ("chain5", 130), ("chain5", 200)])
+def test_reuse_kernel_shapes(name, waypoints):
+    # chain5: J = 5, two joint groups of the projection; fork12: J = 12, four; chain5 at N = 9, 65,
+    # 128, then 129 (the first 1024-thread instantiation) and 199
+    ps = variants(mz.ZOO[name], 3, waypoints=waypoints)
+    assert (ps[0].params.num_rollouts, ps[0].params.num_reused_rollouts) == (12, 5) and ps[0].N == waypoints - 1
+    run_in_chunks(ps)
+
+
+def test_one_reuse_launch_per_iteration_not_one_per_engine():
+    ps = problems(4, 20, 10)
+    g = Group(ps)
+    g.engines[0].set_timing(True)
+    g.group.run(1, 5)
+    g.group.synchronize()
+    noise, cost = g.engines[0].timing("noise")[1], g.engines[0].timing("rollout_cost")[1]
+    print("noise launches", noise, "rollout launches", cost)
+    assert noise == 4      # one grouped reuse launch per reusing iteration (2 .. 5)
+    assert cost == 5
+    oracles = [po.Oracle(p) for p in ps]
+    advance(oracles, 1, 5)
+    for i, (e, o) in enumerate(zip(g.engines, oracles)):
+        assert_same(state(e), state(o), f"engine {i}")
+    g.close()
+
+
+# ------------------------------------------------------------------------------------------------
+# stomp_group_optimize
+
+@functools.lru_cache(maxsize=None)
+def recipe(K=20, Kr=10, max_it=60, P=16):
+    """tests/test_gpu_group_optimize.py's recipe with reuse (shared between the tests, never written)."""
+    base = pb.make_problem(grid_n=64, num_rollouts=K, num_reused_rollouts=Kr)
+    d = np.random.default_rng(11).uniform(-0.15, 0.15, (P, 2, base.J))
+    return tuple(pb.make_problem(grid_n=64, num_rollouts=K, num_reused_rollouts=Kr, seed=base.seed + 1 + i,
+                                 start=list(base.start + d[i, 0]), goal=list(base.goal + d[i, 1]),
+                                 max_iterations=max_it, max_iterations_after_collision_free=2) for i in range(P))
+
+
+@functools.lru_cache(maxsize=None)
+def pr2(idx):
+    """(problems, oracles after optimize, snapshots) of the recipe's problems `idx`; the snapshots are
+    read-only, the oracle objects are continued by one test only."""
+    ps = [recipe()[i] for i in idx]
+    oracles, snaps = optimize_oracles(ps)
+    return ps, oracles, snaps
+
+
+ALL16 = tuple(range(16))
+X_ROWS = ("x_params", "x_noise", "x_control_costs", "x_state_costs")
+ITER_ROWS = ("params", "noise", "control_costs", "state_costs", "probabilities") + X_ROWS
+
+
+def assert_stops_spread(snaps):
+    """On the oracle's own counts: at least four distinct stops below 60, engines that run out their
+    60 iterations, and stops at both parities of the row-set swap."""
+    assert_spread(snaps, 60)
+    its = iterations(snaps)
+    assert {n % 2 for n in its} == {0, 1}, its
+
+
+def full_state(e):
+    out = state(e)
+    out["best"] = e.best_trajectory()
+    return out
+
+
+def continue_against_oracle(o, e, first, count):
+    for it in range(first, first + count):
+        oc, ec = o.iterate(it), e.iterate(it)
+        assert ec[0] == oc[0] and ec[1] == oc[1], (it, ec, oc)
+        for f in ITER_ROWS:
+            np.testing.assert_array_equal(e.rollouts(f), o.rollouts(f), err_msg=f"iteration {it} {f}")
+        np.testing.assert_array_equal(e.theta(), o.theta(), err_msg=f"theta after iteration {it}")
+        np.testing.assert_array_equal(e.last_trajectory(), o.last_trajectory())
+
+
+def test_optimize_stops_spread():
+    ps, oracles, snaps = pr2(ALL16)
+    assert_stops_spread(snaps)
+    g = Group(ps)
+    results = g.group.optimize()
+    assert_group(g, results, snaps)
+    # four engines against twins that ran their own stomp_engine_optimize: the earliest and the
+    # latest early stop, one that ran out its iterations, engine 0, and both parities of the stop
+    its = iterations(snaps)
+    early = [i for i in range(16) if its[i] < 60]
+    picks = sorted({0, min(early, key=lambda i: its[i]), max(early, key=lambda i: its[i]), its.index(60)})
+    picks += [i for i in range(16) if i not in picks][: 4 - len(picks)]
+    assert {its[i] % 2 for i in picks} == {0, 1}, [its[i] for i in picks]
+    for i in picks:
+        twin = eng.Engine(ps[i])
+        tres = twin.optimize()
+        assert_twin(g.engines[i], results[i], twin, tres, f"engine {i} against its twin")
+        a, b = full_state(g.engines[i]), full_state(twin)
+        for k in a:
+            np.testing.assert_array_equal(a[k], b[k], err_msg=f"engine {i} against its twin {k}")
+        twin.close()
+    # a wrongly restored row_set / reused_next / extra_added shows here
+    for i, (o, e) in enumerate(zip(oracles, g.engines)):
+        continue_against_oracle(o, e, its[i] + 1, 2)
+    g.close()
+
+
+@pytest.mark.parametrize("robot", ["chain5", "fork12"])
+def test_per_engine_caps(robot):
+    # never reusing, one reuse, and both sides of the chunk of 8
+    caps = (1, 2, 7, 8, 9, 20)
+    ps = variants(mz.ZOO[robot], len(caps), max_iterations_after_collision_free=1000)
+    assert (ps[0].params.num_rollouts, ps[0].params.num_reused_rollouts) == (12, 5)
+    for p, c in zip(ps, caps):
+        p.params.max_iterations = c
+    oracles, snaps = optimize_oracles(ps)
+    assert tuple(iterations(snaps)) == caps, iterations(snaps)
+    g = Group(ps)
+    results = g.group.optimize(costs_stride=20)
+    assert_group(g, results, snaps)
+    for i, (e, o) in enumerate(zip(g.engines, oracles)):
+        for f in X_ROWS:   # the extra rollout's rows of the engines the flush of their cap ends
+            np.testing.assert_array_equal(e.rollouts(f), o.rollouts(f), err_msg=f"engine {i} {f}")
+    g.close()
+
+
+@pytest.mark.parametrize("compact", ["0", "1"])
+def test_compaction_on_and_off(monkeypatch, compact):
+    monkeypatch.setenv("STOMP_DEBUG_GROUP_COMPACT", compact)   # read when the group is created
+    ps, _, snaps = pr2(ALL16)
+    assert_stops_spread(snaps)
+    g = Group(ps)
+    results = g.group.optimize()
+    assert_group(g, results, snaps)
+    g.close()
+
+
+LIFECYCLE = (1, 2, 8, 11)
+
+
+def assert_states_equal(g, twins, tag):
+    for i, (ge, te) in enumerate(zip(g.engines, twins)):
+        a, b = full_state(ge), full_state(te)
+        for k in a:
+            np.testing.assert_array_equal(a[k], b[k], err_msg=f"{tag}: engine {i} {k}")
+
+
+def close_all(g, twins):
+    for t in twins:
+        t.close()
+    g.close()
+
+
+def test_lifecycle_run_then_optimize():
+    ps = [recipe()[i] for i in LIFECYCLE]
+    g, twins = Group(ps), twins_of(ps)
+    g.group.run(1, 3)
+    gres = g.group.optimize()
+    for t in twins:
+        t.run(1, 3)
+    tres = [t.optimize() for t in twins]
+    assert_results_equal(gres, tres, "run then optimize")
+    assert_states_equal(g, twins, "run then optimize")
+    close_all(g, twins)
+
+
+def test_lifecycle_optimize_then_run():
+    # the engines leave the optimize loop at both parities of the row-set swap
+    ps = [recipe()[i] for i in LIFECYCLE]
+    g, twins = Group(ps), twins_of(ps)
+    gres = g.group.optimize()
+    assert {int(st.iterations) % 2 for st, _ in gres} == {0, 1}, [int(st.iterations) for st, _ in gres]
+    g.group.run(61, 2)
+    g.group.synchronize()
+    tres = [t.optimize() for t in twins]
+    for t in twins:
+        t.run(61, 2)
+        t.synchronize()
+    assert_results_equal(gres, tres, "optimize then run")
+    assert_states_equal(g, twins, "optimize then run")
+    close_all(g, twins)
+
+
+def test_lifecycle_optimize_twice():
+    ps = [recipe()[i] for i in LIFECYCLE]
+    g, twins = Group(ps), twins_of(ps)
+    g1, g2 = g.group.optimize(), g.group.optimize()
+    t1 = [t.optimize() for t in twins]
+    t2 = [t.optimize() for t in twins]
+    assert_results_equal(g1, t1, "first optimize")
+    assert_results_equal(g2, t2, "second optimize")
+    assert_states_equal(g, twins, "optimize twice")
+    close_all(g, twins)
+
+
+def test_lifecycle_a_members_own_iteration_puts_the_group_out_of_step():
+    ps = [recipe()[i] for i in LIFECYCLE]
+    g, twins = Group(ps), twins_of(ps)
+    g.group.run(1, 3)
+    for t in twins:
+        t.run(1, 3)
+    assert g.engines[2].iterate(4) == twins[2].iterate(4)
+    before = [full_state(e) for e in g.engines]
+    with pytest.raises(RuntimeError) as ei:
+        g.group.run(5, 2)
+    assert "error -1" in str(ei.value) and "not at the same iteration state" in str(ei.value), str(ei.value)
+    for i, (e, b) in enumerate(zip(g.engines, before)):   # no engine touched
+        a = full_state(e)
+        for k in a:
+            np.testing.assert_array_equal(a[k], b[k], err_msg=f"engine {i} {k}")
+    for t in twins:
+        t.synchronize()
+    assert_states_equal(g, twins, "after the refused run")
+    close_all(g, twins)
+
+
+def assert_untouched_then_grouped(s, es, ps):
+    """After a refused creation: the engines still match their oracles on iterate(1), and a valid
+    group on the same stream works."""
+    for e, p in zip(es, ps):
+        o = po.Oracle(p)
+        assert e.iterate(1) == o.iterate(1)
+        np.testing.assert_array_equal(e.theta(), o.theta())
+    qs = variants(mz.chain5, 2)
+    fs = [eng.Engine(q, stream=s.ptr) for q in qs]
+    g = eng.EngineGroup(fs)
+    g.run(1, 3)
+    g.synchronize()
+    oracles = [po.Oracle(q) for q in qs]
+    advance(oracles, 1, 3)
+    for i, (e, o) in enumerate(zip(fs, oracles)):
+        assert_same(state(e), state(o), f"engine {i} of the next group")
+    g.close()
+    for e in fs + list(es):
+        e.close()
+
+
+def test_refuses_engines_of_two_reuse_counts():
+    ps = [mz.chain5(Kr=5), mz.chain5(Kr=4)]
+    s = eng.Stream()
+    es = [eng.Engine(p, stream=s.ptr) for p in ps]
+    with pytest.raises(RuntimeError) as ei:
+        eng.EngineGroup(es)
+    assert "error -1" in str(ei.value), str(ei.value)      # STOMP_E_INVALID: one shape
+    assert_untouched_then_grouped(s, es, ps)
+    s.close()
+
+
+@pytest.mark.parametrize("what", ["cumulative", "torque"])
+def test_refuses_reuse_with_cumulative_costs_or_a_torque_term(what):
+    if what == "cumulative":
+        ps = variants(mz.chain5, 2, use_cumulative_costs=True)
+    else:
+        ps = variants(mz.chain5, 2, terms=True, torque_cost_weight=0.001)
+    assert ps[0].params.num_reused_rollouts == 5
+    s = eng.Stream()
+    es = [eng.Engine(p, stream=s.ptr) for p in ps]
+    with pytest.raises(RuntimeError) as ei:
+        eng.EngineGroup(es)
+    assert "error -3" in str(ei.value), str(ei.value)      # STOMP_E_UNSUPPORTED
+    assert_untouched_then_grouped(s, es, ps)
+    s.close()

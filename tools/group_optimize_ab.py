@@ -8,7 +8,10 @@ max_iterations_after_collision_free = 2.  Every way optimizes the same engines f
 initial trajectories, five repeats each; the three must agree on every statistic and best
 trajectory.
 
-    python tools/group_optimize_ab.py [--out FILE] [--problems 64] [--repeats 5]
+--reused K_r gives every problem K_r reused rollouts (0: none, cfg5); every repeat then starts from
+a reset generateRollouts state too, so that all of them optimize the same thing.
+
+    python tools/group_optimize_ab.py [--out FILE] [--problems 64] [--repeats 5] [--reused 0]
 """
 import argparse
 import os
@@ -34,18 +37,20 @@ def main():
     ap.add_argument("--grid", type=int, default=256)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--max-iterations", type=int, default=200)
+    ap.add_argument("--reused", type=int, default=0, help="num_reused_rollouts of every problem")
     args = ap.parse_args()
     P = args.problems
-    base = pb.make_problem(dof=7, waypoints=100, grid_n=args.grid, num_rollouts=args.rollouts, num_reused_rollouts=0,
-                           build_grid=False)
+    base = pb.make_problem(dof=7, waypoints=100, grid_n=args.grid, num_rollouts=args.rollouts,
+                           num_reused_rollouts=args.reused, build_grid=False)
     sdf = eng.DeviceBuffer(2 * args.grid ** 3, device=0)
     eng.sdf_build_device(base, sdf.ptr)
     offsets = np.random.default_rng(1234).uniform(-0.15, 0.15, (P, 2, base.J))
     stream = eng.Stream(0)
     engines = []
     for i in range(P):
-        p = pb.make_problem(dof=7, waypoints=100, grid_n=args.grid, num_rollouts=args.rollouts, num_reused_rollouts=0,
-                            build_grid=False, seed=base.seed + 1 + i, start=list(base.start + offsets[i, 0]),
+        p = pb.make_problem(dof=7, waypoints=100, grid_n=args.grid, num_rollouts=args.rollouts,
+                            num_reused_rollouts=args.reused, build_grid=False, seed=base.seed + 1 + i,
+                            start=list(base.start + offsets[i, 0]),
                             goal=list(base.goal + offsets[i, 1]), max_iterations=args.max_iterations,
                             max_iterations_after_collision_free=2)
         engines.append(eng.Engine(p, device=0, sdf_device_ptr=sdf.ptr, stream=stream.ptr))
@@ -61,11 +66,14 @@ def main():
             e.set_theta(th)
         for e in engines:
             e.synchronize()
+            if args.reused:
+                e.pi_reset()   # the first iteration generates every rollout again
 
     ways = [("a: one stomp_engine_optimize per problem", lambda: [e.optimize() for e in engines]),
             ("b: stomp_group_optimize, compaction off", group_all.optimize),
             ("c: stomp_group_optimize, compaction on", group_compact.optimize)]
-    lines = [f"group_optimize_ab: {P} problems, K = {args.rollouts}, {args.grid}^3, max_iterations = "
+    reused = f", K_r = {args.reused}" if args.reused else ""
+    lines = [f"group_optimize_ab: {P} problems, K = {args.rollouts}{reused}, {args.grid}^3, max_iterations = "
              f"{args.max_iterations}, max_iterations_after_collision_free = 2, {args.repeats} repeats after one warm-up"]
     reference = None
     medians = {}
