@@ -237,7 +237,8 @@ int stomp_engine_optimize(stomp_engine* e, stomp_stats* stats, double* costs_per
 /* STOMPStatistics.torques after optimize (stomp_optimizer.cpp:384-398): per free waypoint,
  * sum_j |tau_j| of the best trajectory by inverse dynamics over the torque chain (N doubles).
  * Needs the segment inertias in the descriptor (also with the torque term off);
- * STOMP_E_UNSUPPORTED without them. */
+ * STOMP_E_UNSUPPORTED without them, and with the term off also when the chain's kernel needs more
+ * than 160 KiB of LDS (the message says which of the two). */
 int stomp_engine_get_best_torques(stomp_engine* e, double* torques);
 
 /* PolicyImprovement (policy_improvement.h:86-126) step by step, for a caller that executes the

@@ -111,6 +111,7 @@ def lib():
         l.so_sdf_distance.argtypes = [P, C.c_double, C.c_double, C.c_double]
         l.so_potential.argtypes = [P, C.c_int, dp, dp]
         l.so_inverse_dynamics.argtypes = [P, dp, dp, dp, dp]
+        l.so_orientation_probe.argtypes = [P, dp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), dp]
         l.so_atan2.restype = C.c_double
         l.so_atan2.argtypes = [C.c_double, C.c_double]
         l.so_asin.restype = C.c_double
@@ -364,6 +365,16 @@ class Oracle:
         if lib().so_inverse_dynamics(self.h, _dp(a[0]), _dp(a[1]), _dp(a[2]), _dp(tau)) != 0:
             raise RuntimeError("torque term off")
         return tau
+
+    def orientation_probe(self, q, constraint: int):
+        """so_orientation_probe: (quaternion branch 0..3, gimbal state -1 / 0 / +1, signed (roll,
+        pitch, yaw)) of the oracle's own orientation-constraint arithmetic at the joint vector q."""
+        qq = np.ascontiguousarray(q, np.float64)
+        branch, gimbal = C.c_int(), C.c_int()
+        rpy = np.zeros(3)
+        if lib().so_orientation_probe(self.h, _dp(qq), constraint, C.byref(branch), C.byref(gimbal), _dp(rpy)) != 0:
+            raise IndexError(constraint)
+        return branch.value, gimbal.value, rpy
 
     def sdf_distance(self, x, y, z) -> float:
         return lib().so_sdf_distance(self.h, x, y, z)

@@ -533,8 +533,9 @@ static void bt_inverse(const double* M, double* O)   /* btMatrix3x3::inverse */
     O[6] = co2 * s; O[7] = bt_cofac(M, 0, 1, 2, 0) * s; O[8] = bt_cofac(M, 0, 0, 1, 1) * s;
 }
 
-/* KDL Rotation::GetQuaternion (row-major R) */
-static void kdl_get_quaternion(const double* R, double* x, double* y, double* z, double* w)
+/* KDL Rotation::GetQuaternion (row-major R); returns the branch taken (0: trace, 1 / 2 / 3: the
+ * single-precision x / y / z branches), which only so_orientation_probe reads */
+static int kdl_get_quaternion(const double* R, double* x, double* y, double* z, double* w)
 {
     const double trace = R[0] + R[4] + R[8];
     if (trace > 1e-12) {
@@ -543,29 +544,34 @@ static void kdl_get_quaternion(const double* R, double* x, double* y, double* z,
         *x = (R[7] - R[5]) * s;
         *y = (R[2] - R[6]) * s;
         *z = (R[3] - R[1]) * s;
+        return 0;
     } else if (R[0] > R[4] && R[0] > R[8]) {
         const float s = (float)(2.0 * sqrtf((float)(1.0 + R[0] - R[4] - R[8])));
         *w = (R[7] - R[5]) / s;
         *x = 0.25 * s;
         *y = (R[1] + R[3]) / s;
         *z = (R[2] + R[6]) / s;
+        return 1;
     } else if (R[4] > R[8]) {
         const float s = (float)(2.0 * sqrtf((float)(1.0 + R[4] - R[0] - R[8])));
         *w = (R[2] - R[6]) / s;
         *x = (R[1] + R[3]) / s;
         *y = 0.25 * s;
         *z = (R[5] + R[7]) / s;
+        return 2;
     } else {
         const float s = (float)(2.0 * sqrtf((float)(1.0 + R[8] - R[0] - R[4])));
         *w = (R[3] - R[1]) / s;
         *x = (R[2] + R[6]) / s;
         *y = (R[5] + R[7]) / s;
         *z = 0.25 * s;
+        return 3;
     }
 }
 
-/* btMatrix3x3::getRPY -> getEulerYPR(yaw, pitch, roll, 1) */
-static void bt_get_rpy(const double* M, double* roll, double* pitch, double* yaw, int libm)
+/* btMatrix3x3::getRPY -> getEulerYPR(yaw, pitch, roll, 1); returns the gimbal state (+1 / -1: the
+ * |M[6]| >= 1 branch by the sign of M[6], 0: the regular branch), which only so_orientation_probe reads */
+static int bt_get_rpy(const double* M, double* roll, double* pitch, double* yaw, int libm)
 {
     const double pi = 3.1415926535897932384626433832795029;
     if (fabs(M[6]) >= 1.0) {
@@ -574,9 +580,11 @@ static void bt_get_rpy(const double* M, double* roll, double* pitch, double* yaw
         if (M[6] > 0.0) {
             *pitch = pi / 2.0;
             *roll = *pitch + delta;
+            return 1;
         } else {
             *pitch = -pi / 2.0;
             *roll = -*pitch + delta;
+            return -1;
         }
     } else {
         double a = M[6];   /* btAsin clamps to [-1, 1] */
@@ -594,6 +602,7 @@ static void bt_get_rpy(const double* M, double* roll, double* pitch, double* yaw
         *roll = libm ? atan2(M[7] / cp, M[8] / cp) : dm_atan2(M[7] / cp, M[8] / cp);
         *yaw = libm ? atan2(M[3] / cp, M[0] / cp) : dm_atan2(M[3] / cp, M[0] / cp);
     }
+    return 0;
 }
 
 static void bt_mul(const double* A, const double* B, double* C)   /* btMatrix3x3 operator* */
@@ -627,20 +636,48 @@ static void oc_init(const so_orientation_constraint* c, struct oc_eval* o)
     if (o->tol[2] >= M_PI) o->yw = 0.0;
 }
 
-/* OrientationConstraintEvaluator::getCost (constraint_evaluator.cpp:80-114); returns satisfied */
-static int oc_cost(const struct oc_eval* o, const double* R, double* cost)
+/* the signed roll / pitch / yaw of getCost's orientation error (constraint_evaluator.cpp:80-98),
+ * with the quaternion branch and the gimbal state the two third-party functions took */
+static void oc_angles(const struct oc_eval* o, const double* R, double* roll, double* pitch, double* yaw, int* branch,
+                      int* gimbal)
 {
-    double x, y, z, w, M[9], res[9], roll, pitch, yaw;
-    kdl_get_quaternion(R, &x, &y, &z, &w);
+    double x, y, z, w, M[9], res[9];
+    *branch = kdl_get_quaternion(R, &x, &y, &z, &w);
     bt_from_quat(x, y, z, w, M);
     if (!o->body_fixed) bt_mul(M, o->ninv, res);
     else bt_mul(o->ninv, M, res);
-    bt_get_rpy(res, &roll, &pitch, &yaw, o->libm);
+    *gimbal = bt_get_rpy(res, roll, pitch, yaw, o->libm);
+}
+
+/* OrientationConstraintEvaluator::getCost (constraint_evaluator.cpp:80-114); returns satisfied */
+static int oc_cost(const struct oc_eval* o, const double* R, double* cost)
+{
+    double roll, pitch, yaw;
+    int branch, gimbal;
+    oc_angles(o, R, &roll, &pitch, &yaw, &branch, &gimbal);
     roll = fabs(roll);
     pitch = fabs(pitch);
     yaw = fabs(yaw);
     *cost = o->weight * (o->rw * roll + o->pw * pitch + o->yw * yaw);
     return !(roll > o->tol[0] || pitch > o->tol[1] || yaw > o->tol[2]);
+}
+
+/* TEST HOOK: which branches oc_cost takes for the joint vector q (length J) and constraint c, by
+ * the functions oc_cost itself calls: branch 0..3 of kdl_get_quaternion, gimbal -1 / 0 / +1 of
+ * bt_get_rpy, rpy = the signed roll, pitch, yaw.  The tests' census reads it; nothing else does. */
+int so_orientation_probe(const so_problem* P, const double* q, int c, int* branch, int* gimbal, double* rpy)
+{
+    if (c < 0 || c >= P->noc) return -1;
+    const struct oc_eval* o = &P->oc[c];
+    frame_t* frames = (frame_t*)malloc(sizeof(frame_t) * (size_t)P->nseg);
+    for (int s = 0; s <= o->seg; ++s) {
+        const so_segment* sg = &P->segs[s];
+        const double qv = sg->q_index >= 0 ? q[sg->q_index] : 0.0;
+        segment_frame(sg, sg->parent >= 0 ? &frames[sg->parent] : NULL, qv, &frames[s], P->cfg.ref_arith >= 3);
+    }
+    oc_angles(o, frames[o->seg].R, &rpy[0], &rpy[1], &rpy[2], branch, gimbal);
+    free(frames);
+    return 0;
 }
 
 /* ---------------------------------------------------------------- distance field

@@ -145,6 +145,10 @@ typedef struct {
 double so_atan2(double y, double x);
 double so_asin(double x);
 int so_inverse_dynamics(const so_problem* P, const double* q, const double* qd, const double* qdd, double* tau);
+/* test hook: the branches OrientationConstraintEvaluator::getCost takes at the joint vector q for
+ * constraint c: KDL GetQuaternion's branch (0 trace, 1 / 2 / 3), bullet getRPY's gimbal state
+ * (-1 / 0 / +1) and the signed roll, pitch, yaw (rpy[3]); -1 when c is no constraint */
+int so_orientation_probe(const so_problem* P, const double* q, int c, int* branch, int* gimbal, double* rpy);
 
 typedef struct {
     int iterations;             /* iterations run */

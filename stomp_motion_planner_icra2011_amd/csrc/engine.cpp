@@ -596,6 +596,8 @@ int stomp_engine_get_best_torques(stomp_engine* e, double* torques)
 {
     if (!e) return fail(nullptr, STOMP_E_INVALID, "null engine");
     DeviceGuard dg(e->device);
+    if (!e->torque_stats && e->terms.nchain > 0)   // a valid chain that build_terms found too large
+        return fail(e, STOMP_E_UNSUPPORTED, "torque statistics kernel needs %zu B of LDS", terms_lds_bytes(e->terms));
     if (!e->torque_stats) return fail(e, STOMP_E_UNSUPPORTED, "no torque chain (segment inertias not given)");
     flush_noiseless(e);
     HIP_TRY(e, hipMemsetAsync(e->d_tq_state, 0, sizeof(double) * e->N, e->stream));

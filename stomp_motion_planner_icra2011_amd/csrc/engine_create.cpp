@@ -567,8 +567,12 @@ int build_terms(stomp_engine* e, const stomp_engine_desc* d, const HostTables& t
         if (terms_lds_bytes(t) > 160 * 1024) {
             if (e->terms_on)
                 return fail(e, STOMP_E_UNSUPPORTED, "state-terms kernel needs %zu B of LDS", terms_lds_bytes(t));
-            e->torque_stats = false;
+            e->torque_stats = false;   // the chain stays in e->terms: get_best_torques says why it cannot run
         }
+        if (getenv("STOMP_DEBUG_LEAN_PRINT"))   // the launch launch_terms takes (read-only: tests and tables)
+            fprintf(stderr, "stomp: terms J %d N %d nchain %d noc %d torque %d stats %d, k_terms<%d>, LDS %zu B, "
+                            "opt-in %d\n", J, N, t.nchain, t.noc, t.torque, e->torque_stats ? 1 : 0, N <= 128 ? 128 : 256,
+                    terms_lds_bytes(t), terms_lds_bytes(t) > 64 * 1024 ? 1 : 0);
         if (e->terms_on)
             if (int rc = dev_alloc(e, &e->d_terms_traj, (size_t)e->K_loc * J * N)) return rc;
         if (e->torque_stats) {

@@ -328,8 +328,10 @@ __global__ __launch_bounds__(BLOCK) void k_terms(TermsModel m, TermsArgs a)
 
 size_t terms_lds_bytes(const TermsModel& m)
 {
-    const size_t a = (size_t)(3 * m.J + 6 * m.nchain) * m.N * sizeof(double);
-    return a > (size_t)m.N * sizeof(double) ? a : (size_t)m.N * sizeof(double);
+    // the first row of F also holds the costs for the total: without a torque chain (constraints
+    // only, nchain = 0) F is that one row
+    const size_t rows = (size_t)3 * m.J + (m.nchain > 0 ? (size_t)6 * m.nchain : 1);
+    return rows * m.N * sizeof(double);
 }
 
 void launch_terms(const TermsModel& m, const TermsArgs& a, hipStream_t s)

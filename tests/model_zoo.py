@@ -22,7 +22,13 @@ Every segment that carries a joint has a non-identity fixed rotation and a skew 
 segments mix identity and non-identity rotations.  Radii, clearances and joint costs vary per
 sphere and per joint.  The robots stand near the low corner of the grid, so perturbed rows leave
 the field, and each scene is a few boxes put where the default trajectory passes (collision and
-hinge zone).  `census` counts what the rows handed to execute actually reach; the tests assert it
+hinge zone).
+
+The `terms=True` variants carry what the state-cost terms read (tests/STATE_TERMS.md): a synthetic
+inertia on every link and a torque chain, whose shape differs per robot (one segment; a fixed first,
+inner or last segment; a root that is not the tree's), and `hand9_constraints` / `fork12_constraints`
+put orientation constraints on other branches than the torque tip.  `crafted_problem` is a robot with
+unit axes and fixed rotations of entries 0 / +-1 whose constrained frames are exact at q = 0.  `census` counts what the rows handed to execute actually reach; the tests assert it
 before they compare anything.
 """
 import numpy as np
@@ -152,18 +158,38 @@ def _problem(b, start, goal, limits, alt, K, Kr, waypoints, shape, overrides, se
     return p
 
 
+def _inertias(b, rng):
+    """A synthetic inertia on every segment below the base (mass, centre of mass, a diagonally
+    dominant inertia tensor)."""
+    for g in b.segs[1:]:
+        c = rng.uniform(-0.05, 0.05, 3)
+        d = rng.uniform(0.002, 0.02, 3)
+        o = rng.uniform(-0.001, 0.001, 3)
+        g.inertia = pb.Inertia(float(rng.uniform(0.3, 2.5)), tuple(c), (d[0], d[1], d[2], o[0], o[1], o[2]))
+
+
 def _start_goal(rng, J, span=1.0):
     return rng.uniform(-span, span, J), rng.uniform(-span, span, J)
 
 
-def stick1(K=12, Kr=5, waypoints=40, shape=None, **overrides):
+def stick1(K=12, Kr=5, waypoints=40, shape=None, terms=False, pedestal=False, **overrides):
+    """terms=True: inertias and a torque chain of one segment (base -> wand: the chain's first
+    segment is its last).  pedestal=True (with terms): a fixed pedestal under the wand, and the chain
+    pedestal, wand, wand_tip: a fixed first segment and a fixed last one around the only joint."""
     b = _Builder(101, 1)
-    s = b.joint("wand", 0, 0, 0.05)
+    parent = b.fixed("pedestal", 0, 0.06) if terms and pedestal else 0
+    s = b.joint("wand", parent, 0, 0.05)
     tip = _dir(b.rng, 0.5)
     b.add("wand_tip", s, -1, tip)
     b.balls(s, tip, 6, radius=(0.04, 0.07))
     start, goal = np.array([-0.9]), np.array([0.8])
-    return _problem(b, start, goal, _limits(b.rng, start, goal), False, K, Kr, waypoints, shape, overrides)
+    lim = _limits(b.rng, start, goal)
+    if terms:
+        _inertias(b, b.rng)
+    p = _problem(b, start, goal, lim, False, K, Kr, waypoints, shape, overrides)
+    if terms:
+        p.torque_root, p.torque_tip = "base", ("wand_tip" if pedestal else "wand")
+    return p
 
 
 def chain5(K=12, Kr=5, waypoints=40, shape=None, terms=False, robot_seed=105, **overrides):
@@ -195,11 +221,7 @@ def chain5(K=12, Kr=5, waypoints=40, shape=None, terms=False, robot_seed=105, **
     lim = _limits(rng, start, goal, unlimited=(2,))
     lim[3] = (0.4, 0.4)
     if terms:
-        for g in b.segs[1:]:
-            c = rng.uniform(-0.05, 0.05, 3)
-            d = rng.uniform(0.002, 0.02, 3)
-            o = rng.uniform(-0.001, 0.001, 3)
-            g.inertia = pb.Inertia(float(rng.uniform(0.3, 2.5)), tuple(c), (d[0], d[1], d[2], o[0], o[1], o[2]))
+        _inertias(b, rng)
     p = _problem(b, start, goal, lim, True, K, Kr, waypoints, shape, overrides)
     if terms:
         p.torque_root, p.torque_tip = "base", "tip"
@@ -226,13 +248,48 @@ def hand9(K=12, Kr=5, waypoints=40, shape=None, **overrides):
                     overrides)
 
 
-def _fork(J, seed, alt, nested, K, Kr, waypoints, shape, overrides):
+def random_constraint(rng, link, header_frame, tolerances, weight=1.0):
+    """An orientation constraint with a random (non-identity) nominal orientation."""
+    q = rng.standard_normal(4)
+    q = q / np.linalg.norm(q)
+    return pb.OrientationConstraint(link, tuple(float(v) for v in q), header_frame=header_frame,
+                                    absolute_roll_tolerance=tolerances[0], absolute_pitch_tolerance=tolerances[1],
+                                    absolute_yaw_tolerance=tolerances[2], weight=weight)
+
+
+def hand9_constraints():
+    """hand9's fingers split the joints, so it can carry no torque chain: orientation constraints
+    only, on the last link of each finger (one header-frame, one body-fixed)."""
+    rng = np.random.default_rng(1109)
+    return [random_constraint(rng, "a2", True, (0.5, 0.4, 10.0)),
+            random_constraint(rng, "b2", False, (0.3, 10.0, 0.6), weight=1.5)]
+
+
+def fork12_constraints():
+    """Three constraints: on prong_a (another branch than the torque tip prong_b), on the palm (on
+    the torque chain, below every joint) and on a mid-arm link (a path shorter than the chain)."""
+    rng = np.random.default_rng(1112)
+    return [random_constraint(rng, "prong_a", True, (0.5, 0.4, 10.0)),
+            random_constraint(rng, "palm", False, (10.0, 0.4, 0.6), weight=2.0),
+            random_constraint(rng, "l5", True, (0.3, 10.0, 0.6), weight=0.5)]
+
+
+def _fork(J, seed, alt, nested, K, Kr, waypoints, shape, overrides, terms=False, root="base"):
     """A serial chain of J joints, then a fixed palm that forks into two fixed prongs (nested: the
     first prong forks again): every save comes after the last joint."""
     b = _Builder(seed, J)
     rng = b.rng
     length = 0.9 / J
-    arm = b.chain(0, 0, J, length)
+    if terms:
+        # a fixed pedestal under joint 0; with root = "base" also a fixed brace in mid-arm
+        ped = b.fixed("pedestal", 0, 0.04)
+        if root == "base":
+            arm = b.chain(ped, 0, J // 2, length)
+            arm += b.chain(b.fixed("brace", arm[-1], 0.03), J // 2, J - J // 2, length)
+        else:
+            arm = b.chain(ped, 0, J, length)
+    else:
+        arm = b.chain(0, 0, J, length)
     every = 1 if J <= 13 else 2
     for i, s in enumerate(arm):
         if i % every == 0 and i + 1 < len(arm):
@@ -248,12 +305,21 @@ def _fork(J, seed, alt, nested, K, Kr, waypoints, shape, overrides):
     pb_ = b.fixed("prong_b", palm, 0.05, rotated=False)
     b.balls(pb_, _dir(rng, 0.05), 2, radius=(0.02, 0.035))
     start, goal = _start_goal(rng, J, 0.8)
-    return _problem(b, start, goal, _limits(rng, start, goal, unlimited=tuple(range(2, J, 3))), alt, K, Kr, waypoints,
-                    shape, overrides)
+    lim = _limits(rng, start, goal, unlimited=tuple(range(2, J, 3)))
+    if terms:
+        _inertias(b, rng)
+    p = _problem(b, start, goal, lim, alt, K, Kr, waypoints, shape, overrides)
+    if terms:
+        p.torque_root, p.torque_tip = root, "prong_b"
+    return p
 
 
-def fork12(K=12, Kr=5, waypoints=40, shape=None, **overrides):
-    return _fork(12, 112, True, False, K, Kr, waypoints, shape, overrides)
+def fork12(K=12, Kr=5, waypoints=40, shape=None, terms=False, root="base", **overrides):
+    """terms=True: inertias, a fixed pedestal between the base and joint 0, and the torque chain up
+    to prong_b (a fixed tail of two segments: palm, prong_b).  root="base": the chain starts with
+    the fixed pedestal and holds a fixed brace between joints 5 and 6 (16 segments);
+    root="pedestal": a torque root that is not the tree's, no brace (14 segments)."""
+    return _fork(12, 112, True, False, K, Kr, waypoints, shape, overrides, terms=terms, root=root)
 
 
 def fork13(K=12, Kr=5, waypoints=40, shape=None, **overrides):
@@ -264,7 +330,7 @@ def fork24(K=12, Kr=5, waypoints=40, shape=None, **overrides):
     return _fork(24, 124, False, True, K, Kr, waypoints, shape, overrides)
 
 
-def _serial(J, seed, alt, K, Kr, waypoints, shape, overrides):
+def _serial(J, seed, alt, K, Kr, waypoints, shape, overrides, terms=False):
     b = _Builder(seed, J)
     rng = b.rng
     arm = b.chain(0, 0, J, 0.9 / J)
@@ -273,12 +339,18 @@ def _serial(J, seed, alt, K, Kr, waypoints, shape, overrides):
             nxt = b.segs[arm[i + 1]].trans if i + 1 < len(arm) else _dir(rng, 0.05)
             b.balls(s, nxt, 2)
     start, goal = _start_goal(rng, J, 0.8)
-    return _problem(b, start, goal, _limits(rng, start, goal, unlimited=tuple(range(2, J, 3))), alt, K, Kr, waypoints,
-                    shape, overrides)
+    lim = _limits(rng, start, goal, unlimited=tuple(range(2, J, 3)))
+    if terms:
+        _inertias(b, rng)
+    p = _problem(b, start, goal, lim, alt, K, Kr, waypoints, shape, overrides)
+    if terms:
+        p.torque_root, p.torque_tip = "base", b.segs[arm[-1]].name
+    return p
 
 
-def chain17(K=12, Kr=5, waypoints=40, shape=None, **overrides):
-    return _serial(17, 117, True, K, Kr, waypoints, shape, overrides)
+def chain17(K=12, Kr=5, waypoints=40, shape=None, terms=False, **overrides):
+    """terms=True: inertias and the torque chain base -> l16: 17 segments, one per joint."""
+    return _serial(17, 117, True, K, Kr, waypoints, shape, overrides, terms=terms)
 
 
 def chain32(K=12, Kr=5, waypoints=40, shape=None, **overrides):
@@ -287,6 +359,33 @@ def chain32(K=12, Kr=5, waypoints=40, shape=None, **overrides):
 
 ZOO = dict(stick1=stick1, chain5=chain5, hand9=hand9, fork12=fork12, fork13=fork13, chain17=chain17, fork24=fork24,
            chain32=chain32)
+
+
+def _with_terms(builder, constraints, **fixed):
+    def make(torque=0.001, constrained=True, **kw):
+        p = builder(terms=True, torque_cost_weight=torque, **fixed, **kw)
+        p.orientation_constraints = list(constraints()) if constrained else []
+        return p
+    return make
+
+
+# the robots of the state-terms tests: name -> make(torque=0.001, constrained=True, **builder arguments)
+TERMS_ZOO = dict(
+    stick1_one=_with_terms(stick1, lambda: []),
+    stick1_pedestal=_with_terms(stick1, lambda: [random_constraint(np.random.default_rng(1101), "wand_tip", False,
+                                                                   (0.5, 0.4, 0.3))], pedestal=True),
+    chain5=_with_terms(chain5, lambda: [pb.upright_constraint("tip")]),
+    fork12_base=_with_terms(fork12, fork12_constraints, root="base"),
+    fork12_pedestal=_with_terms(fork12, fork12_constraints, root="pedestal"),
+    chain17=_with_terms(chain17, lambda: [random_constraint(np.random.default_rng(1117), "l9", True, (0.5, 10.0, 0.3))]))
+# (3 J + 6 nchain): k_terms' LDS is this many doubles per waypoint
+TERMS_LDS_ROWS = dict(stick1_one=9, stick1_pedestal=21, chain5=51, fork12_base=132, fork12_pedestal=120, chain17=153)
+
+
+def hand9_constrained(**kw):
+    p = hand9(**kw)
+    p.orientation_constraints = hand9_constraints()
+    return p
 
 
 def three_saves():
@@ -367,6 +466,88 @@ def _swing_sign(axis, rot_axis, arm_axis, side):
 
 
 FACES = [(a, s) for a in range(3) for s in (0, 1)]
+
+
+# ----------------------------------------------------------------- crafted constraint rows
+# Orientation constraints whose branches random joint rows never take: KDL GetQuaternion's three
+# single-precision branches need a trace <= 1e-12 (exact half turns have -1), bullet getRPY's gimbal
+# branch needs |E[6]| >= 1 (an exact quarter turn of pitch).  The robot below has unit joint axes and
+# identity joint frames, so at q = 0 every joint rotation is exactly the identity, and each fixed
+# probe link below the last joint has a rotation of entries 0 / +-1: its frame is that matrix exactly.
+EXACT = dict(ident=(1, 0, 0, 0, 1, 0, 0, 0, 1),
+             x180=(1, 0, 0, 0, -1, 0, 0, 0, -1), y180=(-1, 0, 0, 0, 1, 0, 0, 0, -1), z180=(-1, 0, 0, 0, -1, 0, 0, 0, 1),
+             pitch_up=(0, 0, 1, 0, 1, 0, -1, 0, 0),        # Ry(+90 deg): R[6] = -1
+             pitch_down=(0, 0, -1, 0, 1, 0, 1, 0, 0),      # Ry(-90 deg): R[6] = +1
+             yaw_pitch_up=(0, -1, 0, 0, 0, 1, -1, 0, 0),   # Rz(+90) Ry(+90)
+             yaw_pitch_down=(0, -1, 0, 0, 0, -1, 1, 0, 0))  # Rz(+90) Ry(-90)
+# exact unit quaternions (x, y, z, w) of half turns: bullet's setRotation gives their matrices exactly
+Q_IDENT, Q_X180, Q_Y180, Q_Z180 = (0.0, 0.0, 0.0, 1.0), (1.0, 0.0, 0.0, 0.0), (0.0, 1.0, 0.0, 0.0), (0.0, 0.0, 1.0, 0.0)
+CRAFTED_T = (0, 7, 38)      # waypoints where every crafted row has all joints exactly 0
+NEAR_T = (3, 20)            # waypoints a nanoradian off zero: either side of the gimbal threshold
+PI_TOL = 3.2                # a tolerance >= pi: the evaluator zeroes that angle's weight
+
+
+def _oc(probe, nominal, body_fixed, tol, weight=1.0):
+    return pb.OrientationConstraint("p_" + probe, nominal, header_frame=not body_fixed, absolute_roll_tolerance=tol[0],
+                                    absolute_pitch_tolerance=tol[1], absolute_yaw_tolerance=tol[2], weight=weight)
+
+
+# case -> constraints (probe link, nominal orientation, body_fixed, (roll, pitch, yaw) tolerance)
+CRAFTED_CASES = dict(
+    half_turns_header=[_oc("ident", Q_IDENT, 0, (0.2, 0.2, PI_TOL)), _oc("x180", Q_IDENT, 0, (PI_TOL, 0.2, 0.3)),
+                       _oc("y180", Q_IDENT, 0, (0.2, PI_TOL, 0.3), 2.0), _oc("z180", Q_IDENT, 0, (0.4, 0.2, 0.3))],
+    half_turns_body=[_oc("ident", Q_X180, 1, (0.2, 0.2, PI_TOL)), _oc("x180", Q_Y180, 1, (PI_TOL, 0.2, 0.3)),
+                     _oc("y180", Q_Z180, 1, (0.2, PI_TOL, 0.3), 0.5), _oc("z180", Q_IDENT, 1, (0.4, 0.2, 0.3))],
+    gimbal_header=[_oc("pitch_up", Q_IDENT, 0, (0.2, 2.0, 0.3)), _oc("pitch_down", Q_IDENT, 0, (0.2, PI_TOL, 0.3)),
+                   _oc("yaw_pitch_up", Q_Z180, 0, (0.2, 2.0, 0.3), 1.5)],
+    gimbal_body=[_oc("pitch_up", Q_IDENT, 1, (0.2, 2.0, 0.3)), _oc("pitch_down", Q_X180, 1, (0.2, PI_TOL, 0.3)),
+                 _oc("yaw_pitch_down", Q_IDENT, 1, (0.2, 2.0, PI_TOL), 1.5)],
+    satisfied=[_oc("z180", Q_Z180, 0, (0.2, 0.2, PI_TOL))])
+
+
+def crafted_problem(case, K=12, Kr=0):
+    """The crafted robot with the constraints of CRAFTED_CASES[case]; N = 39."""
+    segs = [pb.Segment("base", -1, -1, BASE_LONG),
+            pb.Segment("a0", 0, 0, (0.0, 0.0, 0.1), (0.0, 0.0, 1.0)),
+            pb.Segment("a1", 1, 1, (0.15, 0.0, 0.0), (0.0, 1.0, 0.0)),
+            pb.Segment("a2", 2, 2, (0.15, 0.0, 0.0), (1.0, 0.0, 0.0))]
+    for name, R in EXACT.items():
+        segs.append(pb.Segment("p_" + name, 3, -1, (0.05, 0.0, 0.0), rot=tuple(float(v) for v in R)))
+    spheres = [pb.Sphere(i, 0.04 + 0.005 * i, 0.05, (0.07, 0.0, 0.0), segs[i].name) for i in (1, 2, 3)]
+    robot = pb.Robot(segs, [pb.Joint(f"j{j}", False) for j in range(3)], [])
+    start, goal = np.zeros(3), np.array([0.4, -0.3, 0.5])
+    params = pb.StompParameters(trajectory_duration=40 * 0.05, num_rollouts=K, num_reused_rollouts=Kr)
+    boxes = _scene(robot, spheres, start, goal)
+    grid = _grid(spheres, None)
+    p = pb.Problem(robot, spheres, grid, boxes, [], params, start, goal, torque_root=None, torque_tip=None)
+    p.orientation_constraints = list(CRAFTED_CASES[case])
+    p.sdf = pb.build_sdf(grid, boxes, [])
+    return p
+
+
+def crafted_rows(problem, seed=21):
+    """Row 0: every joint 0 at every waypoint.  Rows 1-3: random walks of 0.05 rad per waypoint with
+    all joints exactly 0 at CRAFTED_T and within a few nanoradians of 0 at NEAR_T."""
+    rng = np.random.default_rng(seed)
+    rows = rng.standard_normal((4, problem.J, problem.N)).cumsum(axis=2) * 0.05
+    rows[0] = 0.0
+    for t in CRAFTED_T:
+        rows[:, :, t] = 0.0
+    for t in NEAR_T:
+        rows[1:, :, t] = rng.standard_normal((3, problem.J)) * 3e-9
+    return rows
+
+
+def crafted_census(problem, oracle, rows):
+    """What the oracle's own constraint arithmetic takes on the rows (Oracle.orientation_probe): a
+    list of (constraint, body_fixed, quaternion branch, gimbal state, at an exact waypoint)."""
+    out = []
+    for r in rows:
+        for t in range(problem.N):
+            for c, oc in enumerate(problem.orientation_constraints):
+                branch, gimbal, _ = oracle.orientation_probe(r[:, t], c)
+                out.append((c, 0 if oc.header_frame else 1, branch, gimbal, not r[:, t].any()))
+    return out
 
 
 # ----------------------------------------------------------------- census (numpy only)
