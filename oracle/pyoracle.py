@@ -93,6 +93,11 @@ def lib():
         l.so_execute.argtypes = [P, dp, dp, C.POINTER(C.c_int), dp, C.c_int, C.POINTER(C.c_int)]
         l.so_iterate.argtypes = [P, C.c_int, C.POINTER(so_iter_out)]
         l.so_optimize.argtypes = [P, C.POINTER(so_stats), dp]
+        l.so_pi_get_rollouts.argtypes = [P, C.c_int, dp]
+        l.so_pi_set_rollout_costs.argtypes = [P, dp, C.c_double, dp]
+        l.so_pi_improve_policy.argtypes = [P, dp]
+        l.so_pi_add_extra_rollout.argtypes = [P, dp, dp]
+        l.so_pi_reset.argtypes = [P]
         l.so_get_best_trajectory.argtypes = [P, dp]
         l.so_get_best_torques.argtypes = [P, dp]
         l.so_get_last_trajectory.argtypes = [P, dp]
@@ -311,6 +316,44 @@ class Oracle:
         lib().so_iterate(self.h, iteration_number, C.byref(o))
         self.last_constraints_satisfied = bool(o.constraints_satisfied)
         return o.cost, bool(o.collision_free)
+
+    # ---------------------------------------------------- PolicyImprovement's steps (so_pi_*)
+    def pi_get_rollouts(self, iteration: int, noise_stddev) -> np.ndarray:
+        """getRollouts: the K_gen generated parameter rows (K_gen x J x N)."""
+        sig = np.ascontiguousarray(noise_stddev, np.float64)
+        if sig.shape != (self.J,):
+            raise ValueError(f"noise_stddev has shape {sig.shape}, the problem has {self.J} joints")
+        n = lib().so_pi_get_rollouts(self.h, iteration, _dp(sig))
+        if n < 0:
+            raise RuntimeError(lib().so_last_error().decode())
+        return self.rollouts("params")[:n]
+
+    def pi_set_rollout_costs(self, costs, control_cost_weight: float) -> np.ndarray:
+        """setRolloutCosts: costs are the generated rows' state costs (at least K_gen x N, finite);
+        returns the K totals."""
+        c = np.zeros((self.K, self.N))
+        cc = np.asarray(costs, np.float64).reshape(-1, self.N)
+        c[: cc.shape[0]] = cc
+        if not np.isfinite(c).all():
+            raise ValueError("costs must be finite (outside the reference's contract otherwise)")
+        totals = np.zeros(self.K)
+        lib().so_pi_set_rollout_costs(self.h, _dp(c), float(control_cost_weight), _dp(totals))
+        return totals
+
+    def pi_improve_policy(self) -> np.ndarray:
+        out = np.zeros((self.J, self.N))
+        lib().so_pi_improve_policy(self.h, _dp(out))
+        return out
+
+    def pi_add_extra_rollout(self, params, costs):
+        p = np.ascontiguousarray(params, np.float64)
+        c = np.ascontiguousarray(costs, np.float64)
+        if p.shape != (self.J, self.N) or c.shape != (self.N,) or not np.isfinite(c).all():
+            raise ValueError("one extra rollout: params J x N, finite costs N")
+        lib().so_pi_add_extra_rollout(self.h, _dp(p), _dp(c))
+
+    def pi_reset(self):
+        lib().so_pi_reset(self.h)
 
     def optimize(self):
         st = so_stats()

@@ -74,6 +74,8 @@ struct so_problem {
     double *x_params, *x_noise, *x_nproj, *x_ctrl, *x_state;   /* the one extra rollout */
     double *tmp_params, *tmp_noise, *tmp_nproj, *tmp_ctrl, *tmp_prob, *tmp_state; /* reused_rollouts_ */
     int reused_next, extra_added, K_gen;
+    double pi_weight;      /* control_cost_weight_ of the last setRolloutCosts */
+    double* pi_update;     /* J x N, parameter_updates_ of the last improvePolicy */
     /* the reuse decisions of every ranking so far: Kr candidate indices each (-1 = the extra
      * rollout), in the order generateRollouts kept them (policy_improvement.cpp:198-224) */
     int *rank_log, rank_n, rank_cap;
@@ -745,6 +747,7 @@ void so_destroy(so_problem* P)
     free(P->Rall); free(P->Rinv); free(P->L); free(P->M); free(P->Qinv); free(P->theta); free(P->pad_pos);
     free(P->r_params); free(P->r_noise); free(P->r_nproj); free(P->r_ctrl); free(P->r_prob); free(P->r_state);
     free(P->x_params); free(P->x_noise); free(P->x_nproj); free(P->x_ctrl); free(P->x_state);
+    free(P->pi_update);
     free(P->tmp_params); free(P->tmp_noise); free(P->tmp_nproj); free(P->tmp_ctrl); free(P->tmp_prob);
     free(P->tmp_state);
     free(P->last_traj); free(P->best_traj);
@@ -1017,6 +1020,8 @@ so_problem* so_create(const so_config* cfg)
     P->tmp_ctrl = dalloc(RJN); P->tmp_prob = dalloc(RJN); P->tmp_state = dalloc((size_t)(P->Kr ? P->Kr : 1) * N);
     P->x_params = dalloc((size_t)J * N); P->x_noise = dalloc((size_t)J * N); P->x_nproj = dalloc((size_t)J * N);
     P->x_ctrl = dalloc((size_t)J * N); P->x_state = dalloc((size_t)N);
+    P->pi_update = dalloc((size_t)J * N);
+    P->pi_weight = cfg->smoothness_cost_weight;
     P->last_traj = dalloc((size_t)J * N);
     P->best_traj = dalloc((size_t)J * N);
     memcpy(P->last_traj, P->theta, sizeof(double) * (size_t)J * N);
@@ -1455,27 +1460,155 @@ static double blocked_sum(const double* vals, size_t stride, int K, int B)
     return total;
 }
 
+/* ---- PolicyImprovement step by step (policy_improvement.h:86-126).  so_iterate below is the
+ * composition of these five, so the golden files of the iteration pin every one of them. */
+
+static void projected_noise(const so_problem* P, const double* noise, double* nproj)
+{
+    for (int d = 0; d < P->J; ++d)
+        noise_product(P, P->M, P->N, noise + (size_t)d * P->N, nproj + (size_t)d * P->N, 0);
+}
+
+/* PolicyImprovement::getRollouts (policy_improvement.cpp:241-260): generateRollouts(noise_stddev),
+ * then computeProjectedNoise of all K rows (:283-290, 473-482).  The generated parameter rows are
+ * "params" rows 0 .. K_gen - 1 of so_get_rollouts. */
+int so_pi_get_rollouts(so_problem* P, int iteration_number, const double* sigma)
+{
+    if (!sigma) { set_err("null noise_stddev"); return -1; }
+    const int K = P->K;
+    const size_t JN = (size_t)P->J * P->N;
+    generate_rollouts(P, iteration_number, sigma);
+    int nthreads = P->cfg.threads > 0 ? P->cfg.threads : 1;
+    (void)nthreads;
+    /* rows independent */
+#ifdef _OPENMP
+#pragma omp parallel for num_threads(nthreads) schedule(static)
+#endif
+    for (int r = 0; r < K; ++r) projected_noise(P, P->r_noise + r * JN, P->r_nproj + r * JN);
+    return P->K_gen;
+}
+
+/* PolicyImprovement::setRolloutCosts (policy_improvement.cpp:262-281): the weight is kept
+ * (control_cost_weight_, :266), computeRolloutControlCosts of all K rows with half of it (:292-299,
+ * 484-489), the state rows of the generated rollouts (:269-272; costs NULL: already in place, the
+ * composition's own execute wrote them), Rollout::getCost of every row (:275-279, 149-156). */
+int so_pi_set_rollout_costs(so_problem* P, const double* costs, double control_cost_weight, double* totals)
+{
+    const int K = P->K, N = P->N, Nall = P->Nall;
+    const size_t JN = (size_t)P->J * N;
+    P->pi_weight = control_cost_weight;
+    int nthreads = P->cfg.threads > 0 ? P->cfg.threads : 1;
+    (void)nthreads;
+#ifdef _OPENMP
+#pragma omp parallel num_threads(nthreads)
+#endif
+    {
+        double* xall = dalloc((size_t)Nall);
+        double* call = dalloc((size_t)Nall);
+        double w = 0.5 * control_cost_weight;
+#ifdef _OPENMP
+#pragma omp for schedule(static)
+#endif
+        for (int r = 0; r < K; ++r) control_costs(P, P->r_params + r * JN, P->r_nproj + r * JN, w, P->r_ctrl + r * JN, xall, call);
+        free(xall);
+        free(call);
+    }
+    if (costs) memcpy(P->r_state, costs, sizeof(double) * (size_t)P->K_gen * N);
+    if (totals)
+        for (int r = 0; r < K; ++r) totals[r] = rollout_cost(P, P->r_state + (size_t)r * N, P->r_ctrl + r * JN);
+    return 0;
+}
+
+/* PolicyImprovement::improvePolicy (policy_improvement.cpp:385-401): cumulative costs (:301-320),
+ * probabilities (:322-368), parameter updates M * sum_r eps_r P_r (:370-383).  The policy's
+ * parameters are left alone: the caller adds the update (updateParameters). */
+int so_pi_improve_policy(so_problem* P, double* updates)
+{
+    const int J = P->J, N = P->N, K = P->K;
+    const size_t JN = (size_t)J * N;
+    double* cum = dalloc((size_t)K * JN);   /* [K][J][N] cumulative costs */
+    for (int r = 0; r < K; ++r)
+        for (int d = 0; d < J; ++d) {
+            double* c = cum + r * JN + (size_t)d * N;
+            for (int t = 0; t < N; ++t) c[t] = P->r_state[(size_t)r * N + t] + P->r_ctrl[r * JN + (size_t)d * N + t];
+            if (P->cfg.use_cumulative_costs)
+                for (int t = N - 2; t >= 0; --t) c[t] += c[t + 1];
+        }
+    double* upd = dalloc((size_t)N);
+    double* tmp = dalloc((size_t)K);
+    for (int d = 0; d < J; ++d) {
+        for (int t = 0; t < N; ++t) {
+            size_t off = (size_t)d * N + t;
+            double mn = cum[off], mx = mn;
+            for (int r = 1; r < K; ++r) {
+                double c = cum[r * JN + off];
+                if (c < mn) mn = c;
+                if (c > mx) mx = c;
+            }
+            double denom = mx - mn;
+            if (denom < 1e-8) denom = 1e-8;
+            for (int r = 0; r < K; ++r)
+                P->r_prob[r * JN + off] = P->cfg.ref_arith >= 3 ? exp(-10.0 * (cum[r * JN + off] - mn) / denom)
+                                                                : dm_exp(-10.0 * (cum[r * JN + off] - mn) / denom);
+            double psum = blocked_sum(P->r_prob + off, JN, K, P->B);
+            for (int r = 0; r < K; ++r) P->r_prob[r * JN + off] /= psum;
+            /* computeParameterUpdates (policy_improvement.cpp:370-383) */
+            for (int r = 0; r < K; ++r) tmp[r] = P->r_noise[r * JN + off] * P->r_prob[r * JN + off];
+            upd[t] = blocked_sum(tmp, 1, K, P->B);
+        }
+        matvec(P->M, N, upd, P->pi_update + (size_t)d * N, 0);
+    }
+    free(cum); free(upd); free(tmp);
+    if (updates) memcpy(updates, P->pi_update, JN * 8);
+    return 0;
+}
+
+/* PolicyImprovement::addExtraRollouts (policy_improvement.cpp:443-462) with its one extra
+ * rollout: noise against the policy's current parameters (:448, 464-469), projected noise, control
+ * costs under the weight the last setRolloutCosts kept (:484-489 reads control_cost_weight_). */
+int so_pi_add_extra_rollout(so_problem* P, const double* params, const double* costs)
+{
+    if (!params || !costs) { set_err("null argument"); return -1; }
+    const int N = P->N, Nall = P->Nall;
+    const size_t JN = (size_t)P->J * N;
+    memmove(P->x_params, params, JN * 8);
+    memmove(P->x_state, costs, (size_t)N * 8);
+    for (size_t k = 0; k < JN; ++k) P->x_noise[k] = P->x_params[k] - P->theta[k];
+    projected_noise(P, P->x_noise, P->x_nproj);
+    double* xall = dalloc((size_t)Nall);
+    double* call = dalloc((size_t)Nall);
+    control_costs(P, P->x_params, P->x_nproj, 0.5 * P->pi_weight, P->x_ctrl, xall, call);
+    free(xall);
+    free(call);
+    P->extra_added = 1;
+    return 0;
+}
+
+/* PolicyImprovement::setNumRollouts with the same counts (policy_improvement.cpp:139-143):
+ * rollouts_reused_next_ and extra_rollouts_added_ cleared, the rollouts themselves kept */
+int so_pi_reset(so_problem* P)
+{
+    P->reused_next = 0;
+    P->extra_added = 0;
+    return 0;
+}
+
+/* PolicyImprovementLoop::runSingleIteration (policy_improvement_loop.cpp:143-202) */
 int so_iterate(so_problem* P, int iteration_number, so_iter_out* out)
 {
-    const int J = P->J, N = P->N, K = P->K, Nall = P->Nall;
+    const int J = P->J, N = P->N;
     size_t JN = (size_t)J * N;
     int iteration_member = iteration_number - 1;
     /* noise schedule (policy_improvement_loop.cpp:155-160) */
     double* sigma = dalloc((size_t)J);
     for (int d = 0; d < J; ++d) sigma[d] = P->cfg.noise_stddev[d] * pow(P->cfg.noise_decay[d], iteration_number - 1);
-    generate_rollouts(P, iteration_number, sigma);
+    so_pi_get_rollouts(P, iteration_number, sigma);
     free(sigma);
     int nthreads = P->cfg.threads > 0 ? P->cfg.threads : 1;
     (void)nthreads;
-    /* computeProjectedNoise for all K (policy_improvement.cpp:283-290, 473-482); rows independent */
-#ifdef _OPENMP
-#pragma omp parallel for num_threads(nthreads) schedule(static)
-#endif
-    for (int r = 0; r < K; ++r)
-        for (int d = 0; d < J; ++d)
-            noise_product(P, P->M, N, P->r_noise + r * JN + (size_t)d * N, P->r_nproj + r * JN + (size_t)d * N, 0);
 
-    /* Task::execute for each generated rollout (policy_improvement_loop.cpp:165-170) */
+    /* Task::execute for each generated rollout (policy_improvement_loop.cpp:165-170), straight
+     * into the rollouts' state rows */
 #ifdef _OPENMP
 #pragma omp parallel num_threads(nthreads)
 #endif
@@ -1492,79 +1625,21 @@ int so_iterate(so_problem* P, int iteration_number, so_iter_out* out)
         scratch_free(&sc);
     }
 
-    /* setRolloutCosts -> computeRolloutControlCosts for all K (policy_improvement.cpp:262-281) */
-#ifdef _OPENMP
-#pragma omp parallel num_threads(nthreads)
-#endif
-    {
-        double* xall = dalloc((size_t)Nall);
-        double* call = dalloc((size_t)Nall);
-        double w = 0.5 * P->cfg.smoothness_cost_weight;
-#ifdef _OPENMP
-#pragma omp for schedule(static)
-#endif
-        for (int r = 0; r < K; ++r) control_costs(P, P->r_params + r * JN, P->r_nproj + r * JN, w, P->r_ctrl + r * JN, xall, call);
-        free(xall);
-        free(call);
-    }
+    /* setRolloutCosts with the loop's weight (policy_improvement_loop.cpp:173) */
+    so_pi_set_rollout_costs(P, NULL, P->cfg.smoothness_cost_weight, NULL);
 
-    /* improvePolicy (policy_improvement.cpp:385-401) */
-    {
-        double* cum = dalloc((size_t)K * JN);   /* [K][J][N] cumulative costs */
-        for (int r = 0; r < K; ++r)
-            for (int d = 0; d < J; ++d) {
-                double* c = cum + r * JN + (size_t)d * N;
-                for (int t = 0; t < N; ++t) c[t] = P->r_state[(size_t)r * N + t] + P->r_ctrl[r * JN + (size_t)d * N + t];
-                if (P->cfg.use_cumulative_costs)
-                    for (int t = N - 2; t >= 0; --t) c[t] += c[t + 1];
-            }
-        double* upd = dalloc((size_t)N);
-        double* del = dalloc((size_t)N);
-        double* tmp = dalloc((size_t)K);
-        for (int d = 0; d < J; ++d) {
-            for (int t = 0; t < N; ++t) {
-                size_t off = (size_t)d * N + t;
-                double mn = cum[off], mx = mn;
-                for (int r = 1; r < K; ++r) {
-                    double c = cum[r * JN + off];
-                    if (c < mn) mn = c;
-                    if (c > mx) mx = c;
-                }
-                double denom = mx - mn;
-                if (denom < 1e-8) denom = 1e-8;
-                for (int r = 0; r < K; ++r)
-                    P->r_prob[r * JN + off] = P->cfg.ref_arith >= 3 ? exp(-10.0 * (cum[r * JN + off] - mn) / denom)
-                                                                    : dm_exp(-10.0 * (cum[r * JN + off] - mn) / denom);
-                double psum = blocked_sum(P->r_prob + off, JN, K, P->B);
-                for (int r = 0; r < K; ++r) P->r_prob[r * JN + off] /= psum;
-                /* computeParameterUpdates (policy_improvement.cpp:370-383) */
-                for (int r = 0; r < K; ++r) tmp[r] = P->r_noise[r * JN + off] * P->r_prob[r * JN + off];
-                upd[t] = blocked_sum(tmp, 1, K, P->B);
-            }
-            matvec(P->M, N, upd, del, 0);
-            /* updateParameters (covariant_trajectory_policy.cpp:306-342) */
-            for (int t = 0; t < N; ++t) P->theta[(size_t)d * N + t] += 1.0 * del[t];
-        }
-        free(cum); free(upd); free(del); free(tmp);
-    }
+    /* improvePolicy, then updateParameters (covariant_trajectory_policy.cpp:306-342) */
+    so_pi_improve_policy(P, NULL);
+    for (size_t k = 0; k < JN; ++k) P->theta[k] += 1.0 * P->pi_update[k];
 
-    /* noiseless rollout (policy_improvement_loop.cpp:180-192) */
+    /* noiseless rollout (policy_improvement_loop.cpp:180-192), then addExtraRollouts with it */
     {
         exec_scratch sc;
         scratch_init(P, &sc);
         execute_one(P, &sc, P->theta, P->x_state, &P->last_cf, P->last_traj, iteration_member, &P->last_cost,
                     &P->last_cs);
         scratch_free(&sc);
-        /* addExtraRollouts (policy_improvement.cpp:443-462) */
-        memcpy(P->x_params, P->theta, JN * 8);
-        for (size_t k = 0; k < JN; ++k) P->x_noise[k] = P->x_params[k] - P->theta[k];
-        for (int d = 0; d < J; ++d) noise_product(P, P->M, N, P->x_noise + (size_t)d * N, P->x_nproj + (size_t)d * N, 0);
-        double* xall = dalloc((size_t)Nall);
-        double* call = dalloc((size_t)Nall);
-        control_costs(P, P->x_params, P->x_nproj, 0.5 * P->cfg.smoothness_cost_weight, P->x_ctrl, xall, call);
-        free(xall);
-        free(call);
-        P->extra_added = 1;
+        so_pi_add_extra_rollout(P, P->theta, P->x_state);
     }
     if (out) {
         out->cost = P->last_cost;

@@ -12,6 +12,7 @@
  *
  * Structure follows the reference one-to-one:
  *   so_iterate            PolicyImprovementLoop::runSingleIteration  policy_improvement_loop.cpp:143-202
+ *   so_pi_*               PolicyImprovement's five steps             policy_improvement.cpp:139-462
  *   so_execute            StompOptimizer::execute                    stomp_optimizer.cpp:1063-1165
  *   so_optimize           StompOptimizer::optimize                   stomp_optimizer.cpp:249-401
  * Build-defined choices that the reference leaves to third-party code
@@ -177,6 +178,24 @@ int so_execute(so_problem* p, const double* params, double* costs, int* collisio
 
 /* runSingleIteration(iteration_number); the optimizer's iteration_ is iteration_number-1 */
 int so_iterate(so_problem* p, int iteration_number, so_iter_out* out);
+
+/* PolicyImprovement step by step (policy_improvement.h:86-126), for callers that run their own
+ * Task::execute between the steps; so_iterate is their composition.  Costs must be finite: NaN and
+ * infinite totals are outside the reference's contract (std::sort of such pairs is undefined).
+ *   so_pi_get_rollouts        getRollouts (policy_improvement.cpp:241-260): generateRollouts with
+ *                             noise_stddev (J), projected noise of all K rows; returns K_gen, the
+ *                             generated rows are rows 0 .. K_gen - 1 of "params"
+ *   so_pi_set_rollout_costs   setRolloutCosts (:262-281): costs K_gen x N, totals K (may be NULL);
+ *                             the weight is kept as control_cost_weight_ is
+ *   so_pi_improve_policy      improvePolicy (:385-401): updates J x N (may be NULL), theta untouched
+ *   so_pi_add_extra_rollout   addExtraRollouts (:443-462) with one rollout: noise = params - theta,
+ *                             priced under the kept weight
+ *   so_pi_reset               setNumRollouts with the same counts (:139-143) */
+int so_pi_get_rollouts(so_problem* p, int iteration_number, const double* noise_stddev);
+int so_pi_set_rollout_costs(so_problem* p, const double* costs, double control_cost_weight, double* totals);
+int so_pi_improve_policy(so_problem* p, double* updates);
+int so_pi_add_extra_rollout(so_problem* p, const double* params, const double* costs);
+int so_pi_reset(so_problem* p);
 
 /* StompOptimizer::optimize loop (without the final torque statistics) */
 int so_optimize(so_problem* p, so_stats* stats, double* costs_per_iteration /* may be NULL */);

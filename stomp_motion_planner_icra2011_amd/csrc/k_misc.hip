@@ -4,6 +4,8 @@
 #include "stamps.h"
 
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
 
 #include <map>
 #include <mutex>
@@ -308,6 +310,9 @@ int launch_reuse(int K, int J, int N, int Kr, int K_gen, int with_extra, const d
     const size_t lds = std::max((size_t)P * sizeof(double), rank_bytes);
     if (lds > kReuseLds) return -2;
     if (lds > 48 * 1024) lds_opt_in((const void*)k_reuse, lds);
+    if (getenv("STOMP_DEBUG_LEAN_PRINT"))   // read-only: tests and tables
+        fprintf(stderr, "stomp: reuse n %d Kr %d K_gen %d costs_only %d, k_reuse<%d>, LDS %zu B, opt-in %d\n", n, Kr,
+                K_gen, costs_only ? 1 : 0, kReuseBlock, lds, lds > 48 * 1024 ? 1 : 0);
     hipLaunchKernelGGL(k_reuse, dim3(n), dim3(kReuseBlock), lds, s, K, J, N, Kr, K_gen, with_extra, src_params,
                        src_state, src_control, params, noise, state, x_params, x_state, x_control, theta, costs_g,
                        count, stop, costs_only ? 1 : 0);

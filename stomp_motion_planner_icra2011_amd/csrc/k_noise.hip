@@ -20,6 +20,10 @@
 #include "noise_device.h"
 #include "stamps.h"
 
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+
 namespace stomp {
 
 template <int BLOCK, int RT>
@@ -532,6 +536,9 @@ template <int BLOCK, int NG, bool REUSE>
 void launch_noise_rows_t(const NoiseArgs& a, const ReuseArgs& ra, int rows, size_t lds, hipStream_t s)
 {
     if (lds > 64 * 1024) lds_opt_in((const void*)k_noise_rows<BLOCK, NG, REUSE>, lds);
+    if (!REUSE && getenv("STOMP_DEBUG_LEAN_PRINT"))   // launch_noise's choice (read-only: tests and tables)
+        fprintf(stderr, "stomp: noise J %d N %d rows %d gen 0, k_noise_rows<%d,%d,false>, LDS %zu B, opt-in %d\n", a.J,
+                a.N, rows, BLOCK, NG, lds, lds > 64 * 1024 ? 1 : 0);
     hipLaunchKernelGGL((k_noise_rows<BLOCK, NG, REUSE>), dim3(rows), dim3(BLOCK), lds, s, a, ra);
 }
 
@@ -629,6 +636,11 @@ void launch_noise(const NoiseArgs& a, hipStream_t s)
     const int rt = rows >= NOISE_RT ? NOISE_RT : 1;
     const size_t lds = (size_t)rt * (2 * (a.N + kBandBatch) + 2 * a.Nall) * sizeof(double);
     dim3 grid((rows + rt - 1) / rt, a.J);
+    if (getenv("STOMP_DEBUG_LEAN_PRINT")) {   // the choice taken here (read-only: tests and tables)
+        const int gen = a.zero_noise ? 0 : std::min(std::max(a.K_gen_global - (a.first_global + a.row_begin), 0), rows);
+        fprintf(stderr, "stomp: noise J %d N %d rows %d gen %d, k_noise<%d,%d>, LDS %zu B, opt-in 0\n", a.J, a.N, rows,
+                gen, block, rt, lds);
+    }
     if (rt == NOISE_RT) {
         if (block == 128) hipLaunchKernelGGL((k_noise<128, NOISE_RT>), grid, dim3(128), lds, s, a);
         else hipLaunchKernelGGL((k_noise<256, NOISE_RT>), grid, dim3(256), lds, s, a);
