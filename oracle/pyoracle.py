@@ -297,6 +297,15 @@ class Oracle:
         t = np.ascontiguousarray(theta, np.float64)
         lib().so_set_theta(self.h, _dp(t))
 
+    def refresh_field(self, sdf: np.ndarray):
+        """The distance field rebuilt in place (the oracle reads the buffer it was created on at every
+        lookup): the twin of stomp_engine_refresh_field for an oracle that is already iterating.  A
+        problem.sdf that is that buffer (uint16, contiguous) changes with it."""
+        new = np.ascontiguousarray(sdf, dtype=np.uint16)
+        if new.shape != self._sdf.shape:
+            raise ValueError(f"the new field has shape {new.shape}, the oracle's is {self._sdf.shape}")
+        np.copyto(self._sdf, new)
+
     def pad_positions(self) -> np.ndarray:
         out = np.zeros((12, self.S, 3))
         lib().so_get_pad_positions(self.h, _dp(out))

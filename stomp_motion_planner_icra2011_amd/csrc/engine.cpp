@@ -618,9 +618,9 @@ int stomp_pi_get_rollouts(stomp_engine* e, int32_t iteration, const double* nois
                           int32_t* num_generated)
 {
     if (!e) return fail(nullptr, STOMP_E_INVALID, "null engine");
+    if (e->world > 1 || e->gather) return fail(e, STOMP_E_UNSUPPORTED, "the PolicyImprovement API is single-rank");
     DeviceGuard dg(e->device);
     materialize_rows(e);
-    if (e->world > 1 || e->gather) return fail(e, STOMP_E_UNSUPPORTED, "the PolicyImprovement API is single-rank");
     if (!noise_stddev) return fail(e, STOMP_E_INVALID, "null noise_stddev");
     flush_noiseless(e);
     if (int rc = begin_generate(e)) return rc;
@@ -646,6 +646,8 @@ int stomp_pi_get_rollouts(stomp_engine* e, int32_t iteration, const double* nois
 int stomp_pi_set_rollout_costs(stomp_engine* e, const double* costs, double control_cost_weight, double* totals)
 {
     if (!e || !costs) return fail(e, STOMP_E_INVALID, "null argument");
+    // before anything moves: a rank's row buffers hold K_loc rows, the copies below take K
+    if (e->world > 1 || e->gather) return fail(e, STOMP_E_UNSUPPORTED, "the PolicyImprovement API is single-rank");
     DeviceGuard dg(e->device);
     materialize_rows(e);
     const int K = e->K, J = e->J, N = e->N;
@@ -687,9 +689,9 @@ int stomp_pi_set_rollout_costs(stomp_engine* e, const double* costs, double cont
 int stomp_pi_improve_policy(stomp_engine* e, double* updates)
 {
     if (!e) return fail(nullptr, STOMP_E_INVALID, "null engine");
+    if (e->world > 1 || e->gather) return fail(e, STOMP_E_UNSUPPORTED, "the PolicyImprovement API is single-rank");
     DeviceGuard dg(e->device);
     materialize_rows(e);
-    if (e->world > 1 || e->gather) return fail(e, STOMP_E_UNSUPPORTED, "the PolicyImprovement API is single-rank");
     WeightArgs wa{};
     wa.stop = nullptr;
     wa.J = e->J; wa.N = e->N; wa.K_loc = e->K_loc; wa.use_cumulative = e->use_cum;
@@ -719,6 +721,8 @@ int stomp_pi_improve_policy(stomp_engine* e, double* updates)
 int stomp_pi_reset(stomp_engine* e)
 {
     if (!e) return fail(nullptr, STOMP_E_INVALID, "null engine");
+    // on a rank the two flags decide which collectives the next iteration posts
+    if (e->world > 1 || e->gather) return fail(e, STOMP_E_UNSUPPORTED, "the PolicyImprovement API is single-rank");
     DeviceGuard dg(e->device);
     SYNC_TRY(e);
     e->reused_next = false;
@@ -729,6 +733,7 @@ int stomp_pi_reset(stomp_engine* e)
 int stomp_pi_add_extra_rollouts(stomp_engine* e, int32_t num, const double* params, const double* costs)
 {
     if (!e || !params || !costs) return fail(e, STOMP_E_INVALID, "null argument");
+    if (e->world > 1 || e->gather) return fail(e, STOMP_E_UNSUPPORTED, "the PolicyImprovement API is single-rank");
     DeviceGuard dg(e->device);
     materialize_rows(e);
     if (num != 1) return fail(e, STOMP_E_INVALID, "one extra rollout (the loop's noiseless rollout)");

@@ -773,7 +773,10 @@ int finish_model(stomp_engine* e, const stomp_engine_desc* d)
     }
     if (getenv("STOMP_DEBUG_LEAN_PRINT")) {
         // what creation chose for this model, and the body launch_cost takes for an iteration's
-        // K_loc rollouts + the noiseless one beside the pregen blocks (read-only: tests and tables)
+        // K_loc rollouts + the noiseless one beside the pregen blocks (read-only: tests and tables).
+        // The weights kernel is that of the rows the launch covers now (gather: all K).  Where the
+        // decomposition is still to be measured (e->calibrate) that is gather's layout: if the
+        // calibration then picks partials, the phases run the K_loc-row kernel, not the one named here
         const int nro = e->K_loc + 1, extra = e->pre_on ? e->rows : 0;
         const int P = rollout_split_pieces(m, nro, extra, false);
         const char* body = P ? "split" : nro <= m.cus ? (m.phased_lds > 0 ? "phased" : "wide")
@@ -781,7 +784,7 @@ int finish_model(stomp_engine* e, const stomp_engine_desc* d)
         fprintf(stderr, "stomp: model J %d N %d S %d nseg %d nops %d nsaves %d sincos_pre %d sph_chunk %d lean %d "
                         "pregen %d fused_noise %d brick %d, launch of %d rollouts: %s, %d pieces, weights %s\n",
                 J, N, e->S, m.nseg, m.nops, m.nsaves, m.sincos_pre, m.sph_chunk, m.lean, e->pre_on ? 1 : 0,
-                J <= 16 ? 1 : 0, m.brick, nro, body, P, weights_kernel_name(e->K_loc, !e->split_modes, false));
+                J <= 16 ? 1 : 0, m.brick, nro, body, P, weights_kernel_name(e->rows, !e->split_modes, false));
     }
     return 0;
 }
