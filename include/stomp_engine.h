@@ -374,11 +374,35 @@ int stomp_diff_rules(double* out);
  * rows) and pending noiseless rollout; the engines' own calls keep working between group runs.
  * The engines enter a run at one iteration state (STOMP_E_INVALID with no engine touched
  * otherwise).  stomp_group_synchronize flushes every engine's pending noiseless rollout and
- * waits. */
+ * waits.
+ * stomp_group_create_with takes options; stomp_group_create(e, n, out) is exactly
+ * stomp_group_create_with(e, n, {state_terms 0, compact -1}, out).  With state_terms = 1 the group
+ * also accepts engines with state-cost terms (the torque term, torque_cost_weight > 1e-9, and / or
+ * orientation path constraints), at K_r = 0 and K_r > 0.  Such a group may be mixed: the engines
+ * share J, N, K, K_r, the spheres and the rollout layout as above, and each keeps its own terms
+ * model -- the torque term only, constraints only, both, or neither (for an engine with neither
+ * nothing changes: no terms launch writes any of its rows).  Every grouped rollout launch and every
+ * grouped noiseless flush is then followed by one more launch, the state-cost terms of all its
+ * engines, before anything reads the state costs, the noiseless rollout's total or its
+ * constraints-satisfied flag; stomp_group_run, stomp_group_synchronize and stomp_group_optimize
+ * keep their post-conditions (each engine bit for bit where its own calls leave it, the optimize
+ * loop's stop rule counting only iterations whose noiseless trajectory satisfies the constraints).
+ * Cumulative costs, more than 16 joints, sharded engines and the other conditions above stay
+ * STOMP_E_UNSUPPORTED with state_terms = 1; a refused creation leaves every engine untouched.
+ * compact: -1 leaves the choice to STOMP_DEBUG_GROUP_COMPACT as in stomp_group_create, 0 / 1
+ * turn the compaction of stomp_group_optimize off / on.  NULL options or a struct_size other than
+ * sizeof(stomp_group_options): STOMP_E_INVALID. */
 typedef struct stomp_group stomp_group;
+typedef struct stomp_group_options {
+    int32_t struct_size;   /* sizeof(stomp_group_options) */
+    int32_t state_terms;   /* 1: engines with the torque term and / or path constraints are accepted */
+    int32_t compact;       /* -1: STOMP_DEBUG_GROUP_COMPACT decides, as in stomp_group_create; 0 / 1: off / on */
+} stomp_group_options;
 int stomp_stream_create(int32_t device, void** out_stream);
 int stomp_stream_destroy(void* stream);
 int stomp_group_create(stomp_engine* const* engines, int32_t num_engines, stomp_group** out);
+int stomp_group_create_with(stomp_engine* const* engines, int32_t num_engines,
+                            const stomp_group_options* options, stomp_group** out);
 int stomp_group_run(stomp_group* g, int32_t first_iteration, int32_t count);
 int stomp_group_synchronize(stomp_group* g);
 /* StompOptimizer::optimize (stomp_optimizer.cpp:249-401) for every engine of the group at once.

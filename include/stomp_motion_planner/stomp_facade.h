@@ -420,7 +420,8 @@ public:
     bool optimize();
     // optimize() for several optimizers at once, for optimizers constructed on ONE shared stream
     // (and of one shape: stomp_group_create's rules; reused rollouts are fine when every optimizer
-    // has the same num_reused_rollouts): their engines run as a group
+    // has the same num_reused_rollouts, and so are optimizers with the torque term or orientation
+    // path constraints, each with its own: state_terms = 1): their engines run as a group
     // (stomp_group_optimize), each problem stopping on its own.  Every optimizer ends as after its
     // own optimize(): getStatistics() (torques included) filled, the best trajectory written back
     // into its trajectory.  On failure returns false with the reason in the first optimizer's

@@ -12,6 +12,12 @@
 // reusing iterations; the host keeps every engine's generateRollouts state (reused_next,
 // extra_added, the row-set swap) in step with the staged iterations and, after an optimize loop,
 // puts back the state of the iteration each engine stopped at.
+// A group created with state_terms (stomp_group_create_with) also takes engines with the torque
+// term and / or orientation path constraints: every grouped rollout launch and every grouped
+// noiseless flush is followed by one launch of the state-cost terms for all of its engines
+// (k_terms_group, each engine with its own TermsModel; an engine without terms has no workgroup
+// that writes), before anything reads the state costs, the noiseless total or the
+// constraints-satisfied flag.
 #include "engine_internal.h"
 
 #include <algorithm>
@@ -24,7 +30,12 @@ struct stomp_group {
     hipStream_t stream = nullptr;
     int nt = 0;                           // weights tiles per engine
     DevModel* d_models = nullptr;         // [P]
-    unsigned char* d_args = nullptr;      // [iterations][P] CostArgs, WeightArgs, UpdateArgs, (K_r > 0) ReuseRowArgs
+    bool state_terms = false;             // engines with terms accepted (stomp_group_create_with)
+    TermsModel* d_tmodels = nullptr;      // [P] every engine's terms model (state_terms)
+    int nterms = 0;                       // engines with terms
+    size_t terms_lds = 0;                 // the largest terms_lds_bytes among them: k_terms_group's dynamic LDS
+    unsigned char* d_args = nullptr;      // [iterations][P] CostArgs, WeightArgs, UpdateArgs, (K_r > 0) ReuseRowArgs,
+                                          // (engines with terms) TermsArgs
     size_t d_cap = 0;
     unsigned char* h_args = nullptr;      // pinned staging of one run's arguments
     size_t h_cap = 0;
@@ -94,6 +105,7 @@ StagedIteration stage_iteration(stomp_engine* e, int it, bool keep_in_pre, CostA
         ca.tot_rows = e->K;
         ca.tot_state = e->d_state_b; ca.tot_control = e->d_control_b; ca.tot_out = e->d_reuse_costs;
     }
+    if (e->terms_on) ca.traj_out = e->d_terms_traj;
     if (e->pending_member >= 0) {
         // with K_r > 0 it is also the extra rollout of this iteration's ranking (priced with ca.nz)
         set_noiseless(e, ca, e->pending_member, true, e->Kr > 0);
@@ -133,10 +145,26 @@ CostArgs noiseless_args(stomp_engine* e)
     CostArgs ca{};
     ca.stop = e->d_stop;
     ca.num_noisy = 0;
+    if (e->terms_on) ca.traj_out = e->d_terms_traj;
     set_noiseless(e, ca, e->pending_member, true, e->Kr > 0);
     if (e->Kr > 0) ca.nz = noise_args(e, e->pending_member + 1);
     e->pending_member = -1;
     return ca;
+}
+
+// the engine's entry of the grouped terms launch after a grouped rollout launch with its
+// arguments `ca` (launch_terms_for's arguments); an engine without terms gets an entry of no
+// rollouts: none of its rows is touched
+TermsArgs terms_args(const stomp_engine* e, const CostArgs& ca)
+{
+    TermsArgs ta{};
+    if (!e->terms_on) return ta;
+    ta.stop = e->d_stop;
+    ta.traj = ca.traj_out; ta.state = ca.state_out; ta.total = ca.total_out; ta.num_noisy = ca.num_noisy;
+    if (ca.x_params) {
+        ta.x_traj = ca.x_traj; ta.x_state = ca.x_state; ta.x_total = ca.x_total; ta.x_cs = e->d_cs;
+    }
+    return ta;
 }
 }  // namespace
 
@@ -151,6 +179,7 @@ void stomp_group_destroy(stomp_group* g)
         hipEventDestroy(g->staged);
     }
     if (g->d_models) hipFree(g->d_models);
+    if (g->d_tmodels) hipFree(g->d_tmodels);
     if (g->d_args) hipFree(g->d_args);
     if (g->h_args) hipHostFree(g->h_args);
     if (g->d_opt) hipFree(g->d_opt);
@@ -165,7 +194,17 @@ void stomp_group_destroy(stomp_group* g)
 
 int stomp_group_create(stomp_engine* const* engines, int32_t n, stomp_group** out)
 {
+    const stomp_group_options o = {(int32_t)sizeof(stomp_group_options), 0, -1};
+    return stomp_group_create_with(engines, n, &o, out);
+}
+
+int stomp_group_create_with(stomp_engine* const* engines, int32_t n, const stomp_group_options* options,
+                            stomp_group** out)
+{
     if (!engines || n <= 0 || !out) return gfail(nullptr, STOMP_E_INVALID, "invalid group arguments");
+    if (!options || options->struct_size != (int32_t)sizeof(stomp_group_options))
+        return gfail(nullptr, STOMP_E_INVALID, "invalid group options (null, or struct_size is not sizeof(stomp_group_options))");
+    const bool state_terms = options->state_terms != 0;
     stomp_engine* e0 = engines[0];
     if (!e0) return gfail(nullptr, STOMP_E_INVALID, "null engine");
     const size_t lds0 = rollout_lds_bytes(e0->model, e0->model.pad_lds);
@@ -178,10 +217,12 @@ int stomp_group_create(stomp_engine* const* engines, int32_t n, stomp_group** ou
             rollout_lds_bytes(e->model, e->model.pad_lds) != lds0 || e->model.brick != e0->model.brick)
             return gfail(nullptr, STOMP_E_INVALID,
                          "the engines of a group have one shape (J, N, K, K_r, spheres, model, field layout)");
-        if (e->world != 1 || !e->pre_on || e->terms_on || e->split_modes || e->gather || e->use_cum || e->J > 16)
+        if (e->world != 1 || !e->pre_on || (e->terms_on && !state_terms) || e->split_modes || e->gather ||
+            e->use_cum || e->J > 16)
             return gfail(nullptr, STOMP_E_UNSUPPORTED,
-                         "groups run single-device engines of at most 16 joints without state-cost terms or "
-                         "cumulative costs");
+                         state_terms ? "groups run single-device engines of at most 16 joints without cumulative costs"
+                                     : "groups run single-device engines of at most 16 joints without state-cost "
+                                       "terms or cumulative costs");
         if (e->Kr > 0) {
             // the reuse step is the reused rows' kernel (launch_reuse_rows_ok: K + 1 candidates
             // ranked by a workgroup, J <= 16, the row kernel's LDS)
@@ -202,7 +243,9 @@ int stomp_group_create(stomp_engine* const* engines, int32_t n, stomp_group** ou
     g->device = e0->device;
     g->stream = e0->stream;
     g->nt = nt;
-    if (const char* c = getenv("STOMP_DEBUG_GROUP_COMPACT")) g->compact = c[0] == '1';
+    if (options->compact >= 0) g->compact = options->compact != 0;
+    else if (const char* c = getenv("STOMP_DEBUG_GROUP_COMPACT")) g->compact = c[0] == '1';
+    g->state_terms = state_terms;
     std::vector<DevModel> ms(n);
     for (int p = 0; p < n; ++p) ms[p] = engines[p]->model;
     if (hipMalloc(&g->d_models, sizeof(DevModel) * n) != hipSuccess ||
@@ -211,10 +254,27 @@ int stomp_group_create(stomp_engine* const* engines, int32_t n, stomp_group** ou
         stomp_group_destroy(g);
         return gfail(nullptr, STOMP_E_DEVICE, "group allocation failed");
     }
+    if (state_terms) {
+        std::vector<TermsModel> ts(n);
+        for (int p = 0; p < n; ++p) {
+            ts[p] = engines[p]->terms;
+            if (!engines[p]->terms_on) continue;
+            ++g->nterms;
+            g->terms_lds = std::max(g->terms_lds, terms_lds_bytes(ts[p]));
+        }
+        if (hipMalloc(&g->d_tmodels, sizeof(TermsModel) * n) != hipSuccess ||
+            hipMemcpy(g->d_tmodels, ts.data(), sizeof(TermsModel) * n, hipMemcpyHostToDevice) != hipSuccess) {
+            stomp_group_destroy(g);
+            return gfail(nullptr, STOMP_E_DEVICE, "group allocation failed");
+        }
+    }
     if (getenv("STOMP_DEBUG_LEAN_PRINT"))   // the group's own choices (read-only: tests and tables)
         fprintf(stderr, "stomp: group of %d engines J %d N %d K %d brick %d, %d weights tiles per engine, "
                         "weights %s\n", (int)n, e0->J, e0->N, e0->K_loc, e0->model.brick, nt,
                 weights_kernel_name(e0->K_loc, true, true));
+    if (state_terms && getenv("STOMP_DEBUG_LEAN_PRINT"))   // the launch launch_terms_group takes (read-only)
+        fprintf(stderr, "stomp: group terms k_terms_group<%d>, LDS %zu B, opt-in %d, engines with terms %d of %d\n",
+                e0->N <= 128 ? 128 : 256, g->terms_lds, g->terms_lds > 64 * 1024 ? 1 : 0, g->nterms, (int)n);
     *out = g;
     return 0;
 }
@@ -238,7 +298,8 @@ int stomp_group_run(stomp_group* g, int32_t first, int32_t count)
     }
     const size_t szc = align256(sizeof(CostArgs) * P), szw = align256(sizeof(WeightArgs) * P),
                  szu = align256(sizeof(UpdateArgs) * P),
-                 szr = e0->Kr > 0 ? align256(sizeof(ReuseRowArgs) * P) : 0, per = szc + szw + szu + szr;
+                 szr = e0->Kr > 0 ? align256(sizeof(ReuseRowArgs) * P) : 0,
+                 szt = g->nterms > 0 ? align256(sizeof(TermsArgs) * P) : 0, per = szc + szw + szu + szr + szt;
     const size_t bytes = per * (size_t)count;
     if (g->staged && hipEventSynchronize(g->staged) != hipSuccess)   // h_args free again
         return gfail(g, STOMP_E_DEVICE, "group staging wait failed");
@@ -267,6 +328,7 @@ int stomp_group_run(stomp_group* g, int32_t first, int32_t count)
         WeightArgs* was = (WeightArgs*)(g->h_args + per * i + szc);
         UpdateArgs* uas = (UpdateArgs*)(g->h_args + per * i + szc + szw);
         ReuseRowArgs* ras = (ReuseRowArgs*)(g->h_args + per * i + szc + szw + szu);
+        TermsArgs* tas = (TermsArgs*)(g->h_args + per * i + szc + szw + szu + szr);
         for (int p = 0; p < P; ++p) {
             stomp_engine* e = g->e[p];
             if (e->pre_it != it) {
@@ -274,6 +336,7 @@ int stomp_group_run(stomp_group* g, int32_t first, int32_t count)
                 pregen_first[p] = 1;
             }
             const StagedIteration st = stage_iteration(e, it, true, cas[p], was[p], uas[p], ras + p);
+            if (szt) tas[p] = terms_args(e, cas[p]);
             if (p == 0) steps[i] = st;
             else if (st.nro != steps[i].nro || st.ntot != steps[i].ntot || st.reuse != steps[i].reuse)
                 return gfail(g, STOMP_E_INVALID, "group engines out of step");
@@ -293,6 +356,13 @@ int stomp_group_run(stomp_group* g, int32_t first, int32_t count)
         {
             Timed tm(e0, T_COST, s);
             launch_cost_group(e0->model, g->d_models, (const CostArgs*)base, P, steps[i].nro, K + steps[i].ntot, s);
+        }
+        if (szt) {
+            // every engine's state-cost terms on the rollouts just evaluated, before the reuse
+            // ranking, the weights (and the next flush's bookkeeping) read them
+            Timed tm(e0, T_TERMS, s);
+            launch_terms_group(g->d_tmodels, (const TermsArgs*)(base + szc + szw + szu + szr), P, steps[i].nro, N,
+                               g->terms_lds, s);
         }
         if (steps[i].reuse) {
             // every engine's reuse step (an engine on its own records its reused rows' launch on
@@ -323,18 +393,28 @@ int stomp_group_synchronize(stomp_group* g)
     for (stomp_engine* e : g->e) all = all && e->pending_member >= 0 && !e->tracking;
     if (all) {
         // every engine's pending noiseless rollout in one launch (one workgroup per engine)
-        const size_t bytes = align256(sizeof(CostArgs) * P);
+        const size_t szc = align256(sizeof(CostArgs) * P);
+        const size_t bytes = szc + (g->nterms > 0 ? align256(sizeof(TermsArgs) * P) : 0);
         if (g->staged && hipEventSynchronize(g->staged) != hipSuccess)
             return gfail(g, STOMP_E_DEVICE, "group staging wait failed");
         if (bytes > g->h_cap || bytes > g->d_cap) {
             all = false;   // the arrays of a run are larger; no run yet: per-engine flushes
         } else {
             CostArgs* cas = (CostArgs*)g->h_args;
-            for (int p = 0; p < P; ++p) cas[p] = noiseless_args(g->e[p]);
+            TermsArgs* tas = (TermsArgs*)(g->h_args + szc);
+            for (int p = 0; p < P; ++p) {
+                cas[p] = noiseless_args(g->e[p]);
+                if (g->nterms > 0) tas[p] = terms_args(g->e[p], cas[p]);
+            }
             hipError_t err = hipMemcpyAsync(g->d_args, g->h_args, bytes, hipMemcpyHostToDevice, g->stream);
             if (err == hipSuccess) err = hipEventRecord(g->staged, g->stream);
             if (err != hipSuccess) return gfail(g, STOMP_E_DEVICE, "group argument upload failed");
             launch_cost_group(g->e[0]->model, g->d_models, (const CostArgs*)g->d_args, P, 1, 0, g->stream);
+            if (g->nterms > 0) {
+                Timed tm(g->e[0], T_TERMS, g->stream);
+                launch_terms_group(g->d_tmodels, (const TermsArgs*)(g->d_args + szc), P, 1, g->e[0]->N, g->terms_lds,
+                                   g->stream);
+            }
         }
     }
     for (stomp_engine* e : g->e) flush_noiseless(e);
@@ -376,8 +456,10 @@ int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_i
     // weights, update and track arguments
     const size_t szc = align256(sizeof(CostArgs) * P), szw = align256(sizeof(WeightArgs) * P),
                  szu = align256(sizeof(UpdateArgs) * P), szt = align256(sizeof(TrackArgs) * P),
-                 szm = align256(sizeof(DevModel) * P), szr = e0->Kr > 0 ? align256(sizeof(ReuseRowArgs) * P) : 0;
-    const size_t slot_bytes = (2 * szc + 2 * szm + szw + szu + szt + szr) * (size_t)chunk;
+                 szm = align256(sizeof(DevModel) * P), szr = e0->Kr > 0 ? align256(sizeof(ReuseRowArgs) * P) : 0,
+                 // both rollout launches' TermsArgs and TermsModel lists
+                 szx = g->nterms > 0 ? 2 * (align256(sizeof(TermsArgs) * P) + align256(sizeof(TermsModel) * P)) : 0;
+    const size_t slot_bytes = (2 * szc + 2 * szm + szw + szu + szt + szr + szx) * (size_t)chunk;
     auto track_args = [&](int p) {
         stomp_engine* e = g->e[p];
         return TrackArgs{e->d_track, e->d_total, e->d_cf, e->d_cs, e->d_opt_costs, e->d_last_traj, e->d_best_traj,
@@ -442,10 +524,15 @@ int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_i
             bool reuse;
             size_t cas, was, uas, tas, ccs, mms, cms, ras;
             const DevModel* m0;
+            // the terms launches after the rollout launch and after the flush: arguments, models,
+            // engines with terms among the launch's (0: no launch)
+            size_t xas, xms, cxas, cxms;
+            int nx, ncx;
         };
         std::vector<Step> steps;
         std::vector<int> prev_main;
-        size_t prev_mms = 0;
+        size_t prev_mms = 0, prev_xms = 0;
+        int prev_nx = 0;
         const int end = std::min(next + chunk, last_step + 1);
         for (int it = next; it < end; ++it) {
             Step st{};
@@ -464,21 +551,37 @@ int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_i
             st.ccs = take(sizeof(CostArgs) * st.nc);
             st.cms = take(sizeof(DevModel) * st.nc);
             st.ras = e0->Kr > 0 ? take(sizeof(ReuseRowArgs) * st.nm) : 0;
+            const bool terms = g->nterms > 0;
+            st.xas = terms ? take(sizeof(TermsArgs) * st.nm) : 0;
+            st.cxas = terms ? take(sizeof(TermsArgs) * st.nc) : 0;
+            st.cxms = terms ? take(sizeof(TermsModel) * st.nc) : 0;
             // the DevModel list of the rollout launch: once per chunk, again where an engine's
             // max_iterations takes it out within the chunk
             if (st.nm > 0 && main != prev_main) {
                 prev_mms = take(sizeof(DevModel) * st.nm);
                 DevModel* ms = (DevModel*)(hb + prev_mms);
                 for (int k = 0; k < st.nm; ++k) ms[k] = g->e[main[k]]->model;
+                if (terms) {
+                    prev_xms = take(sizeof(TermsModel) * st.nm);
+                    TermsModel* xs = (TermsModel*)(hb + prev_xms);
+                    prev_nx = 0;
+                    for (int k = 0; k < st.nm; ++k) {
+                        xs[k] = g->e[main[k]]->terms;
+                        prev_nx += g->e[main[k]]->terms_on ? 1 : 0;
+                    }
+                }
                 prev_main = main;
             }
             st.mms = prev_mms;
+            st.xms = prev_xms;
+            st.nx = st.nm > 0 ? prev_nx : 0;
             if (st.nm > 0) st.m0 = &g->e[main[0]]->model;
             CostArgs* cas = (CostArgs*)(hb + st.cas);
             WeightArgs* was = (WeightArgs*)(hb + st.was);
             UpdateArgs* uas = (UpdateArgs*)(hb + st.uas);
             TrackArgs* tas = (TrackArgs*)(hb + st.tas);
             ReuseRowArgs* ras = (ReuseRowArgs*)(hb + st.ras);
+            TermsArgs* xas = (TermsArgs*)(hb + st.xas);
             for (int k = 0; k < st.nm; ++k) {
                 stomp_engine* e = g->e[main[k]];
                 // inside the optimize loop the noise / params rows are copied out of the pregen
@@ -486,6 +589,7 @@ int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_i
                 // weights read d_noise
                 if (e->pre_it != it) return gfail(g, STOMP_E_INVALID, "group pregen rows out of step");
                 const StagedIteration si = stage_iteration(e, it, false, cas[k], was[k], uas[k], ras + k);
+                if (terms) xas[k] = terms_args(e, cas[k]);
                 if (k == 0) {
                     st.nro = si.nro;
                     st.ntot = si.ntot;
@@ -498,10 +602,17 @@ int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_i
             }
             CostArgs* ccs = (CostArgs*)(hb + st.ccs);
             DevModel* cms = (DevModel*)(hb + st.cms);
+            TermsArgs* cxas = (TermsArgs*)(hb + st.cxas);
+            TermsModel* cxms = (TermsModel*)(hb + st.cxms);
             for (int k = 0; k < st.nc; ++k) {
                 stomp_engine* e = g->e[cohort[k]];
                 ccs[k] = noiseless_args(e);   // with K_r > 0 the extra rollout's rows too
                 cms[k] = e->model;
+                if (terms) {
+                    cxas[k] = terms_args(e, ccs[k]);
+                    cxms[k] = e->terms;
+                    st.ncx += e->terms_on ? 1 : 0;
+                }
                 tas[st.nm + k] = track_args(cohort[k]);
             }
             steps.push_back(st);
@@ -517,10 +628,22 @@ int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_i
                 launch_cost_group(g->e[0]->model, (const DevModel*)(db + st.cms), (const CostArgs*)(db + st.ccs), st.nc,
                                   1, 0, s);
             }
+            if (st.ncx > 0) {
+                Timed tm(e0, T_TERMS, s);
+                launch_terms_group((const TermsModel*)(db + st.cxms), (const TermsArgs*)(db + st.cxas), st.nc, 1, N,
+                                   g->terms_lds, s);
+            }
             if (st.nm > 0) {
                 Timed tm(e0, T_COST, s);
                 launch_cost_group(*st.m0, (const DevModel*)(db + st.mms), (const CostArgs*)(db + st.cas), st.nm, st.nro,
                                   K + st.ntot, s);
+            }
+            // the state-cost terms of both launches before the bookkeeping reads the noiseless
+            // rollouts' totals and constraints-satisfied flags
+            if (st.nx > 0) {
+                Timed tm(e0, T_TERMS, s);
+                launch_terms_group((const TermsModel*)(db + st.xms), (const TermsArgs*)(db + st.xas), st.nm, st.nro, N,
+                                   g->terms_lds, s);
             }
             // before this step's weights / update: a break decided on the previous iteration's
             // noiseless rollout leaves theta where the reference leaves it

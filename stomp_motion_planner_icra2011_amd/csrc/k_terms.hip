@@ -158,15 +158,17 @@ __device__ bool oc_cost(const OcDev& o, const double* R, double* cost)
     return !(roll > o.tol[0] || pitch > o.tol[1] || yaw > o.tol[2]);
 }
 
+// e: the workgroup's rollout of the launch (k_terms: blockIdx.x; k_terms_group: the engines of a
+// group share one launch)
 template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void k_terms(TermsModel m, TermsArgs a)
+__device__ __forceinline__ void terms_body(const TermsModel& m, const TermsArgs& a, const int e)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     if (a.stop && *a.stop) return;
     const int J = m.J, N = m.N, nc = m.nchain;
     double* Q = (double*)lds_raw;            // [3][J][N]
     double* F = Q + (size_t)3 * J * N;       // [nc][6][N]
-    const int e = blockIdx.x, t = threadIdx.x;
+    const int t = threadIdx.x;
     const bool extra = e == a.num_noisy;
     const double* traj = extra ? a.x_traj : a.traj + (long long)e * J * N;
     double* state = extra ? a.x_state : a.state + (long long)e * N;
@@ -324,6 +326,32 @@ __global__ __launch_bounds__(BLOCK) void k_terms(TermsModel m, TermsArgs a)
     if (t == 0 && cso) *cso = all_ok ? 1 : 0;
 }
 
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_terms(TermsModel m, TermsArgs a)
+{
+    terms_body<BLOCK>(m, a, blockIdx.x);
+}
+
+// the terms of a group of engines of one shape in one launch (stomp_group_run): engine p's rollouts
+// are workgroups [p rows, (p + 1) rows), rows the most any engine of the launch evaluated; the
+// models and arguments live in device memory, one entry per engine.  The workgroups past an
+// engine's own rollouts, of an engine without terms (its state rows are the rollout kernel's) and
+// of a stopped engine return before they write anything.
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_terms_group(const TermsModel* ms, const TermsArgs* as, int rows)
+{
+    const int p = blockIdx.x / rows, r = blockIdx.x - p * rows;
+    // read through the constant address space: wave-uniform scalar loads the compiler may repeat,
+    // as it does for a kernel argument (k_rollout_group)
+    using CModel = const __attribute__((address_space(4))) TermsModel;
+    using CArgs = const __attribute__((address_space(4))) TermsArgs;
+    const TermsModel& m = *(const TermsModel*)((CModel*)ms + p);
+    const TermsArgs& a = *(const TermsArgs*)((CArgs*)as + p);
+    if (!(m.torque || m.noc > 0)) return;
+    if (r >= a.num_noisy + (a.x_traj ? 1 : 0)) return;
+    terms_body<BLOCK>(m, a, r);
+}
+
 }  // namespace
 
 size_t terms_lds_bytes(const TermsModel& m)
@@ -345,6 +373,19 @@ void launch_terms(const TermsModel& m, const TermsArgs& a, hipStream_t s)
     } else {
         if (lds > 64 * 1024) lds_opt_in((const void*)k_terms<256>, lds);
         hipLaunchKernelGGL((k_terms<256>), dim3(blocks), dim3(256), lds, s, m, a);
+    }
+}
+
+void launch_terms_group(const TermsModel* ms, const TermsArgs* as, int engines, int rows, int N, size_t lds,
+                        hipStream_t s)
+{
+    if (engines <= 0 || rows <= 0) return;
+    if (N <= 128) {
+        if (lds > 64 * 1024) lds_opt_in((const void*)k_terms_group<128>, lds);
+        hipLaunchKernelGGL((k_terms_group<128>), dim3(engines * rows), dim3(128), lds, s, ms, as, rows);
+    } else {
+        if (lds > 64 * 1024) lds_opt_in((const void*)k_terms_group<256>, lds);
+        hipLaunchKernelGGL((k_terms_group<256>), dim3(engines * rows), dim3(256), lds, s, ms, as, rows);
     }
 }
 

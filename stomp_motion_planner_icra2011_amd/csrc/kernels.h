@@ -330,6 +330,12 @@ const char* lds_opt_in_error();
 
 size_t terms_lds_bytes(const TermsModel& m);
 void launch_terms(const TermsModel& m, const TermsArgs& a, hipStream_t s);
+// the terms of a group of engines of one shape (J, N) in one launch: ms / as [engines] in device
+// memory, `rows` workgroups per engine (the most rollouts any entry names: num_noisy + the extra
+// one), lds the largest terms_lds_bytes of the entries' models.  An entry without terms (no torque
+// term, no constraints) or with its stop flag up is a no-op: nothing of that engine is written.
+void launch_terms_group(const TermsModel* ms, const TermsArgs* as, int engines, int rows, int N, size_t lds,
+                        hipStream_t s);
 
 void launch_noise(const NoiseArgs& a, hipStream_t s);
 // The reuse step with the reused rows' projection and control costs (policy_improvement.cpp:

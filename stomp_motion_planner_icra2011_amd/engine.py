@@ -79,6 +79,10 @@ class stomp_stats(C.Structure):
                 ("collision_success_duration", C.c_double)]
 
 
+class stomp_group_options(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("state_terms", C.c_int32), ("compact", C.c_int32)]
+
+
 # every symbol include/stomp_engine.h declares (checked by tests/test_abi.py)
 EXPORTED = ["stomp_engine_create", "stomp_engine_destroy", "stomp_engine_last_error", "stomp_last_error",
             "stomp_engine_get_theta", "stomp_engine_set_theta", "stomp_engine_iterate", "stomp_engine_run",
@@ -92,7 +96,7 @@ EXPORTED = ["stomp_engine_create", "stomp_engine_destroy", "stomp_engine_last_er
             "stomp_pi_improve_policy", "stomp_pi_add_extra_rollouts", "stomp_pi_reset", "stomp_sdf_build_objects",
             "stomp_stream_create", "stomp_stream_destroy", "stomp_group_create", "stomp_group_run",
             "stomp_group_synchronize", "stomp_group_last_error", "stomp_group_destroy", "stomp_engine_shard_mode",
-            "stomp_group_optimize", "stomp_group_optimize_chunk",
+            "stomp_group_optimize", "stomp_group_optimize_chunk", "stomp_group_create_with",
             "stomp_engine_shard_info", "stomp_shard_decide", "stomp_engine_source_hash",
             "stomp_engine_refresh_field", "stomp_device_selftest_trig"]
 
@@ -160,6 +164,8 @@ def load_library(path: Optional[str] = None):
     l.stomp_stream_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
     l.stomp_stream_destroy.argtypes = [C.c_void_p]
     l.stomp_group_create.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]
+    l.stomp_group_create_with.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(stomp_group_options),
+                                          C.POINTER(C.c_void_p)]
     l.stomp_group_run.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     l.stomp_group_synchronize.argtypes = [C.c_void_p]
     l.stomp_group_optimize.argtypes = [C.c_void_p, C.POINTER(stomp_stats), dp, C.c_int32]
@@ -497,15 +503,26 @@ class EngineGroup:
     (stomp_group_run: three dispatches per iteration for the whole group, four on the iterations
     that reuse rollouts).  One shape: J, N, K, num_reused_rollouts, spheres, model and field layout
     agree; at most 16 joints, no cumulative costs, no state-cost terms, one device per engine, and
-    with reused rollouts at most 1023 rollouts."""
+    with reused rollouts at most 1023 rollouts.
+    state_terms=True (stomp_group_create_with): engines with the torque term and / or orientation
+    path constraints are accepted too, each with its own terms (a group may mix engines with the
+    torque term, with constraints, with both and with neither); one more launch per grouped rollout
+    launch prices the terms of all of them.  compact: None leaves stomp_group_optimize's compaction
+    to STOMP_DEBUG_GROUP_COMPACT, False / True turn it off / on.  EngineGroup(engines) alone is
+    stomp_group_create."""
 
-    def __init__(self, engines):
+    def __init__(self, engines, state_terms: bool = False, compact: Optional[bool] = None):
         self._h = None   # set before the call that may raise, so __del__ has nothing to free
         l = load_library()
         self.engines = list(engines)
         arr = (C.c_void_p * len(self.engines))(*[e.h.value for e in self.engines])
         h = C.c_void_p()
-        rc = l.stomp_group_create(arr, len(self.engines), C.byref(h))
+        if state_terms or compact is not None:
+            opt = stomp_group_options(C.sizeof(stomp_group_options), 1 if state_terms else 0,
+                                      -1 if compact is None else (1 if compact else 0))
+            rc = l.stomp_group_create_with(arr, len(self.engines), C.byref(opt), C.byref(h))
+        else:
+            rc = l.stomp_group_create(arr, len(self.engines), C.byref(h))
         if rc != 0:
             raise RuntimeError(f"stomp group error {rc}: {l.stomp_last_error().decode()}")
         self._h = h

@@ -184,7 +184,8 @@ bool StompOptimizer::finishOptimize(const stomp_stats& st)
 }
 
 // optimize() for several optimizers at once: their engines as one group (stomp_group_optimize),
-// every problem stopping on its own (with or without reused rollouts: one count for the batch)
+// every problem stopping on its own (with or without reused rollouts: one count for the batch;
+// optimizers with the torque term or path constraints plan in the group too, state_terms)
 bool StompOptimizer::optimizeBatch(const std::vector<StompOptimizer*>& optimizers)
 {
     if (optimizers.empty()) return true;
@@ -201,7 +202,8 @@ bool StompOptimizer::optimizeBatch(const std::vector<StompOptimizer*>& optimizer
         stride = std::max(stride, o->parameters_->max_iterations);
     }
     stomp_group* g = nullptr;
-    if (stomp_group_create(engines.data(), (int32_t)engines.size(), &g) != 0) {
+    const stomp_group_options options = {(int32_t)sizeof(stomp_group_options), 1, -1};
+    if (stomp_group_create_with(engines.data(), (int32_t)engines.size(), &options, &g) != 0) {
         first->error_ = stomp_last_error();
         return false;
     }

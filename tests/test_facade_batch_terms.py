@@ -1,0 +1,97 @@
+"""GPU: StompOptimizer::optimizeBatch of the C++ facade over optimizers with state-cost terms --
+three PR2 problems with the torque term and the upright path constraint on one shared stream,
+optimized as one engine group (stomp_group_create_with, state_terms = 1), each against the CPU
+oracle's optimize() of its problem, bit for bit.  tests/facade_batch_driver.cpp hands no constraints
+and no term weights over, so the driver is tests/facade_batch_terms_driver.cpp.
+
+Before state_terms, optimizeBatch returned false for this batch (STOMP_E_UNSUPPORTED)."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle import pyoracle as po
+from stomp_motion_planner_icra2011_amd import problem as pb
+from tests import facade_util as fu
+from tests.test_gpu_group_optimize import INT_STATS
+from tests.test_gpu_group_terms import UPRIGHT_TOL, upright
+
+pytestmark = pytest.mark.gpu
+
+
+def build_terms_driver(directory):
+    """facade_util.build_driver's compile line for tests/facade_batch_terms_driver.cpp."""
+    from stomp_motion_planner_icra2011_amd import _build
+    lib = _build.build_facade()
+    exe = os.path.join(directory, "facade_batch_terms_driver")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-I", os.path.join(fu.ROOT, "include"),
+                           os.path.join(fu.ROOT, "tests", "facade_batch_terms_driver.cpp"), "-o", exe, lib, _build.LIB,
+                           "-Wl,-rpath," + fu.PKG])
+    return exe
+
+
+def write_terms(p, directory):
+    rows = [" ".join(map(repr, [float(p.params.constraint_cost_weight), float(p.params.torque_cost_weight),
+                                len(p.orientation_constraints)]))]
+    for c in p.orientation_constraints:
+        rows.append(" ".join(map(repr, [p.robot.index(c.link_name), *map(float, c.orientation), int(not c.header_frame),
+                                        float(c.absolute_roll_tolerance), float(c.absolute_pitch_tolerance),
+                                        float(c.absolute_yaw_tolerance), float(c.weight)])))
+    with open(os.path.join(directory, "terms.txt"), "w") as f:
+        f.write("\n".join(rows) + "\n")
+
+
+def problems():
+    """Problems 0, 8 and 1 of tests/test_gpu_group_terms.py's recipe, all three with the torque term:
+    two stop on their own, one runs out its 60 iterations because its trajectory never satisfies
+    the constraint."""
+    base = pb.make_problem(grid_n=64, num_rollouts=20, num_reused_rollouts=10)
+    d = np.random.default_rng(11).uniform(-0.15, 0.15, (16, 2, base.J))
+    return [pb.make_problem(grid_n=64, num_rollouts=20, num_reused_rollouts=10, seed=base.seed + 1 + i,
+                            start=list(base.start + d[i, 0]), goal=list(base.goal + d[i, 1]),
+                            max_iterations=60, max_iterations_after_collision_free=2,
+                            orientation_constraints=[upright(UPRIGHT_TOL)], torque_cost_weight=0.001)
+            for i in (0, 8, 1)]
+
+
+def test_facade_optimize_batch_with_terms_matches_the_oracles(tmp_path):
+    ps = problems()
+    assert all(p.params.torque_cost_weight > 1e-9 and len(p.orientation_constraints) == 1 for p in ps)
+    oracles = [po.Oracle(p, threads=8) for p in ps]
+    oresults = [o.optimize() for o in oracles]
+    ostops = [int(st.iterations) for st, _ in oresults]
+    print("oracle stops", ostops)
+    assert len(set(ostops)) == 3 and max(ostops) == 60, ostops   # the three stop on their own
+    dirs = []
+    for i, p in enumerate(ps):
+        d = tmp_path / f"p{i}"
+        d.mkdir()
+        fu.write_problem(p, str(d))
+        write_terms(p, str(d))
+        dirs.append(str(d))
+    exe = build_terms_driver(str(tmp_path))
+    res = str(tmp_path / "out.txt")
+    r = subprocess.run([exe, res] + dirs, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr
+    toks = open(res).read().split()
+    pos = 0
+    for i, (p, o) in enumerate(zip(ps, oracles)):
+        ost, ocosts = oresults[i]
+        head = toks[pos:pos + 9]
+        pos += 9
+        it, ntq = int(head[0]), int(head[8])
+        print("optimizer", i, "iterations", it, "oracle", ost.iterations)
+        assert [int(x) for x in head[:5]] == [int(getattr(ost, k)) for k in INT_STATS], i
+        assert float(head[5]) == ost.best_cost, i
+        success_duration, collision_duration = float(head[6]), float(head[7])
+        assert (success_duration > 0) == (ost.success_iteration >= 0) and 0 <= success_duration < 60
+        assert (collision_duration > 0) == (ost.collision_success_iteration >= 0) and 0 <= collision_duration < 60
+        vals = np.array([float(x) for x in toks[pos:pos + it + ntq + p.J * p.N]])
+        pos += it + ntq + p.J * p.N
+        np.testing.assert_array_equal(vals[:it], ocosts, err_msg=f"optimizer {i} costs")
+        assert ntq == p.N
+        np.testing.assert_array_equal(vals[it:it + ntq], o.best_torques(), err_msg=f"optimizer {i} torques")
+        np.testing.assert_array_equal(vals[it + ntq:].reshape(p.J, p.N), o.best_trajectory(),
+                                      err_msg=f"optimizer {i} best trajectory")
+    assert pos == len(toks)

@@ -11,7 +11,14 @@ trajectory.
 --reused K_r gives every problem K_r reused rollouts (0: none, cfg5); every repeat then starts from
 a reset generateRollouts state too, so that all of them optimize the same thing.
 
+--upright gives every problem the reference's upright path constraint on the gripper
+(problem.upright_constraint; --upright-tolerance R replaces its 0.2 rad of roll and pitch), and
+--torque-weight W the torque term; the groups are then created with state_terms (and their compaction
+chosen through the options).  --ways picks the ways to run (a library without
+stomp_group_create_with, or one that refuses terms in groups, runs `--ways a` alone).
+
     python tools/group_optimize_ab.py [--out FILE] [--problems 64] [--repeats 5] [--reused 0]
+                                      [--upright] [--upright-tolerance 0.2] [--torque-weight 0] [--ways abc]
 """
 import argparse
 import os
@@ -38,8 +45,21 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--max-iterations", type=int, default=200)
     ap.add_argument("--reused", type=int, default=0, help="num_reused_rollouts of every problem")
+    ap.add_argument("--upright", action="store_true", help="the reference's upright constraint on every problem")
+    ap.add_argument("--upright-tolerance", type=float, default=None, help="roll / pitch tolerance (rad) in its place")
+    ap.add_argument("--torque-weight", type=float, default=0.0, help="torque_cost_weight of every problem")
+    ap.add_argument("--ways", default="abc", help="which of a, b, c to run")
     args = ap.parse_args()
     P = args.problems
+    terms = args.upright or args.torque_weight > 1e-9
+    extra = {}
+    if args.upright:
+        oc = pb.upright_constraint()
+        if args.upright_tolerance is not None:
+            oc.absolute_roll_tolerance = oc.absolute_pitch_tolerance = args.upright_tolerance
+        extra["orientation_constraints"] = [oc]
+    if args.torque_weight:
+        extra["torque_cost_weight"] = args.torque_weight
     base = pb.make_problem(dof=7, waypoints=100, grid_n=args.grid, num_rollouts=args.rollouts,
                            num_reused_rollouts=args.reused, build_grid=False)
     sdf = eng.DeviceBuffer(2 * args.grid ** 3, device=0)
@@ -52,13 +72,22 @@ def main():
                             num_reused_rollouts=args.reused, build_grid=False, seed=base.seed + 1 + i,
                             start=list(base.start + offsets[i, 0]),
                             goal=list(base.goal + offsets[i, 1]), max_iterations=args.max_iterations,
-                            max_iterations_after_collision_free=2)
+                            max_iterations_after_collision_free=2, **extra)
         engines.append(eng.Engine(p, device=0, sdf_device_ptr=sdf.ptr, stream=stream.ptr))
-    # the switch is read when a group is created
-    os.environ["STOMP_DEBUG_GROUP_COMPACT"] = "0"
-    group_all = eng.EngineGroup(engines)
-    os.environ["STOMP_DEBUG_GROUP_COMPACT"] = "1"
-    group_compact = eng.EngineGroup(engines)
+    group_all = group_compact = None
+    if terms:
+        if "b" in args.ways:
+            group_all = eng.EngineGroup(engines, state_terms=True, compact=False)
+        if "c" in args.ways:
+            group_compact = eng.EngineGroup(engines, state_terms=True, compact=True)
+    else:
+        # the switch is read when a group is created
+        if "b" in args.ways:
+            os.environ["STOMP_DEBUG_GROUP_COMPACT"] = "0"
+            group_all = eng.EngineGroup(engines)
+        if "c" in args.ways:
+            os.environ["STOMP_DEBUG_GROUP_COMPACT"] = "1"
+            group_compact = eng.EngineGroup(engines)
     theta0 = [e.theta() for e in engines]
 
     def reset():
@@ -70,9 +99,15 @@ def main():
                 e.pi_reset()   # the first iteration generates every rollout again
 
     ways = [("a: one stomp_engine_optimize per problem", lambda: [e.optimize() for e in engines]),
-            ("b: stomp_group_optimize, compaction off", group_all.optimize),
-            ("c: stomp_group_optimize, compaction on", group_compact.optimize)]
+            ("b: stomp_group_optimize, compaction off", group_all.optimize if group_all else None),
+            ("c: stomp_group_optimize, compaction on", group_compact.optimize if group_compact else None)]
+    ways = [(name, run) for name, run in ways if name[0] in args.ways]
     reused = f", K_r = {args.reused}" if args.reused else ""
+    if args.upright:
+        tol = 0.2 if args.upright_tolerance is None else args.upright_tolerance
+        reused += f", upright constraint (roll / pitch within {tol:g} rad)"
+    if args.torque_weight:
+        reused += f", torque_cost_weight = {args.torque_weight:g}"
     lines = [f"group_optimize_ab: {P} problems, K = {args.rollouts}{reused}, {args.grid}^3, max_iterations = "
              f"{args.max_iterations}, max_iterations_after_collision_free = 2, {args.repeats} repeats after one warm-up"]
     reference = None
@@ -99,19 +134,24 @@ def main():
         lines.append(f"{name:48s} median {times[len(times) // 2]:9.2f} ms  min {times[0]:9.2f}  max {times[-1]:9.2f}")
     stops = sorted(s[0] for s in reference[0])
     total = sum(stops)
-    lines.append("statistics, cost histories and best trajectories identical across a, b, c and all repeats")
+    lines.append(f"statistics, cost histories and best trajectories identical across {', '.join(args.ways)} and all "
+                 "repeats")
     lines.append(f"stop iterations (sorted): {stops}")
+    lines.append(f"problems that stop before max_iterations: {sum(1 for n in stops if n < args.max_iterations)} of {P}")
     lines.append(f"problem-iterations run: {total} of {P * args.max_iterations} "
                  f"(lockstep without compaction: {P} x {max(stops)} = {P * max(stops)})")
-    lines.append(f"speed-up of c over a: {medians['a'] / medians['c']:.2f}x, of c over b: {medians['b'] / medians['c']:.2f}x")
+    if all(w in medians for w in "abc"):
+        lines.append(f"speed-up of c over a: {medians['a'] / medians['c']:.2f}x, of c over b: "
+                     f"{medians['b'] / medians['c']:.2f}x")
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             f.write(text)
-    group_all.close()
-    group_compact.close()
+    for g in (group_all, group_compact):
+        if g:
+            g.close()
     for e in engines:
         e.close()
     stream.close()
