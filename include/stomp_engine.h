@@ -270,7 +270,9 @@ int stomp_engine_get_last_trajectory(stomp_engine* e, double* traj);
 /* Inspection for parity tests.  which: "params","noise","control_costs","probabilities"
  * -> K_local x J x N; "state_costs" -> K_local x N; the extra (noiseless) rollout of
  * addExtraRollouts (policy_improvement.cpp:443-462): "x_params","x_noise","x_control_costs"
- * -> J x N (kept with K_r > 0 only), "x_state_costs" -> N. */
+ * -> J x N (kept with K_r > 0 only), "x_state_costs" -> N; "cumulative_costs" -> K_local x J x N,
+ * the rows the last weights launch read (computeRolloutCumulativeCosts, policy_improvement.cpp:
+ * 301-320), STOMP_E_INVALID on an engine created without use_cumulative_costs. */
 int stomp_engine_get_rollouts(stomp_engine* e, const char* which, double* out);
 /* which: "Rinv","L","M","Qinv" (N x N, joint selects Qinv), "R" (free block of the
  * control-cost matrix, CovariantTrajectoryPolicy::getControlCosts,
@@ -391,7 +393,23 @@ int stomp_diff_rules(double* out);
  * STOMP_E_UNSUPPORTED with state_terms = 1; a refused creation leaves every engine untouched.
  * compact: -1 leaves the choice to STOMP_DEBUG_GROUP_COMPACT as in stomp_group_create, 0 / 1
  * turn the compaction of stomp_group_optimize off / on.  NULL options or a struct_size other than
- * sizeof(stomp_group_options): STOMP_E_INVALID. */
+ * sizeof(stomp_group_options): STOMP_E_INVALID.
+ * stomp_group_create_flags takes plain arguments: accept, a mask of STOMP_GROUP_ACCEPT_*, and
+ * compact as above (-1 / 0 / 1).  stomp_group_create_with(e, n, {state_terms s, compact c}, out) is
+ * exactly stomp_group_create_flags(e, n, s ? STOMP_GROUP_ACCEPT_STATE_TERMS : 0, c, out).  With
+ * STOMP_GROUP_ACCEPT_CUMULATIVE the group also accepts engines with use_cumulative_costs (the
+ * reference's default), mixed freely with engines without, at K_r = 0 and K_r > 0, with or
+ * without state-cost terms (both bits): every grouped weights launch of stomp_group_run and
+ * stomp_group_optimize is then preceded by one more launch, the cumulative rows of all its
+ * engines (computeRolloutCumulativeCosts' suffix sums, policy_improvement.cpp:308-316; an engine
+ * without cumulative costs has no workgroup that writes), after the state-cost terms and the
+ * reused rows' launch; the post-conditions stay the ones above, the rows of
+ * stomp_engine_get_rollouts("cumulative_costs") included.  Such a group takes N <= 256; every
+ * other condition is unchanged.  Unknown bits in accept, a compact outside -1 / 0 / 1, NULL
+ * engines or out, num_engines <= 0: STOMP_E_INVALID, checked before any engine or device is
+ * touched (a machine without a GPU can make these calls). */
+#define STOMP_GROUP_ACCEPT_STATE_TERMS 1u
+#define STOMP_GROUP_ACCEPT_CUMULATIVE 2u
 typedef struct stomp_group stomp_group;
 typedef struct stomp_group_options {
     int32_t struct_size;   /* sizeof(stomp_group_options) */
@@ -403,6 +421,8 @@ int stomp_stream_destroy(void* stream);
 int stomp_group_create(stomp_engine* const* engines, int32_t num_engines, stomp_group** out);
 int stomp_group_create_with(stomp_engine* const* engines, int32_t num_engines,
                             const stomp_group_options* options, stomp_group** out);
+int stomp_group_create_flags(stomp_engine* const* engines, int32_t num_engines, uint32_t accept, int32_t compact,
+                             stomp_group** out);
 int stomp_group_run(stomp_group* g, int32_t first_iteration, int32_t count);
 int stomp_group_synchronize(stomp_group* g);
 /* StompOptimizer::optimize (stomp_optimizer.cpp:249-401) for every engine of the group at once.

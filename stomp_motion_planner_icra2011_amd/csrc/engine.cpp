@@ -794,6 +794,11 @@ int stomp_engine_get_rollouts(stomp_engine* e, const char* which, double* out)
     else if (!std::strcmp(which, "noise")) src = e->d_noise + o;
     else if (!std::strcmp(which, "control_costs")) src = e->d_control + o;
     else if (!std::strcmp(which, "probabilities")) src = e->d_prob + o;
+    else if (!std::strcmp(which, "cumulative_costs")) {
+        // the rows the last weights launch read (k_cumulative / k_cumulative_group)
+        if (!e->use_cum) return fail(e, STOMP_E_INVALID, "the engine was created without use_cumulative_costs");
+        src = e->d_cum + o;
+    }
     else if (!std::strcmp(which, "state_costs")) { src = e->d_state + (size_t)e->row0 * e->N; n = (size_t)e->K_loc * e->N; }
     else if (!std::strncmp(which, "x_", 2)) {
         // the extra (noiseless) rollout of addExtraRollouts (policy_improvement.cpp:443-462);

@@ -18,6 +18,10 @@
 // (k_terms_group, each engine with its own TermsModel; an engine without terms has no workgroup
 // that writes), before anything reads the state costs, the noiseless total or the
 // constraints-satisfied flag.
+// A group created accepting cumulative costs (stomp_group_create_flags) also takes engines with
+// use_cumulative_costs, mixed freely with engines without: every grouped weights launch is then
+// preceded, inside the same timed scope, by one launch of the cumulative rows of all of its
+// engines (k_cumulative_group; an engine without cumulative costs has no workgroup that writes).
 #include "engine_internal.h"
 
 #include <algorithm>
@@ -33,6 +37,7 @@ struct stomp_group {
     bool state_terms = false;             // engines with terms accepted (stomp_group_create_with)
     TermsModel* d_tmodels = nullptr;      // [P] every engine's terms model (state_terms)
     int nterms = 0;                       // engines with terms
+    int ncum = 0;                         // engines with cumulative costs (stomp_group_create_flags)
     size_t terms_lds = 0;                 // the largest terms_lds_bytes among them: k_terms_group's dynamic LDS
     unsigned char* d_args = nullptr;      // [iterations][P] CostArgs, WeightArgs, UpdateArgs, (K_r > 0) ReuseRowArgs,
                                           // (engines with terms) TermsArgs
@@ -131,6 +136,9 @@ StagedIteration stage_iteration(stomp_engine* e, int it, bool keep_in_pre, CostA
     }
     WeightArgs wa = weight_args(e, e->K_loc, rows_pre ? na.pre_eps : e->d_noise);
     wa.mode = W_FUSED;
+    // enqueue_iteration's: the grouped cumulative launch makes the rows the weights read
+    wa.use_cumulative = e->use_cum;
+    wa.cum = e->use_cum ? e->d_cum : nullptr;
     wa_out = wa;
     ua_out = UpdateArgs{e->d_MT, e->d_u, e->d_theta, e->d_stop};
     e->pending_member = it - 1;
@@ -204,7 +212,21 @@ int stomp_group_create_with(stomp_engine* const* engines, int32_t n, const stomp
     if (!engines || n <= 0 || !out) return gfail(nullptr, STOMP_E_INVALID, "invalid group arguments");
     if (!options || options->struct_size != (int32_t)sizeof(stomp_group_options))
         return gfail(nullptr, STOMP_E_INVALID, "invalid group options (null, or struct_size is not sizeof(stomp_group_options))");
-    const bool state_terms = options->state_terms != 0;
+    return stomp_group_create_flags(engines, n, options->state_terms ? STOMP_GROUP_ACCEPT_STATE_TERMS : 0u,
+                                    options->compact, out);
+}
+
+int stomp_group_create_flags(stomp_engine* const* engines, int32_t n, uint32_t accept, int32_t compact,
+                             stomp_group** out)
+{
+    // all of this before any engine or device is touched
+    if (!engines || n <= 0 || !out) return gfail(nullptr, STOMP_E_INVALID, "invalid group arguments");
+    if (accept & ~(STOMP_GROUP_ACCEPT_STATE_TERMS | STOMP_GROUP_ACCEPT_CUMULATIVE))
+        return gfail(nullptr, STOMP_E_INVALID, "invalid group arguments: unknown bits in accept");
+    if (compact < -1 || compact > 1)
+        return gfail(nullptr, STOMP_E_INVALID, "invalid group arguments: compact is -1, 0 or 1");
+    const bool state_terms = (accept & STOMP_GROUP_ACCEPT_STATE_TERMS) != 0;
+    const bool cumulative = (accept & STOMP_GROUP_ACCEPT_CUMULATIVE) != 0;
     stomp_engine* e0 = engines[0];
     if (!e0) return gfail(nullptr, STOMP_E_INVALID, "null engine");
     const size_t lds0 = rollout_lds_bytes(e0->model, e0->model.pad_lds);
@@ -218,11 +240,16 @@ int stomp_group_create_with(stomp_engine* const* engines, int32_t n, const stomp
             return gfail(nullptr, STOMP_E_INVALID,
                          "the engines of a group have one shape (J, N, K, K_r, spheres, model, field layout)");
         if (e->world != 1 || !e->pre_on || (e->terms_on && !state_terms) || e->split_modes || e->gather ||
-            e->use_cum || e->J > 16)
+            (e->use_cum && !cumulative) || e->J > 16)
             return gfail(nullptr, STOMP_E_UNSUPPORTED,
-                         state_terms ? "groups run single-device engines of at most 16 joints without cumulative costs"
-                                     : "groups run single-device engines of at most 16 joints without state-cost "
-                                       "terms or cumulative costs");
+                         cumulative ? (state_terms ? "groups run single-device engines of at most 16 joints"
+                                                   : "groups run single-device engines of at most 16 joints without "
+                                                     "state-cost terms")
+                         : state_terms ? "groups run single-device engines of at most 16 joints without cumulative costs"
+                                       : "groups run single-device engines of at most 16 joints without state-cost "
+                                         "terms or cumulative costs");
+        if (e->use_cum && cumulative_group_rows(e->N) <= 0)
+            return gfail(nullptr, STOMP_E_UNSUPPORTED, "groups with cumulative costs take at most 256 time steps");
         if (e->Kr > 0) {
             // the reuse step is the reused rows' kernel (launch_reuse_rows_ok: K + 1 candidates
             // ranked by a workgroup, J <= 16, the row kernel's LDS)
@@ -243,9 +270,10 @@ int stomp_group_create_with(stomp_engine* const* engines, int32_t n, const stomp
     g->device = e0->device;
     g->stream = e0->stream;
     g->nt = nt;
-    if (options->compact >= 0) g->compact = options->compact != 0;
+    if (compact >= 0) g->compact = compact != 0;
     else if (const char* c = getenv("STOMP_DEBUG_GROUP_COMPACT")) g->compact = c[0] == '1';
     g->state_terms = state_terms;
+    for (int p = 0; p < n; ++p) g->ncum += engines[p]->use_cum ? 1 : 0;
     std::vector<DevModel> ms(n);
     for (int p = 0; p < n; ++p) ms[p] = engines[p]->model;
     if (hipMalloc(&g->d_models, sizeof(DevModel) * n) != hipSuccess ||
@@ -275,6 +303,10 @@ int stomp_group_create_with(stomp_engine* const* engines, int32_t n, const stomp
     if (state_terms && getenv("STOMP_DEBUG_LEAN_PRINT"))   // the launch launch_terms_group takes (read-only)
         fprintf(stderr, "stomp: group terms k_terms_group<%d>, LDS %zu B, opt-in %d, engines with terms %d of %d\n",
                 e0->N <= 128 ? 128 : 256, g->terms_lds, g->terms_lds > 64 * 1024 ? 1 : 0, g->nterms, (int)n);
+    if (g->ncum > 0 && getenv("STOMP_DEBUG_LEAN_PRINT"))   // the launch launch_cumulative_group takes (read-only)
+        fprintf(stderr, "stomp: group cumulative k_cumulative_group<%d>, rows per workgroup %d, LDS %zu B, engines "
+                        "with cumulative costs %d of %d\n", cumulative_group_rows(e0->N), cumulative_group_rows(e0->N),
+                cumulative_group_lds_bytes(e0->N), g->ncum, (int)n);
     *out = g;
     return 0;
 }
@@ -371,7 +403,10 @@ int stomp_group_run(stomp_group* g, int32_t first, int32_t count)
             launch_reuse_rows_group(shape, (const ReuseRowArgs*)(base + szc + szw + szu), P, e0->K, e0->Kr, s);
         }
         {
+            // the cumulative rows of the engines that use them, on the control costs the reuse
+            // launch re-priced, in the weights' scope as an engine's own launch_cumulative
             Timed tm(e0, T_WEIGHTS, s);
+            if (g->ncum > 0) launch_cumulative_group((const WeightArgs*)(base + szc), P, J, N, K, s);
             launch_weights_group((const WeightArgs*)(base + szc), P, J, N, K, s);
         }
         {
@@ -656,7 +691,9 @@ int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_i
                     launch_reuse_rows_group(shape, (const ReuseRowArgs*)(db + st.ras), st.nm, e0->K, e0->Kr, s);
                 }
                 {
+                    // (the step's own list: compacted, or a stopped engine a no-op at its flag)
                     Timed tm(e0, T_WEIGHTS, s);
+                    if (g->ncum > 0) launch_cumulative_group((const WeightArgs*)(db + st.was), st.nm, J, N, K, s);
                     launch_weights_group((const WeightArgs*)(db + st.was), st.nm, J, N, K, s);
                 }
                 {

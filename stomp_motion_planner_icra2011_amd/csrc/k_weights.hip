@@ -801,6 +801,133 @@ void launch_cumulative(const WeightArgs& a, double* cum, hipStream_t s)
     hipLaunchKernelGGL(k_cumulative, dim3((n + 255) / 256), dim3(256), 0, s, a, cum);
 }
 
+// k_cumulative's rows for every engine of a group in one launch (engine p's slabs at p * nslab).
+// Rows (r J + d) of control and of cum are contiguous, so a workgroup takes a slab of ROWS
+// consecutive rows -- ROWS * N contiguous doubles -- and stages state + control through LDS with
+// flat coalesced loads (lane i takes element i, i + 256, ...: every wave access is 512 contiguous
+// bytes, whole 128-B lines since a slab starts at a multiple of ROWS * N * 8 >= 128 N bytes).
+// The LDS row pitch is N | 1 doubles: odd, so the lanes of a half-wave, one row each, read and
+// write b64 words of distinct banks.  Lane l < ROWS then runs row l's chain c[t] += c[t + 1],
+// t = N - 2 .. 0, out of LDS: kCumAhead elements read ahead of the adds that need them, so the
+// dependent chain is the fp64 adds and not the LDS latency; the adds are the reference's, in its
+// order (one add per element twice over: nothing to contract or re-associate).  The slab goes back
+// with the same flat mapping.
+// Sizing: the chain is ~N dependent adds (well under a microsecond), the launch is bound by the
+// loads and stores, so what matters is workgroups in flight per CU and loads in flight per lane.
+// N <= 128: 32 rows, LDS <= 32 * 129 * 8 = 33 024 B; N <= 256: 16 rows, LDS <= 16 * 257 * 8 =
+// 32 896 B.  Either way four workgroups fit the 144 KiB budgeted per CU without the large-LDS
+// opt-in, a lane holds at most ROWS * N / 256 = 16 elements (all its loads in flight at once,
+// 64 VGPRs), and a slab is at most 32 KiB each way.  Wider slabs (64 rows, a whole wave of chains)
+// would need 66 KB and halve the workgroups per CU for a phase that is not the bound; J <= 16 only
+// bounds the state rows a slab touches (ROWS / J + 2, read straight from global: they stay in L2).
+// The last slab of an engine is partial unless K J is a multiple of ROWS; no slab crosses engines.
+constexpr int kCumAhead = 16;
+constexpr int kCumEpt = 16;   // ROWS * N <= kCumEpt * 256
+
+template <int ROWS>
+__global__ __launch_bounds__(256) void k_cumulative_group(const WeightArgs* as, int nslab)
+{
+    extern __shared__ __attribute__((aligned(16))) double C[];   // [ROWS][N | 1]
+    const int p = blockIdx.x / nslab;
+    using CArgs = const __attribute__((address_space(4))) WeightArgs;   // scalar loads, as a kernel argument
+    const WeightArgs& a = *(const WeightArgs*)((CArgs*)as + p);
+    if (!a.cum) return;   // an engine without cumulative costs in a mixed group
+    if (a.stop && *a.stop) return;
+    const int N = a.N, J = a.J, KJ = a.K_loc * J;
+    const int row0 = (blockIdx.x - p * nslab) * ROWS;
+    const int nrows = min(ROWS, KJ - row0);
+    if (nrows <= 0) return;
+    const int nel = nrows * N, pitch = N | 1;
+    const int tid = threadIdx.x;
+    const double* ctl = a.control + (size_t)row0 * N;
+    double* cum = const_cast<double*>(a.cum) + (size_t)row0 * N;
+    // element f = tid + 256 k is (row, t) = (f / N, f % N): one division, then steps of 256
+    const int qN = 256 / N, rN = 256 % N;
+    const int rowA = tid / N, tA = tid % N;
+    double cv[kCumEpt], sv[kCumEpt];
+    {
+        int row = rowA, t = tA;
+#pragma unroll
+        for (int k = 0; k < kCumEpt; ++k) {
+            if (k * 256 < nel) {   // workgroup-uniform; lanes past the slab load a clamped address
+                const bool ok = tid + k * 256 < nel;
+                const int rw = ok ? row : nrows - 1, tt = ok ? t : N - 1;
+                cv[k] = ctl[(size_t)rw * N + tt];
+                sv[k] = a.state[(size_t)((row0 + rw) / J) * N + tt];
+            }
+            row += qN;
+            t += rN;
+            if (t >= N) {
+                t -= N;
+                ++row;
+            }
+        }
+    }
+    {
+        int row = rowA, t = tA;
+#pragma unroll
+        for (int k = 0; k < kCumEpt; ++k) {
+            if (k * 256 < nel && tid + k * 256 < nel) C[row * pitch + t] = sv[k] + cv[k];
+            row += qN;
+            t += rN;
+            if (t >= N) {
+                t -= N;
+                ++row;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < nrows) {
+        double* c = C + tid * pitch;
+        double acc = c[N - 1];
+        int t = N - 2;
+        for (; t >= kCumAhead - 1; t -= kCumAhead) {
+            double v[kCumAhead];
+#pragma unroll
+            for (int q = 0; q < kCumAhead; ++q) v[q] = c[t - q];
+#pragma unroll
+            for (int q = 0; q < kCumAhead; ++q) {
+                acc = v[q] + acc;
+                c[t - q] = acc;
+            }
+        }
+        for (; t >= 0; --t) {
+            acc = c[t] + acc;
+            c[t] = acc;
+        }
+    }
+    __syncthreads();
+    {
+        int row = rowA, t = tA;
+#pragma unroll
+        for (int k = 0; k < kCumEpt; ++k) {
+            if (k * 256 < nel && tid + k * 256 < nel) cum[tid + k * 256] = C[row * pitch + t];
+            row += qN;
+            t += rN;
+            if (t >= N) {
+                t -= N;
+                ++row;
+            }
+        }
+    }
+}
+
+// rows per workgroup of k_cumulative_group (its instantiation), 0: N beyond the kernel
+int cumulative_group_rows(int N) { return N <= 0 || N > 256 ? 0 : N <= 128 ? 32 : 16; }
+size_t cumulative_group_lds_bytes(int N) { return (size_t)cumulative_group_rows(N) * (N | 1) * sizeof(double); }
+
+void launch_cumulative_group(const WeightArgs* as, int engines, int J, int N, int K_loc, hipStream_t s)
+{
+    const int rows = cumulative_group_rows(N);
+    if (rows <= 0 || engines <= 0) return;
+    const int nslab = (K_loc * J + rows - 1) / rows;
+    const size_t lds = cumulative_group_lds_bytes(N);
+    if (rows == 32)
+        hipLaunchKernelGGL((k_cumulative_group<32>), dim3(nslab * engines), dim3(256), lds, s, as, nslab);
+    else
+        hipLaunchKernelGGL((k_cumulative_group<16>), dim3(nslab * engines), dim3(256), lds, s, as, nslab);
+}
+
 // delta = M u (policy_improvement.cpp:380), theta += 1.0 * delta (covariant_trajectory_policy.cpp:318-323).
 // With u_all (multi-GPU) u is first summed over the all-gathered block partials in block order.
 // One output per lane, so registers allow a deep ring: kUpdateBatch rows per batch, three

@@ -458,6 +458,13 @@ struct ReuseRowArgs {
 void launch_reuse_rows_group(const NoiseArgs& a0, const ReuseRowArgs* as, int engines, int K, int Kr, hipStream_t s);
 int weights_group_tiles(int J, int N, int K_loc);
 void launch_weights_group(const WeightArgs* as, int engines, int J, int N, int K_loc, hipStream_t s);
+// the cumulative rows (launch_cumulative's, bit for bit) of every engine of a group in one launch,
+// directly before the grouped weights launch with the same entries: an entry with cum == nullptr
+// (an engine without cumulative costs) or with its stop flag up writes nothing.  N <= 256
+// (cumulative_group_rows(N) > 0: the rows a workgroup stages in LDS, 32 up to N = 128, else 16).
+int cumulative_group_rows(int N);
+size_t cumulative_group_lds_bytes(int N);
+void launch_cumulative_group(const WeightArgs* as, int engines, int J, int N, int K_loc, hipStream_t s);
 void launch_update_group(int J, int N, const UpdateArgs* as, int engines, hipStream_t s);
 void launch_gather_max(const double* gathered, int world, int n, double* out, hipStream_t s);
 void launch_pad_fk(const DevModel& m, const double* start, const double* goal, double* pad_pos, int* pad_cf,

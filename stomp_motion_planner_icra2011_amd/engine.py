@@ -79,6 +79,11 @@ class stomp_stats(C.Structure):
                 ("collision_success_duration", C.c_double)]
 
 
+# stomp_group_create_flags' accept mask
+STOMP_GROUP_ACCEPT_STATE_TERMS = 1
+STOMP_GROUP_ACCEPT_CUMULATIVE = 2
+
+
 class stomp_group_options(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("state_terms", C.c_int32), ("compact", C.c_int32)]
 
@@ -97,6 +102,7 @@ EXPORTED = ["stomp_engine_create", "stomp_engine_destroy", "stomp_engine_last_er
             "stomp_stream_create", "stomp_stream_destroy", "stomp_group_create", "stomp_group_run",
             "stomp_group_synchronize", "stomp_group_last_error", "stomp_group_destroy", "stomp_engine_shard_mode",
             "stomp_group_optimize", "stomp_group_optimize_chunk", "stomp_group_create_with",
+            "stomp_group_create_flags",
             "stomp_engine_shard_info", "stomp_shard_decide", "stomp_engine_source_hash",
             "stomp_engine_refresh_field", "stomp_device_selftest_trig"]
 
@@ -166,6 +172,9 @@ def load_library(path: Optional[str] = None):
     l.stomp_group_create.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]
     l.stomp_group_create_with.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(stomp_group_options),
                                           C.POINTER(C.c_void_p)]
+    if hasattr(l, "stomp_group_create_flags"):   # (a variant library named by STOMP_ENGINE_LIB may predate it)
+        l.stomp_group_create_flags.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_uint32, C.c_int32,
+                                               C.POINTER(C.c_void_p)]
     l.stomp_group_run.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     l.stomp_group_synchronize.argtypes = [C.c_void_p]
     l.stomp_group_optimize.argtypes = [C.c_void_p, C.POINTER(stomp_stats), dp, C.c_int32]
@@ -452,6 +461,9 @@ class Engine:
         _check(load_library().stomp_pi_reset(self.h), self.h)
 
     def rollouts(self, which: str) -> np.ndarray:
+        """params, noise, control_costs, probabilities, cumulative_costs (engines with
+        use_cumulative_costs: the rows the last weights launch read): K_loc x J x N; state_costs:
+        K_loc x N; x_params, x_noise, x_control_costs: J x N; x_state_costs: N."""
         if which.startswith("x_"):
             shape = (self.N,) if which == "x_state_costs" else (self.J, self.N)
         else:
@@ -509,15 +521,23 @@ class EngineGroup:
     torque term, with constraints, with both and with neither); one more launch per grouped rollout
     launch prices the terms of all of them.  compact: None leaves stomp_group_optimize's compaction
     to STOMP_DEBUG_GROUP_COMPACT, False / True turn it off / on.  EngineGroup(engines) alone is
-    stomp_group_create."""
+    stomp_group_create.
+    cumulative_costs=True (stomp_group_create_flags): engines with use_cumulative_costs are accepted
+    too, mixed freely with engines without; one more launch before every grouped weights launch
+    makes the cumulative rows of all of them."""
 
-    def __init__(self, engines, state_terms: bool = False, compact: Optional[bool] = None):
+    def __init__(self, engines, state_terms: bool = False, compact: Optional[bool] = None,
+                 cumulative_costs: bool = False):
         self._h = None   # set before the call that may raise, so __del__ has nothing to free
         l = load_library()
         self.engines = list(engines)
         arr = (C.c_void_p * len(self.engines))(*[e.h.value for e in self.engines])
         h = C.c_void_p()
-        if state_terms or compact is not None:
+        if cumulative_costs:
+            accept = STOMP_GROUP_ACCEPT_CUMULATIVE | (STOMP_GROUP_ACCEPT_STATE_TERMS if state_terms else 0)
+            rc = l.stomp_group_create_flags(arr, len(self.engines), accept,
+                                            -1 if compact is None else (1 if compact else 0), C.byref(h))
+        elif state_terms or compact is not None:
             opt = stomp_group_options(C.sizeof(stomp_group_options), 1 if state_terms else 0,
                                       -1 if compact is None else (1 if compact else 0))
             rc = l.stomp_group_create_with(arr, len(self.engines), C.byref(opt), C.byref(h))

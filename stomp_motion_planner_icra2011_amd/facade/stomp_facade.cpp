@@ -185,7 +185,7 @@ bool StompOptimizer::finishOptimize(const stomp_stats& st)
 
 // optimize() for several optimizers at once: their engines as one group (stomp_group_optimize),
 // every problem stopping on its own (with or without reused rollouts: one count for the batch;
-// optimizers with the torque term or path constraints plan in the group too, state_terms)
+// optimizers with the torque term, path constraints or use_cumulative_costs plan in the group too)
 bool StompOptimizer::optimizeBatch(const std::vector<StompOptimizer*>& optimizers)
 {
     if (optimizers.empty()) return true;
@@ -202,8 +202,8 @@ bool StompOptimizer::optimizeBatch(const std::vector<StompOptimizer*>& optimizer
         stride = std::max(stride, o->parameters_->max_iterations);
     }
     stomp_group* g = nullptr;
-    const stomp_group_options options = {(int32_t)sizeof(stomp_group_options), 1, -1};
-    if (stomp_group_create_with(engines.data(), (int32_t)engines.size(), &options, &g) != 0) {
+    if (stomp_group_create_flags(engines.data(), (int32_t)engines.size(),
+                                 STOMP_GROUP_ACCEPT_STATE_TERMS | STOMP_GROUP_ACCEPT_CUMULATIVE, -1, &g) != 0) {
         first->error_ = stomp_last_error();
         return false;
     }

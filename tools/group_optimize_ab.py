@@ -17,8 +17,13 @@ a reset generateRollouts state too, so that all of them optimize the same thing.
 chosen through the options).  --ways picks the ways to run (a library without
 stomp_group_create_with, or one that refuses terms in groups, runs `--ways a` alone).
 
+--cumulative sets use_cumulative_costs (the reference's default) on every problem; the groups are
+then created accepting cumulative costs (stomp_group_create_flags), with or without the terms above.
+A library from before groups took cumulative costs runs `--ways a` alone.
+
     python tools/group_optimize_ab.py [--out FILE] [--problems 64] [--repeats 5] [--reused 0]
-                                      [--upright] [--upright-tolerance 0.2] [--torque-weight 0] [--ways abc]
+                                      [--upright] [--upright-tolerance 0.2] [--torque-weight 0] [--cumulative]
+                                      [--ways abc]
 """
 import argparse
 import os
@@ -48,6 +53,7 @@ def main():
     ap.add_argument("--upright", action="store_true", help="the reference's upright constraint on every problem")
     ap.add_argument("--upright-tolerance", type=float, default=None, help="roll / pitch tolerance (rad) in its place")
     ap.add_argument("--torque-weight", type=float, default=0.0, help="torque_cost_weight of every problem")
+    ap.add_argument("--cumulative", action="store_true", help="use_cumulative_costs on every problem")
     ap.add_argument("--ways", default="abc", help="which of a, b, c to run")
     args = ap.parse_args()
     P = args.problems
@@ -60,6 +66,8 @@ def main():
         extra["orientation_constraints"] = [oc]
     if args.torque_weight:
         extra["torque_cost_weight"] = args.torque_weight
+    if args.cumulative:
+        extra["use_cumulative_costs"] = True
     base = pb.make_problem(dof=7, waypoints=100, grid_n=args.grid, num_rollouts=args.rollouts,
                            num_reused_rollouts=args.reused, build_grid=False)
     sdf = eng.DeviceBuffer(2 * args.grid ** 3, device=0)
@@ -75,7 +83,12 @@ def main():
                             max_iterations_after_collision_free=2, **extra)
         engines.append(eng.Engine(p, device=0, sdf_device_ptr=sdf.ptr, stream=stream.ptr))
     group_all = group_compact = None
-    if terms:
+    if args.cumulative:
+        if "b" in args.ways:
+            group_all = eng.EngineGroup(engines, state_terms=terms, compact=False, cumulative_costs=True)
+        if "c" in args.ways:
+            group_compact = eng.EngineGroup(engines, state_terms=terms, compact=True, cumulative_costs=True)
+    elif terms:
         if "b" in args.ways:
             group_all = eng.EngineGroup(engines, state_terms=True, compact=False)
         if "c" in args.ways:
@@ -108,6 +121,8 @@ def main():
         reused += f", upright constraint (roll / pitch within {tol:g} rad)"
     if args.torque_weight:
         reused += f", torque_cost_weight = {args.torque_weight:g}"
+    if args.cumulative:
+        reused += ", cumulative costs"
     lines = [f"group_optimize_ab: {P} problems, K = {args.rollouts}{reused}, {args.grid}^3, max_iterations = "
              f"{args.max_iterations}, max_iterations_after_collision_free = 2, {args.repeats} repeats after one warm-up"]
     reference = None
