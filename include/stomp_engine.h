@@ -210,6 +210,26 @@ const char* stomp_engine_source_hash(void);
  * STOMP_E_UNSUPPORTED. */
 int stomp_engine_refresh_field(stomp_engine* e);
 
+/* Puts a live engine onto a new planning request: start and goal (J doubles each) and the noise
+ * seed (to keep the seed, pass the old one).  Afterwards the engine is observably the engine
+ * stomp_engine_create would return for the same descriptor with start, goal and seed replaced (and,
+ * after the caller rebuilt its device field in place and called stomp_engine_refresh_field, with
+ * that field): theta, last_trajectory and best_trajectory are theta_0 (setToMinControlCost, the
+ * bits creation computes), get_pad_positions and the padding-collision flag of iteration_member 0
+ * are the new poses', and every later iterate / run / optimize / eval / stomp_pi_* call gives
+ * what it gives on the fresh engine, bit for bit.  Whatever iteration state the engine held is
+ * dropped: a pending noiseless rollout, rows made ahead, the reuse state (the next iteration
+ * generates every rollout) and the step API's state as stomp_pi_reset drops it.  The matrices, the
+ * model, the field, the timing accumulators, the stream and group membership are not changed.
+ * The device work is one launch on the engine's stream, ordered after everything enqueued before
+ * (an earlier refresh_field included), and one read-back of the padding-collision flag: the call
+ * waits for the stream.  NULL engine, start or goal, or a value that is not finite:
+ * STOMP_E_INVALID, checked before any engine or device is touched (a machine without a GPU can make
+ * these calls).  A sharded engine (world_size > 1): STOMP_E_UNSUPPORTED, its ranks would have to
+ * retarget in lockstep.  A refused call leaves the engine untouched.
+ * stomp_group_retarget (declared with the groups below) does the same for every engine of a group. */
+int stomp_engine_retarget(stomp_engine* e, const double* start, const double* goal, uint64_t seed);
+
 int stomp_engine_get_theta(stomp_engine* e, double* theta);
 int stomp_engine_set_theta(stomp_engine* e, const double* theta);
 
@@ -447,6 +467,17 @@ int stomp_group_synchronize(stomp_group* g);
 #define STOMP_GROUP_OPTIMIZE_CHUNK 8
 int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_iteration, int32_t costs_stride);
 int32_t stomp_group_optimize_chunk(void);
+/* stomp_engine_retarget for every engine of the group at once: starts and goals are P x J (row p
+ * for engine p), seeds P values.  One launch retargets the whole group and one read-back fetches
+ * the P padding-collision flags; the group's own copy of every engine's model carries the new flag
+ * before the next grouped launch.  Each engine is then the freshly created engine of its new
+ * problem, so engines that left stomp_group_optimize at different iterations are in one iteration
+ * state again: stomp_group_run and stomp_group_optimize accept them with any first iteration.
+ * (An engine of a group may also be retargeted on its own with stomp_engine_retarget; the group
+ * picks its new flag up at its next call.)  NULL group or array, or a value that is not finite:
+ * STOMP_E_INVALID before any engine or device is touched; a refused call leaves every engine
+ * untouched. */
+int stomp_group_retarget(stomp_group* g, const double* starts, const double* goals, const uint64_t* seeds);
 const char* stomp_group_last_error(const stomp_group* g);
 void stomp_group_destroy(stomp_group* g);
 

@@ -427,6 +427,22 @@ public:
     // into its trajectory.  On failure returns false with the reason in the first optimizer's
     // lastError().
     static bool optimizeBatch(const std::vector<StompOptimizer*>& optimizers);
+    // The live optimizer onto a new planning request (stomp_engine_retarget): start and goal of
+    // num_joints entries and the noise seed (parameters().seed keeps it).  Afterwards the optimizer
+    // is the one constructed for a trajectory with that start and goal: its engine restarts from
+    // the minimum-control-cost trajectory, the caller's trajectory object holds the new start and
+    // goal (its free waypoints are written by the next optimize()), and the statistics and the
+    // last* accessors are those of a freshly constructed optimizer.  A scene rebuilt in place in a
+    // device field comes first: stomp_engine_refresh_field(engine()), then retarget.  false with
+    // lastError() when refused (sizes, values that are not finite); nothing is changed then.
+    bool retarget(const std::vector<double>& start, const std::vector<double>& goal, uint64_t seed);
+    // retarget() for several optimizers at once (starts[i], goals[i], seeds[i] for optimizers[i]):
+    // their engines as one group, which retargetBatch obtains as optimizeBatch does, retargeted in
+    // one launch (stomp_group_retarget).  On failure returns false with the reason in the first
+    // optimizer's lastError() and no optimizer changed.
+    static bool retargetBatch(const std::vector<StompOptimizer*>& optimizers,
+                              const std::vector<std::vector<double>>& starts,
+                              const std::vector<std::vector<double>>& goals, const std::vector<uint64_t>& seeds);
     const STOMPStatistics& getStatistics() const { return stats_; }
 
     // Task (stomp_optimizer.cpp:1063-1165, 1167-1182)
@@ -477,6 +493,7 @@ private:
     friend class CovariantTrajectoryPolicy;
     bool check(int rc);
     bool finishOptimize(const stomp_stats& st);
+    void followRetarget(const std::vector<double>& start, const std::vector<double>& goal, uint64_t seed);
     // an engine of the same problem with other rollout counts / cumulative-cost setting (the
     // device rollout set of a PolicyImprovement that asks for them); nullptr and err on failure
     stomp_engine* createSibling(int num_rollouts, int num_reused_rollouts, bool use_cumulative_costs,

@@ -39,6 +39,7 @@ void release(stomp_engine* e)
     if (e->h_cf) hipHostFree(e->h_cf);
     if (e->h_track) hipHostFree(e->h_track);
     if (e->h_stall) hipHostFree(e->h_stall);
+    if (e->h_rt) hipHostFree(e->h_rt);
     for (auto& r : e->coll_ring)
         if (r.ev) hipEventDestroy(r.ev);
     comm_destroy(e);

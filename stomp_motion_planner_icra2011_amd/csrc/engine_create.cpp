@@ -157,6 +157,7 @@ void oc_nominal_inverse(const double* q, double* O)
 // the spheres as the kernels hold them, each published frame slot's first sphere, the joint limits.
 struct HostTables {
     std::vector<double> LT, MT, QT;
+    std::vector<double> Rb, RinvT;   // stomp_engine_retarget's tables (engine_internal.h)
     std::vector<DevSegment> segs;
     std::vector<DevSphere> sph;
     std::vector<int> slot_sph, has_lim;
@@ -336,6 +337,17 @@ int setup_tables(stomp_engine* e, const stomp_engine_desc* d, HostTables& t)
         for (int i = 0; i < N; ++i)
             for (int k = 0; k < N; ++k)
                 t.QT[((size_t)j * N + k) * N + i] = e->su.Qinv[((size_t)j * N + i) * N + k];
+    // what theta_0 reads (compute_setup, setToMinControlCost): the start-side and goal-side
+    // boundary rows of R over the free columns, and R^-1 with lane i's entries consecutive
+    t.Rb.resize((size_t)2 * kPad * N);
+    t.RinvT.resize((size_t)N * N);
+    for (int i = 0; i < kPad; ++i)
+        for (int c = 0; c < N; ++c) {
+            t.Rb[(size_t)i * N + c] = e->su.Rall[(size_t)i * e->Nall + (c + kPad)];
+            t.Rb[(size_t)(kPad + i) * N + c] = e->su.Rall[(size_t)(N + kPad + i) * e->Nall + (c + kPad)];
+        }
+    for (int i = 0; i < N; ++i)
+        for (int k = 0; k < N; ++k) t.RinvT[(size_t)k * N + i] = e->su.Rinv[(size_t)i * N + k];
     t.segs.resize(e->nseg);
     for (int s = 0; s < e->nseg; ++s) {
         const stomp_segment& g = d->segments[s];
@@ -413,6 +425,8 @@ int alloc_buffers(stomp_engine* e, const stomp_engine_desc* d, const HostTables&
     if (int rc = upload(e, &e->d_QT, tab.QT.data(), tab.QT.size())) return rc;
     if (int rc = upload(e, &e->d_LT, tab.LT.data(), tab.LT.size())) return rc;
     if (int rc = upload(e, &e->d_MT, tab.MT.data(), tab.MT.size())) return rc;
+    if (int rc = upload(e, &e->d_Rb, tab.Rb.data(), tab.Rb.size())) return rc;
+    if (int rc = upload(e, &e->d_RinvT, tab.RinvT.data(), tab.RinvT.size())) return rc;
     if (int rc = upload(e, &e->d_theta, e->su.theta.data(), e->su.theta.size())) return rc;
     if (int rc = upload(e, &e->d_start, e->start.data(), e->start.size())) return rc;
     if (int rc = upload(e, &e->d_goal, e->goal.data(), e->goal.size())) return rc;

@@ -22,6 +22,9 @@
 // use_cumulative_costs, mixed freely with engines without: every grouped weights launch is then
 // preceded, inside the same timed scope, by one launch of the cumulative rows of all of its
 // engines (k_cumulative_group; an engine without cumulative costs has no workgroup that writes).
+// stomp_group_retarget puts every engine of the group onto a new start, goal and seed in one launch
+// and one read-back (engine_retarget.cpp); the launch also writes the padding-collision flags of
+// the group's own DevModel list, which the grouped launches of a run and a synchronize read.
 #include "engine_internal.h"
 
 #include <algorithm>
@@ -54,6 +57,11 @@ struct stomp_group {
     int* h_mirror = nullptr;              // [2][P][2]
     TrackArgs* d_track_all = nullptr;     // [P]
     hipEvent_t opt_ev[2] = {nullptr, nullptr};
+    // stomp_group_retarget: one call's staging (pinned and device); the padding-collision flag each
+    // entry of d_models holds, so that an engine retargeted on its own (stomp_engine_retarget knows
+    // no group) gets its entry refreshed before the next launch that reads the list
+    unsigned char *h_rt = nullptr, *d_rt = nullptr;
+    std::vector<int> pad_flags;
     std::string err;
 };
 
@@ -174,6 +182,21 @@ TermsArgs terms_args(const stomp_engine* e, const CostArgs& ca)
     }
     return ta;
 }
+
+// d_models' padding-collision flags brought up to the engines' own (changed by a
+// stomp_engine_retarget on a member): rare, so a wait and a blocking 4-byte copy per changed entry
+int sync_model_flags(stomp_group* g)
+{
+    for (size_t p = 0; p < g->e.size(); ++p) {
+        if (g->pad_flags[p] == g->e[p]->pad_collision) continue;
+        const int f = g->e[p]->pad_collision;
+        if (hipStreamSynchronize(g->stream) != hipSuccess ||
+            hipMemcpy(&g->d_models[p].pad_collision, &f, sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+            return gfail(g, STOMP_E_DEVICE, "group model refresh failed");
+        g->pad_flags[p] = f;
+    }
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -195,6 +218,8 @@ void stomp_group_destroy(stomp_group* g)
     if (g->d_mirror) hipFree(g->d_mirror);
     if (g->h_mirror) hipHostFree(g->h_mirror);
     if (g->d_track_all) hipFree(g->d_track_all);
+    if (g->d_rt) hipFree(g->d_rt);
+    if (g->h_rt) hipHostFree(g->h_rt);
     for (hipEvent_t ev : g->opt_ev)
         if (ev) hipEventDestroy(ev);
     delete g;
@@ -276,6 +301,7 @@ int stomp_group_create_flags(stomp_engine* const* engines, int32_t n, uint32_t a
     for (int p = 0; p < n; ++p) g->ncum += engines[p]->use_cum ? 1 : 0;
     std::vector<DevModel> ms(n);
     for (int p = 0; p < n; ++p) ms[p] = engines[p]->model;
+    for (int p = 0; p < n; ++p) g->pad_flags.push_back(engines[p]->pad_collision);
     if (hipMalloc(&g->d_models, sizeof(DevModel) * n) != hipSuccess ||
         hipMemcpy(g->d_models, ms.data(), sizeof(DevModel) * n, hipMemcpyHostToDevice) != hipSuccess ||
         hipEventCreateWithFlags(&g->staged, hipEventDisableTiming) != hipSuccess) {
@@ -311,6 +337,28 @@ int stomp_group_create_flags(stomp_engine* const* engines, int32_t n, uint32_t a
     return 0;
 }
 
+int stomp_group_retarget(stomp_group* g, const double* starts, const double* goals, const uint64_t* seeds)
+{
+    // all of this before any engine or device is touched
+    if (!g) return gfail(nullptr, STOMP_E_INVALID, "null group");
+    if (!starts || !goals || !seeds) return gfail(nullptr, STOMP_E_INVALID, "retarget: null starts, goals or seeds");
+    const int P = (int)g->e.size();
+    if (int rc = retarget_validate(g->e.data(), P, starts, goals)) return gfail(g, rc, std::string(g_last_error).c_str());
+    DeviceGuard dg(g->device);
+    if (!g->d_rt) {
+        const size_t bytes = retarget_stage_bytes(P, g->e[0]->J);
+        if ((!g->h_rt && hipHostMalloc((void**)&g->h_rt, bytes) != hipSuccess) ||
+            hipMalloc((void**)&g->d_rt, bytes) != hipSuccess)
+            return gfail(g, STOMP_E_DEVICE, "group retarget allocation failed");
+    }
+    // one launch and one read-back for the whole group; every engine leaves in the freshly created
+    // iteration state, whichever iteration its optimize loop stopped at
+    if (int rc = retarget_engines(g->e.data(), P, starts, goals, seeds, g->h_rt, g->d_rt, g->d_models))
+        return gfail(g, rc, std::string(g_last_error).c_str());
+    for (int p = 0; p < P; ++p) g->pad_flags[p] = g->e[p]->pad_collision;
+    return 0;
+}
+
 const char* stomp_group_last_error(const stomp_group* g) { return g ? g->err.c_str() : g_last_error.c_str(); }
 
 int stomp_group_run(stomp_group* g, int32_t first, int32_t count)
@@ -333,6 +381,7 @@ int stomp_group_run(stomp_group* g, int32_t first, int32_t count)
                  szr = e0->Kr > 0 ? align256(sizeof(ReuseRowArgs) * P) : 0,
                  szt = g->nterms > 0 ? align256(sizeof(TermsArgs) * P) : 0, per = szc + szw + szu + szr + szt;
     const size_t bytes = per * (size_t)count;
+    if (int rc = sync_model_flags(g)) return rc;
     if (g->staged && hipEventSynchronize(g->staged) != hipSuccess)   // h_args free again
         return gfail(g, STOMP_E_DEVICE, "group staging wait failed");
     if (bytes > g->h_cap) {
@@ -424,6 +473,7 @@ int stomp_group_synchronize(stomp_group* g)
     if (!g) return gfail(nullptr, STOMP_E_INVALID, "null group");
     DeviceGuard dg(g->device);
     const int P = (int)g->e.size();
+    if (int rc = sync_model_flags(g)) return rc;
     bool all = true;
     for (stomp_engine* e : g->e) all = all && e->pending_member >= 0 && !e->tracking;
     if (all) {

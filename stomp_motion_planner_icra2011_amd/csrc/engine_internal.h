@@ -6,6 +6,7 @@
 //   engine_create.cpp    descriptor validation and stomp_engine_create's stages
 //   engine_exchange.cpp  the in-process group, the RCCL path, the collectives, calibration
 //   engine_group.cpp     stomp_group
+//   engine_retarget.cpp  stomp_engine_retarget and the part of it stomp_group_retarget shares
 //   sdf_build.cpp        the distance-field builders (does not include this header)
 #pragma once
 
@@ -148,6 +149,11 @@ struct stomp_engine {
     int grid_n[3] = {0, 0, 0};
     int* d_pad_cf = nullptr;
     int pad_collision = 0;
+    // stomp_engine_retarget: the boundary rows of R cut to the free columns [12][N] and R^-1
+    // transposed [N][N] (uploaded at creation), the engine's own staging of one call (pinned and
+    // device, allocated by its first call; a group stages its engines in buffers of its own)
+    double *d_Rb = nullptr, *d_RinvT = nullptr;
+    unsigned char *h_rt = nullptr, *d_rt = nullptr;
     bool reused_next = false, extra_added = false;
     int pending_member = -1;   // iteration_ of a noiseless rollout of theta not evaluated yet
     double *d_mm = nullptr, *d_psum_part = nullptr, *d_psum_all = nullptr, *d_u_part = nullptr, *d_u_all = nullptr;
@@ -227,6 +233,18 @@ int fail(stomp_engine* e, int code, const char* fmt, ...);   // (sdf_build.cpp d
 void release(stomp_engine* e);
 void launch_noiseless(stomp_engine* e, int member);
 int run_reuse(stomp_engine* e);
+
+// ---- engine_retarget.cpp
+// One call's staging for P engines of J joints: [P] RetargetArgs, [P][2][J] vectors, [P] flags.
+size_t retarget_stage_bytes(int P, int J);
+// everything stomp_engine_retarget / stomp_group_retarget refuse before an engine or a device is
+// touched (es: the P engines, none null; seeds may be null: every engine keeps its own)
+int retarget_validate(stomp_engine* const* es, int P, const double* starts, const double* goals);
+// the P engines (one shape, one stream, validated) onto their new problems in one launch and one
+// read-back of the P padding-collision flags; h / d: staging of retarget_stage_bytes(P, J), free
+// for this call; d_models: the group's DevModel list whose flags the launch also writes, or null
+int retarget_engines(stomp_engine* const* es, int P, const double* starts, const double* goals,
+                     const uint64_t* seeds, unsigned char* h, unsigned char* d, DevModel* d_models);
 
 // ---- engine_exchange.cpp
 extern const bool kWithRccl;

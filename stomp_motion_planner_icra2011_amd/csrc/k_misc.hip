@@ -46,12 +46,10 @@ const char* lds_opt_in_error()
 
 // padding-point sphere positions: iteration-0 full FK of start (rows 0..5) and goal (rows 6..11)
 // (stomp_optimizer.cpp:626-630 with JntToCartFull; padding rows of the group trajectory hold
-// start/goal, stomp_trajectory.cpp:94-107)
-__global__ void k_pad_fk(DevModel m, const double* start, const double* goal, double* pad_pos, int* pad_cf)
+// start/goal, stomp_trajectory.cpp:94-107).  pad_fk_side: one side (0: start, 1: goal) of the pose
+// q; returns whether a sphere collides
+__device__ __forceinline__ bool pad_fk_side(const DevModel& m, const double* q, int side, double* pad_pos)
 {
-    const int side = threadIdx.x;
-    if (side > 1) return;
-    const double* q = side ? goal : start;
     Frame C, S0, S1;
     bool col = false;
     for (int op = 0; op < m.nops; ++op) {
@@ -70,7 +68,66 @@ __global__ void k_pad_fk(DevModel m, const double* start, const double* goal, do
                 for (int c = 0; c < 3; ++c) pad_pos[((size_t)(side * 6 + row) * m.S + s) * 3 + c] = p[c];
         }
     }
-    if (col) atomicOr(pad_cf, 1);
+    return col;
+}
+
+__global__ void k_pad_fk(DevModel m, const double* start, const double* goal, double* pad_pos, int* pad_cf)
+{
+    const int side = threadIdx.x;
+    if (side > 1) return;
+    if (pad_fk_side(m, side ? goal : start, side, pad_pos)) atomicOr(pad_cf, 1);
+}
+
+// stomp_engine_retarget / stomp_group_retarget (RetargetArgs): grid (J + 1, engines), N <= 256
+// lanes per workgroup.  Workgroup d < J makes joint d's row of theta_0 as compute_setup does
+// (setup.cpp, setToMinControlCost): lin[c] by lane c through LDS, both sums i-ascending, then
+// theta[d][i] by lane i, k-ascending, reading Rinv[i][k] itself (RinvT[k][i]: R^-1 is not bitwise
+// symmetric).  Workgroup J is the padding FK on the new vectors in the staging buffer: the other
+// workgroups of the launch are writing start / goal meanwhile.
+__global__ __launch_bounds__(256) void k_retarget(const RetargetArgs* __restrict__ as, int J, int N)
+{
+    const RetargetArgs& a = as[blockIdx.y];
+    __shared__ double lin[256];
+    __shared__ int col[2];
+    if ((int)blockIdx.x == J) {
+        const int side = threadIdx.x;
+        if (side < 2) col[side] = pad_fk_side(a.model, a.stage + (size_t)side * J, side, a.pad_pos) ? 1 : 0;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int f = col[0] | col[1];
+            *a.pad_cf = f;
+            if (a.model_flag) *a.model_flag = f;
+            *a.flag_out = f;
+        }
+        return;
+    }
+    const int d = blockIdx.x, c = threadIdx.x;
+    const double sd = a.stage[d], gd = a.stage[J + d];
+    if (c < N) {
+        double x = 0.0;
+        for (int i = 0; i < 6; ++i) x += sd * a.Rb[(size_t)i * N + c];
+        double y = 0.0;
+        for (int i = 0; i < 6; ++i) y += gd * a.Rb[(size_t)(6 + i) * N + c];
+        lin[c] = (x + y) * 2.0;
+    }
+    __syncthreads();
+    if (c < N) {
+        double s = 0.0;
+        for (int k = 0; k < N; ++k) s += (-0.5 * a.RinvT[(size_t)k * N + c]) * lin[k];
+        const size_t o = (size_t)d * N + c;
+        a.theta[o] = s;
+        a.last_traj[o] = s;
+        a.best_traj[o] = s;
+    }
+    if (c == 0) {
+        a.start[d] = sd;
+        a.goal[d] = gd;
+    }
+}
+
+void launch_retarget(const RetargetArgs* as, int engines, int J, int N, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_retarget, dim3(J + 1, engines), dim3(256), 0, s, as, J, N);
 }
 
 __global__ void k_gather_max(const double* g, int world, int n, double* out)

@@ -469,6 +469,28 @@ void launch_update_group(int J, int N, const UpdateArgs* as, int engines, hipStr
 void launch_gather_max(const double* gathered, int world, int n, double* out, hipStream_t s);
 void launch_pad_fk(const DevModel& m, const double* start, const double* goal, double* pad_pos, int* pad_cf,
                    hipStream_t s);
+// A live engine put onto a new problem (stomp_engine_retarget / stomp_group_retarget): what
+// creation derives from the start and goal vectors, remade on the device.  One entry per engine in
+// device memory; engine p of the launch gets J workgroups for theta_0 (compute_setup's
+// setToMinControlCost, the same operations in the same order) and one for the padding rows' FK
+// (k_pad_fk's body on the engine's own model).
+struct RetargetArgs {
+    DevModel model;             // the engine's model (its tables and field; pad_collision not read)
+    const double* stage;        // [2][J] the new start, then the new goal (the call's staging buffer:
+                                // the padding FK reads them here, never start / goal below)
+    const double* Rb;           // [12][N] rows 0..5 and N + 6..N + 11 of R, cut to the free columns
+    const double* RinvT;        // [N(k)][N(i)] R^-1 transposed: lane i reads consecutive addresses
+    double* theta;              // [J][N] theta_0, also written to last_traj and best_traj
+    double* last_traj;
+    double* best_traj;
+    double* start;              // [J]
+    double* goal;               // [J]
+    double* pad_pos;            // [12][S][3]
+    int* pad_cf;                // the engine's padding-collision flag (stored, not or-ed)
+    int* model_flag;            // pad_collision of the engine's DevModel in a group's list, or null
+    int* flag_out;              // the call's read-back slot of this engine
+};
+void launch_retarget(const RetargetArgs* as, int engines, int J, int N, hipStream_t s);
 // src_*: the previous iteration's rows (ranked, copied from); params / noise / state: this
 // iteration's rows K_gen.. (written).  The two row sets must be distinct buffers (the copy has no
 // staging pass); returns -1 without launching when they alias, -2 when one candidate's cost rows

@@ -6,6 +6,7 @@ constructor raises.  The CPU oracle lives under oracle/ and is test-only.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import os
 from typing import Optional
 
@@ -104,7 +105,8 @@ EXPORTED = ["stomp_engine_create", "stomp_engine_destroy", "stomp_engine_last_er
             "stomp_group_optimize", "stomp_group_optimize_chunk", "stomp_group_create_with",
             "stomp_group_create_flags",
             "stomp_engine_shard_info", "stomp_shard_decide", "stomp_engine_source_hash",
-            "stomp_engine_refresh_field", "stomp_device_selftest_trig"]
+            "stomp_engine_refresh_field", "stomp_device_selftest_trig", "stomp_engine_retarget",
+            "stomp_group_retarget"]
 
 _lib = None
 
@@ -139,6 +141,9 @@ def load_library(path: Optional[str] = None):
     l.stomp_last_error.restype = C.c_char_p
     l.stomp_engine_get_theta.argtypes = [P, dp]
     l.stomp_engine_refresh_field.argtypes = [P]
+    if hasattr(l, "stomp_engine_retarget"):   # (a variant library named by STOMP_ENGINE_LIB may predate them)
+        l.stomp_engine_retarget.argtypes = [P, dp, dp, C.c_uint64]
+        l.stomp_group_retarget.argtypes = [C.c_void_p, dp, dp, C.POINTER(C.c_uint64)]
     l.stomp_engine_set_theta.argtypes = [P, dp]
     l.stomp_engine_iterate.argtypes = [P, C.c_int32, C.POINTER(stomp_iter_out)]
     l.stomp_engine_run.argtypes = [P, C.c_int32, C.c_int32]
@@ -392,6 +397,26 @@ class Engine:
         """stomp_engine_refresh_field: the caller rebuilt its device field in place."""
         _check(load_library().stomp_engine_refresh_field(self.h), self.h)
 
+    def retarget(self, start, goal, seed: Optional[int] = None):
+        """stomp_engine_retarget: the live engine onto a new start, goal and seed (None keeps the
+        engine's seed).  Afterwards it is the engine Engine(problem') would be for problem' =
+        dataclasses.replace(problem, start=..., goal=..., seed=...), which self.problem becomes; the
+        iteration state it held is dropped.  A refused call raises and changes nothing."""
+        s = np.ascontiguousarray(start, np.float64).reshape(-1)
+        g = np.ascontiguousarray(goal, np.float64).reshape(-1)
+        if s.shape != (self.J,) or g.shape != (self.J,):
+            raise ValueError(f"start and goal must hold {self.J} values")
+        seed = int(self.problem.seed if seed is None else seed)
+        _check(load_library().stomp_engine_retarget(self.h, _dp(s), _dp(g), C.c_uint64(seed)), self.h)
+        self._follow(s, g, seed)
+
+    def _follow(self, start, goal, seed):
+        """the Python side of a retarget: the problem attribute and the vectors the descriptor names"""
+        # fresh arrays: the old ones may be the caller's problem's own
+        self._start, self._goal = np.array(start, np.float64), np.array(goal, np.float64)
+        self._desc.start, self._desc.goal, self._desc.seed = _dp(self._start), _dp(self._goal), seed
+        self.problem = dataclasses.replace(self.problem, start=self._start.copy(), goal=self._goal.copy(), seed=seed)
+
     def execute(self, params, iteration_member: int = 1):
         prm = np.ascontiguousarray(params, np.float64)
         single = prm.ndim == 2
@@ -581,6 +606,27 @@ class EngineGroup:
         costs = np.zeros((n, max(costs_stride, 1)))
         self._check(load_library().stomp_group_optimize(self._h, st, _dp(costs), costs_stride))
         return [(st[i], costs[i, : st[i].iterations].copy()) for i in range(n)]
+
+    def retarget(self, starts, goals, seeds=None):
+        """stomp_group_retarget: every engine onto its new start, goal and seed (rows of starts /
+        goals, P x J; seeds None keeps every engine's seed) in one launch.  Each engine is then the
+        freshly created engine of its new problem, so engines that left optimize() at different
+        iterations run in lockstep again; every engine's problem attribute follows."""
+        n = len(self.engines)
+        J = self.engines[0].J
+        s = np.ascontiguousarray(starts, np.float64).reshape(-1)
+        g = np.ascontiguousarray(goals, np.float64).reshape(-1)
+        if s.shape != (n * J,) or g.shape != (n * J,):
+            raise ValueError(f"starts and goals must be {n} x {J}")
+        if seeds is None:
+            seeds = [e.problem.seed for e in self.engines]
+        sd = np.array([int(v) for v in seeds], np.uint64)
+        if sd.shape != (n,):
+            raise ValueError(f"seeds must hold {n} values")
+        self._check(load_library().stomp_group_retarget(self._h, _dp(s), _dp(g),
+                                                        sd.ctypes.data_as(C.POINTER(C.c_uint64))))
+        for p, e in enumerate(self.engines):
+            e._follow(s[p * J:(p + 1) * J], g[p * J:(p + 1) * J], int(sd[p]))
 
     def close(self):
         if self._h is not None and self._h.value:

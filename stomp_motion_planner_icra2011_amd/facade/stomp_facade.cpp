@@ -225,6 +225,75 @@ bool StompOptimizer::optimizeBatch(const std::vector<StompOptimizer*>& optimizer
     return true;
 }
 
+// the facade's side of a retarget: the descriptor's copies (createSibling reads them), the caller's
+// trajectory object, and the statistics / last* accessors of a freshly constructed optimizer
+void StompOptimizer::followRetarget(const std::vector<double>& start, const std::vector<double>& goal, uint64_t seed)
+{
+    std::copy(start.begin(), start.end(), start_.begin());   // in place: desc_ points at them
+    std::copy(goal.begin(), goal.end(), goal_.begin());
+    desc_.seed = seed;
+    trajectory_->start = start;
+    trajectory_->goal = goal;
+    stats_ = STOMPStatistics();
+    last_cost_ = 0.0;
+    last_cf_ = false;
+    last_cs_ = true;
+}
+
+bool StompOptimizer::retarget(const std::vector<double>& start, const std::vector<double>& goal, uint64_t seed)
+{
+    if (!engine_) return false;
+    if ((int)start.size() != J_ || (int)goal.size() != J_) {
+        error_ = "retarget: start and goal must have num_joints entries";
+        return false;
+    }
+    if (!check(stomp_engine_retarget(engine_, start.data(), goal.data(), seed))) return false;
+    followRetarget(start, goal, seed);
+    return true;
+}
+
+bool StompOptimizer::retargetBatch(const std::vector<StompOptimizer*>& optimizers,
+                                   const std::vector<std::vector<double>>& starts,
+                                   const std::vector<std::vector<double>>& goals, const std::vector<uint64_t>& seeds)
+{
+    if (optimizers.empty()) return true;
+    StompOptimizer* first = optimizers[0];
+    if (!first) return false;
+    const size_t P = optimizers.size();
+    if (starts.size() != P || goals.size() != P || seeds.size() != P) {
+        first->error_ = "retargetBatch: one start, goal and seed per optimizer";
+        return false;
+    }
+    std::vector<stomp_engine*> engines;
+    std::vector<double> s, g;
+    for (size_t p = 0; p < P; ++p) {
+        StompOptimizer* o = optimizers[p];
+        if (!o || !o->engine_) {
+            first->error_ = "retargetBatch: an optimizer without an engine";
+            return false;
+        }
+        if ((int)starts[p].size() != o->J_ || (int)goals[p].size() != o->J_) {
+            first->error_ = "retargetBatch: start and goal must have num_joints entries";
+            return false;
+        }
+        engines.push_back(o->engine_);
+        s.insert(s.end(), starts[p].begin(), starts[p].end());
+        g.insert(g.end(), goals[p].begin(), goals[p].end());
+    }
+    stomp_group* grp = nullptr;
+    if (stomp_group_create_flags(engines.data(), (int32_t)P, STOMP_GROUP_ACCEPT_STATE_TERMS | STOMP_GROUP_ACCEPT_CUMULATIVE,
+                                 -1, &grp) != 0) {
+        first->error_ = stomp_last_error();
+        return false;
+    }
+    const int rc = stomp_group_retarget(grp, s.data(), g.data(), seeds.data());
+    if (rc != 0) first->error_ = stomp_group_last_error(grp);
+    stomp_group_destroy(grp);
+    if (rc != 0) return false;
+    for (size_t p = 0; p < P; ++p) optimizers[p]->followRetarget(starts[p], goals[p], seeds[p]);
+    return true;
+}
+
 bool StompOptimizer::initialize(int num_time_steps)
 {
     if (!engine_) return false;

@@ -1,0 +1,70 @@
+"""GPU: StompOptimizer::retargetBatch of the C++ facade -- three optimizers on one shared stream plan
+their problems as one engine group (optimizeBatch), are retargeted onto new starts, goals and seeds
+in one launch (stomp_group_retarget), and plan again.  The second plan's statistics, cost history,
+torques and best trajectory equal the CPU oracle's optimize() of the new problems, bit for bit; the
+driver itself checks that every optimizer was in the freshly constructed state in between and that
+a refused batch changes nothing (tests/facade_retarget_driver.cpp)."""
+import dataclasses
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle import pyoracle as po
+from tests import facade_util as fu
+from tests.test_gpu_group_optimize import INT_STATS, recipe
+
+pytestmark = pytest.mark.gpu
+
+
+def build_retarget_driver(directory):
+    """facade_util.build_driver's compile line for tests/facade_retarget_driver.cpp."""
+    from stomp_motion_planner_icra2011_amd import _build
+    lib = _build.build_facade()
+    exe = os.path.join(directory, "facade_retarget_driver")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-I", os.path.join(fu.ROOT, "include"),
+                           os.path.join(fu.ROOT, "tests", "facade_retarget_driver.cpp"), "-o", exe, lib, _build.LIB,
+                           "-Wl,-rpath," + fu.PKG])
+    return exe
+
+
+def test_facade_retarget_batch_matches_the_oracles(tmp_path):
+    all16 = recipe(20, 60)
+    ps = [all16[i] for i in (1, 2, 8)]
+    # the new problems: the start, goal and seed of three other problems of the recipe
+    qs = [dataclasses.replace(p, start=all16[i].start, goal=all16[i].goal, seed=all16[i].seed)
+          for p, i in zip(ps, (12, 14, 3))]
+    oracles = [po.Oracle(q, threads=8) for q in qs]
+    oresults = [o.optimize() for o in oracles]
+    first = [int(po.Oracle(p, threads=8).optimize()[0].iterations) for p in ps]
+    ostops = [int(st.iterations) for st, _ in oresults]
+    assert len(set(first)) >= 2 and len(set(ostops)) >= 2, (first, ostops)   # each stops on its own, both times
+    dirs = []
+    for i, p in enumerate(ps + qs):
+        d = tmp_path / f"p{i}"
+        d.mkdir()
+        fu.write_problem(p, str(d))
+        dirs.append(str(d))
+    exe = build_retarget_driver(str(tmp_path))
+    res = str(tmp_path / "out.txt")
+    r = subprocess.run([exe, res, str(len(ps))] + dirs, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.returncode, r.stderr)
+    toks = open(res).read().split()
+    pos = 0
+    for i, (q, o) in enumerate(zip(qs, oracles)):
+        ost, ocosts = oresults[i]
+        head = toks[pos:pos + 9]
+        pos += 9
+        it, ntq = int(head[0]), int(head[8])
+        print("optimizer", i, "iterations", it, "oracle", ost.iterations)
+        assert [int(x) for x in head[:5]] == [int(getattr(ost, k)) for k in INT_STATS], i
+        assert float(head[5]) == ost.best_cost, i
+        vals = np.array([float(x) for x in toks[pos:pos + it + ntq + q.J * q.N]])
+        pos += it + ntq + q.J * q.N
+        np.testing.assert_array_equal(vals[:it], ocosts, err_msg=f"optimizer {i} costs")
+        assert ntq == q.N
+        np.testing.assert_array_equal(vals[it:it + ntq], o.best_torques(), err_msg=f"optimizer {i} torques")
+        np.testing.assert_array_equal(vals[it + ntq:].reshape(q.J, q.N), o.best_trajectory(),
+                                      err_msg=f"optimizer {i} best trajectory")
+    assert pos == len(toks)
