@@ -578,18 +578,7 @@ int stomp_engine_optimize(stomp_engine* e, stomp_stats* st, double* costs_per_it
     // later launches (iterate / run / eval) are not gated
     HIP_TRY(e, hipMemsetAsync(e->d_track, 0, sizeof(int), e->stream));
     SYNC_TRY(e);
-    stomp_stats s;
-    s.iterations = t.iterations;
-    s.success = t.success;
-    s.success_iteration = t.success_iteration;
-    s.collision_success_iteration = t.collision_success_iteration;
-    s.last_improvement_iteration = t.last_improvement_iteration;
-    s.best_cost = t.best;
-    const double tick_s = e->wall_khz > 0 ? 1.0 / (1000.0 * e->wall_khz) : 0.0;
-    s.success_duration = t.success_iteration >= 0 ? (double)(t.t_success - t.t0) * tick_s : 0.0;
-    s.collision_success_duration =
-        t.collision_success_iteration >= 0 ? (double)(t.t_collision_success - t.t0) * tick_s : 0.0;
-    if (st) *st = s;
+    if (st) *st = stats_from_track(e, t);
     return 0;
 }
 

@@ -2,48 +2,48 @@
 // Several engines of one shape driven in lockstep by shared launches: per iteration one rollout
 // launch covering every engine's rollout workgroups and pregen blocks, one weights launch and one
 // update launch (k_rollout_group, k_weights_rows_group, k_update_group), so a batch of independent
-// planning problems costs three dispatches per iteration instead of three per problem.  The
-// per-engine kernel arguments of a whole run are staged in pinned memory and uploaded once; each
-// engine's results are the ones its own stomp_engine_run gives, bit for bit.  stomp_group_optimize
-// runs the whole optimize loop that way, the bookkeeping of every engine in one more launch per
-// iteration (k_track_group), each engine stopping on its own.
-// Engines with reused rollouts (one K_r for the group) add the reuse candidates' totals blocks to
-// the rollout launch and one launch for every engine's reused rows (k_reuse_rows_group) on the
-// reusing iterations; the host keeps every engine's generateRollouts state (reused_next,
-// extra_added, the row-set swap) in step with the staged iterations and, after an optimize loop,
-// puts back the state of the iteration each engine stopped at.
-// A group created with state_terms (stomp_group_create_with) also takes engines with the torque
-// term and / or orientation path constraints: every grouped rollout launch and every grouped
-// noiseless flush is followed by one launch of the state-cost terms for all of its engines
-// (k_terms_group, each engine with its own TermsModel; an engine without terms has no workgroup
-// that writes), before anything reads the state costs, the noiseless total or the
-// constraints-satisfied flag.
-// A group created accepting cumulative costs (stomp_group_create_flags) also takes engines with
-// use_cumulative_costs, mixed freely with engines without: every grouped weights launch is then
-// preceded, inside the same timed scope, by one launch of the cumulative rows of all of its
-// engines (k_cumulative_group; an engine without cumulative costs has no workgroup that writes).
+// planning problems costs three dispatches per iteration instead of three per problem.  Each
+// engine's results are the ones its own stomp_engine_run gives, bit for bit.
+// One grouped step is described by a StepLaunch and issued by launch_step, the only place that
+// knows the launches and their order: per iteration of stomp_group_run, per staged step of
+// stomp_group_optimize (with the flush cohort and k_track_group, the bookkeeping of every engine,
+// each stopping on its own), and for stomp_group_synchronize's flush.  stage_step writes a step's
+// per-engine kernel arguments through an Arena over a pinned buffer and its device twin; a run or
+// a chunk of steps is uploaded once.  What a group may hold adds launches to the step:
+//   reused rollouts (one K_r for the group): the candidates' totals blocks in the rollout launch and
+//     k_reuse_rows_group on the reusing iterations; the host keeps every engine's generateRollouts
+//     state in step with the staged iterations and, after an optimize loop, puts back the state of
+//     the iteration each engine stopped at
+//   state-cost terms (stomp_group_create_with): k_terms_group after every grouped rollout launch
+//     and flush, each engine with its own TermsModel (an engine without terms has no workgroup
+//     that writes)
+//   cumulative costs (stomp_group_create_flags): k_cumulative_group before the weights launch, in
+//     its timed scope (an engine without has no workgroup that writes)
 // stomp_group_retarget puts every engine of the group onto a new start, goal and seed in one launch
 // and one read-back (engine_retarget.cpp); the launch also writes the padding-collision flags of
 // the group's own DevModel list, which the grouped launches of a run and a synchronize read.
 #include "engine_internal.h"
 
 #include <algorithm>
+#include <optional>
 
 using namespace stomp;
 
 struct stomp_group {
     std::vector<stomp_engine*> e;
+    std::vector<int> all;                 // 0 .. P - 1: the engines of a run's step and of a synchronize's flush
     int device = 0;
     hipStream_t stream = nullptr;
     int nt = 0;                           // weights tiles per engine
+    NoiseArgs shape{};                    // J, N, Nall of the reuse launches
     DevModel* d_models = nullptr;         // [P]
     bool state_terms = false;             // engines with terms accepted (stomp_group_create_with)
     TermsModel* d_tmodels = nullptr;      // [P] every engine's terms model (state_terms)
     int nterms = 0;                       // engines with terms
     int ncum = 0;                         // engines with cumulative costs (stomp_group_create_flags)
     size_t terms_lds = 0;                 // the largest terms_lds_bytes among them: k_terms_group's dynamic LDS
-    unsigned char* d_args = nullptr;      // [iterations][P] CostArgs, WeightArgs, UpdateArgs, (K_r > 0) ReuseRowArgs,
-                                          // (engines with terms) TermsArgs
+    // stomp_group_run / stomp_group_synchronize: one run's arguments, a take_step per iteration
+    unsigned char* d_args = nullptr;
     size_t d_cap = 0;
     unsigned char* h_args = nullptr;      // pinned staging of one run's arguments
     size_t h_cap = 0;
@@ -66,13 +66,184 @@ struct stomp_group {
 };
 
 namespace {
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 int gfail(stomp_group* g, int code, const char* msg)
 {
     g_last_error = msg;
     if (g) g->err = msg;
     return code;
+}
+
+// the group's buffers are made with hipMalloc / hipHostMalloc and freed here, pointer reset
+template <class... T>
+void free_device(T*&... p) { ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...); }
+template <class... T>
+void free_pinned(T*&... p) { ((p ? (void)hipHostFree(p) : (void)0, p = nullptr), ...); }
+
+// A bump allocator over a staging buffer, `cap` bytes pinned at `h` and on the device at `d`:
+// take(n, dev) hands out the next array of n T at a 256-byte aligned offset of both, the host side
+// returned, the device side in `dev`.  The caller checks overflowed() before it fills.  With no
+// buffers it only measures: used() after the takes is the capacity they need.
+struct Arena {
+    unsigned char *h = nullptr, *d = nullptr;
+    size_t cap = ~(size_t)0, off = 0;
+    template <class T>
+    T* take(size_t n, const T*& dev)
+    {
+        const size_t o = off;
+        off += align256(sizeof(T) * n);
+        dev = d ? (const T*)(d + o) : nullptr;
+        return h ? (T*)(h + o) : nullptr;
+    }
+    size_t used() const { return off; }
+    bool overflowed() const { return off > cap; }
+};
+
+// the DevModel and TermsModel lists of a launch: the group's own over all P engines, or staged ones
+struct ModelLists {
+    const DevModel* models = nullptr;
+    const TermsModel* tmodels = nullptr;
+    int nx = 0;   // engines with terms among the launch's (0: no terms launch)
+};
+
+// One grouped step: what launch_step needs and nothing else, device pointers and counts.
+struct StepLaunch {
+    // the engines that run the iteration: rollouts, weights, update
+    const CostArgs* cas = nullptr; const WeightArgs* was = nullptr; const UpdateArgs* uas = nullptr;
+    const ReuseRowArgs* ras = nullptr; const TermsArgs* xas = nullptr;
+    ModelLists lists;
+    int nm = 0, nro = 0, ntot = 0;   // engines; rollout workgroups and totals blocks of each
+    bool reuse = false;
+    // the flush cohort: engines whose pending noiseless rollout alone is evaluated
+    const CostArgs* ccs = nullptr; const TermsArgs* cxas = nullptr;
+    ModelLists clists;
+    int nc = 0;
+    bool time_flush = true;          // the cohort's rollout launch is recorded on T_NOISELESS
+    // k_track_group over both sets ([nm + nc]); track_it < 0: no launch
+    const TrackArgs* tas = nullptr;
+    int track_it = -1;
+};
+
+// The launches of one grouped step, in the order everything depends on.  With timing on for the
+// group's first engine, its timers hold the group's launches.
+void launch_step(stomp_group* g, const StepLaunch& L)
+{
+    stomp_engine* e0 = g->e[0];
+    hipStream_t s = g->stream;
+    const int J = e0->J, N = e0->N, K = e0->K_loc;
+    const DevModel& shape = e0->model;   // the engines of a group have one shape and one field layout
+    if (L.nc > 0) {
+        // every cohort engine's pending noiseless rollout in one launch (one workgroup per engine)
+        std::optional<Timed> tm;
+        if (L.time_flush) tm.emplace(e0, T_NOISELESS, s);
+        launch_cost_group(shape, L.clists.models, L.ccs, L.nc, 1, 0, s);
+    }
+    if (L.nc > 0 && L.clists.nx > 0) {
+        Timed tm(e0, T_TERMS, s);
+        launch_terms_group(L.clists.tmodels, L.cxas, L.nc, 1, N, g->terms_lds, s);
+    }
+    if (L.nm > 0) {
+        Timed tm(e0, T_COST, s);
+        launch_cost_group(shape, L.lists.models, L.cas, L.nm, L.nro, K + L.ntot, s);
+    }
+    if (L.nm > 0 && L.lists.nx > 0) {
+        // the state-cost terms of both rollout launches before the bookkeeping reads the noiseless
+        // rollouts' totals and constraints-satisfied flags, the reuse ranking and the weights the rows
+        Timed tm(e0, T_TERMS, s);
+        launch_terms_group(L.lists.tmodels, L.xas, L.nm, L.nro, N, g->terms_lds, s);
+    }
+    // before this step's weights / update: a break decided on the previous iteration's noiseless
+    // rollout leaves theta where the reference leaves it
+    if (L.track_it >= 0) launch_track_group(L.tas, L.nm + L.nc, L.track_it, J * N, s);
+    if (L.nm <= 0) return;
+    if (L.reuse) {
+        // every engine's reuse step (an engine on its own records its reused rows' launch on this
+        // timer too); after the bookkeeping, as the engine's own loop: a stopped engine's reused
+        // rows stay the ones of the iteration it stopped at
+        Timed tm(e0, T_NOISE, s);
+        launch_reuse_rows_group(g->shape, L.ras, L.nm, e0->K, e0->Kr, s);
+    }
+    {
+        // the cumulative rows of the engines that use them, on the control costs the reuse launch
+        // re-priced, in the weights' scope as an engine's own launch_cumulative (the step's own
+        // list: compacted, or a stopped engine a no-op at its flag)
+        Timed tm(e0, T_WEIGHTS, s);
+        if (g->ncum > 0) launch_cumulative_group(L.was, L.nm, J, N, K, s);
+        launch_weights_group(L.was, L.nm, J, N, K, s);
+    }
+    {
+        Timed tm(e0, T_UPDATE, s);
+        launch_update_group(J, N, L.uas, L.nm, s);
+    }
+}
+
+// one step's staged arrays over nm engines that run the iteration and nc of the flush cohort (the
+// arrays a group has no use for are empty): the host side; L gets the device side and the counts
+struct StepHost {
+    CostArgs* cas; WeightArgs* was; UpdateArgs* uas; ReuseRowArgs* ras; TermsArgs* xas;
+    CostArgs* ccs; TermsArgs* cxas; TrackArgs* tas;
+};
+
+StepHost take_step(Arena& a, const stomp_group* g, int nm, int nc, bool track, StepLaunch& L)
+{
+    const int terms = g->nterms > 0 ? 1 : 0, reuse = g->e[0]->Kr > 0 ? 1 : 0;
+    L.nm = nm; L.nc = nc;
+    return StepHost{a.take(nm, L.cas), a.take(nm, L.was), a.take(nm, L.uas), a.take(reuse * nm, L.ras),
+                    a.take(terms * nm, L.xas), a.take(nc, L.ccs), a.take(terms * nc, L.cxas),
+                    a.take(track ? nm + nc : 0, L.tas)};
+}
+
+// the model lists of a launch over the n engines `of`, staged (of == nullptr: measured only)
+ModelLists take_models(Arena& a, const stomp_group* g, const int* of, int n)
+{
+    ModelLists l;
+    DevModel* ms = a.take(n, l.models);
+    TermsModel* xs = a.take(g->nterms > 0 ? n : 0, l.tmodels);
+    if (a.overflowed() || !of) return l;
+    for (int k = 0; k < n; ++k) ms[k] = g->e[of[k]]->model;
+    for (int k = 0; k < n && g->nterms > 0; ++k) {
+        xs[k] = g->e[of[k]]->terms;
+        l.nx += g->e[of[k]]->terms_on ? 1 : 0;
+    }
+    return l;
+}
+
+// the capacity one staged step needs, with `lists` its two launches' model lists too
+size_t step_bytes(const stomp_group* g, int nm, int nc, bool track, bool lists)
+{
+    Arena measure;
+    StepLaunch L;
+    take_step(measure, g, nm, nc, track, L);
+    if (lists) take_models(measure, g, nullptr, nm), take_models(measure, g, nullptr, nc);
+    return measure.used();
+}
+
+// h_args / d_args of at least `bytes` and h_args free again: the last upload has left it; a device
+// buffer is freed once the stream's launches have read it
+int reserve_args(stomp_group* g, size_t bytes)
+{
+    if (g->staged && hipEventSynchronize(g->staged) != hipSuccess)
+        return gfail(g, STOMP_E_DEVICE, "group staging wait failed");
+    if (bytes > g->h_cap) {
+        free_pinned(g->h_args);
+        g->h_cap = hipHostMalloc((void**)&g->h_args, bytes) == hipSuccess ? bytes : 0;
+        if (!g->h_cap) return gfail(g, STOMP_E_DEVICE, "hipHostMalloc failed");
+    }
+    if (bytes > g->d_cap) {
+        if (g->d_args) hipStreamSynchronize(g->stream);
+        free_device(g->d_args);
+        g->d_cap = hipMalloc(&g->d_args, bytes) == hipSuccess ? bytes : 0;
+        if (!g->d_cap) return gfail(g, STOMP_E_DEVICE, "hipMalloc failed");
+    }
+    return 0;
+}
+
+// the arena's staged bytes on their way to the device; `done` (or none) recorded behind them
+int upload(stomp_group* g, const Arena& a, hipEvent_t done)
+{
+    hipError_t err = a.used() ? hipMemcpyAsync(a.d, a.h, a.used(), hipMemcpyHostToDevice, g->stream) : hipSuccess;
+    if (err == hipSuccess && done) err = hipEventRecord(done, g->stream);
+    if (err != hipSuccess) return gfail(g, STOMP_E_DEVICE, "group argument upload failed");
+    return 0;
 }
 
 // what one engine's staged iteration adds to the step's launches
@@ -197,6 +368,213 @@ int sync_model_flags(stomp_group* g)
     }
     return 0;
 }
+
+// what stomp_group_create_flags tells an engine the group does not take, by what the group accepts
+const char* refusal_text(bool state_terms, bool cumulative)
+{
+    if (state_terms && cumulative) return "groups run single-device engines of at most 16 joints";
+    if (cumulative) return "groups run single-device engines of at most 16 joints without state-cost terms";
+    if (state_terms) return "groups run single-device engines of at most 16 joints without cumulative costs";
+    return "groups run single-device engines of at most 16 joints without state-cost terms or cumulative costs";
+}
+
+TrackArgs track_args(const stomp_group* g, int p)
+{
+    const stomp_engine* e = g->e[p];
+    return TrackArgs{e->d_track, e->d_total, e->d_cf, e->d_cs, e->d_opt_costs, e->d_last_traj, e->d_best_traj,
+                     e->max_it_cf, e->max_it, g->d_mirror + 2 * p};
+}
+
+// One step's arguments into the arena, host only: iteration `it` of the engines `main`
+// (stage_iteration and their terms arguments; they must agree on the step's counts), the flush of
+// the engines `cohort`, and with `track` the bookkeeping arguments of both sets.
+int stage_step(stomp_group* g, Arena& a, const std::vector<int>& main, const std::vector<int>& cohort, int it,
+               bool keep_in_pre, bool track, StepLaunch& L)
+{
+    const int nm = (int)main.size(), nc = (int)cohort.size();
+    const StepHost h = take_step(a, g, nm, nc, track, L);
+    if (a.overflowed()) return gfail(g, STOMP_E_INVALID, "group optimize staging overflow");
+    for (int k = 0; k < nm; ++k) {
+        stomp_engine* e = g->e[main[k]];
+        const StagedIteration si = stage_iteration(e, it, keep_in_pre, h.cas[k], h.was[k], h.uas[k], h.ras + k);
+        if (g->nterms > 0) h.xas[k] = terms_args(e, h.cas[k]);
+        if (k == 0) { L.nro = si.nro; L.ntot = si.ntot; L.reuse = si.reuse; }
+        else if (si.nro != L.nro || si.ntot != L.ntot || si.reuse != L.reuse)
+            return gfail(g, STOMP_E_INVALID, "group engines out of step");
+        if (track) h.tas[k] = track_args(g, main[k]);
+    }
+    for (int k = 0; k < nc; ++k) {
+        stomp_engine* e = g->e[cohort[k]];
+        h.ccs[k] = noiseless_args(e);   // with K_r > 0 the extra rollout's rows too
+        if (g->nterms > 0) h.cxas[k] = terms_args(e, h.ccs[k]);
+        if (track) h.tas[nm + k] = track_args(g, cohort[k]);
+    }
+    return 0;
+}
+
+// ---- stomp_group_optimize's stages
+
+// what the stages of one stomp_group_optimize call share
+struct OptimizeLoop {
+    struct HostState { bool reused_next, extra_added; int row_set; };   // generateRollouts' on the host
+    stomp_group* g = nullptr;
+    std::vector<int> live;     // the engines staged from here on (all, or with g->compact the ones not seen stopped)
+    int next = 1;              // the first step not staged yet
+    int last_step = 0;         // the flush of the engines that ran the largest max_iterations
+    // after[p][it - 1]: engine p's state after iteration it, to restore for every engine the one
+    // of the iteration the device stopped it at (stomp_engine_optimize's)
+    std::vector<std::vector<HostState>> after;
+    std::vector<int> main, cohort;    // the step being staged
+    std::vector<StepLaunch> steps;    // the chunk being staged
+};
+
+// The model lists of the rollout launch within a chunk: staged once, again where an engine's
+// max_iterations takes it out of the set (the upload of a chunk carries them once, not per step).
+struct MainLists {
+    std::vector<int> of;
+    ModelLists lists;
+    const ModelLists& get(Arena& a, const stomp_group* g, const std::vector<int>& main)
+    {
+        if (!main.empty() && main != of) {
+            lists = take_models(a, g, main.data(), (int)main.size());
+            of = main;
+        }
+        return lists;
+    }
+};
+
+// first-call allocations and the track arguments' upload
+int optimize_prepare(stomp_group* g)
+{
+    if (g->d_mirror) return 0;
+    const int P = (int)g->e.size();
+    // one chunk of steps with every engine in both sets at most, and both launches' model lists
+    const size_t slot_bytes = step_bytes(g, P, P, true, true) * (size_t)STOMP_GROUP_OPTIMIZE_CHUNK;
+    if (hipMalloc((void**)&g->d_mirror, sizeof(int) * 2 * P) != hipSuccess ||
+        hipHostMalloc((void**)&g->h_mirror, sizeof(int) * 4 * P) != hipSuccess ||
+        hipMalloc((void**)&g->d_track_all, sizeof(TrackArgs) * P) != hipSuccess ||
+        hipMalloc((void**)&g->d_opt, 2 * slot_bytes) != hipSuccess ||
+        hipHostMalloc((void**)&g->h_opt, 2 * slot_bytes) != hipSuccess ||
+        hipEventCreateWithFlags(&g->opt_ev[0], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&g->opt_ev[1], hipEventDisableTiming) != hipSuccess)
+        return gfail(g, STOMP_E_DEVICE, "group optimize allocation failed");
+    g->opt_slot = slot_bytes;
+    // every engine's track arguments, for the start and clear launches
+    std::vector<TrackArgs> ta(P);
+    for (int p = 0; p < P; ++p) ta[p] = track_args(g, p);
+    if (hipMemcpy(g->d_track_all, ta.data(), sizeof(TrackArgs) * P, hipMemcpyHostToDevice) != hipSuccess)
+        return gfail(g, STOMP_E_DEVICE, "group argument upload failed");
+    return 0;
+}
+
+// The engines enter in any state: rows out of the pregen buffers, pending noiseless rollouts
+// evaluated, the pregen rows of iteration 1 made where another iteration's are held.
+void optimize_enter(stomp_group* g)
+{
+    for (stomp_engine* e : g->e) {
+        materialize_rows(e);
+        flush_noiseless(e);
+        if (e->max_it > 0 && e->pre_it != 1) {
+            launch_pregen(pregen_args(e, 1), e->K_loc, g->stream);
+            e->pre_it = 1;
+        }
+    }
+    launch_track_start_group(g->d_track_all, (int)g->e.size(), false, g->stream);   // stomp_optimizer.cpp:251 start_time
+}
+
+// The next chunk of steps into the arena and onto o.steps, host only.  In step `it` the engines
+// of o.main run the iteration and the ones of o.cohort, which ended with it - 1, get their flush
+// (the table above stomp_group_optimize).
+int optimize_stage_chunk(OptimizeLoop& o, Arena& a)
+{
+    stomp_group* g = o.g;
+    MainLists lists;
+    o.steps.clear();
+    const int end = std::min(o.next + STOMP_GROUP_OPTIMIZE_CHUNK, o.last_step + 1);
+    for (int it = o.next; it < end; ++it) {
+        o.main.clear();
+        o.cohort.clear();
+        for (int p : o.live) {
+            if (g->e[p]->max_it >= it) o.main.push_back(p);
+            else if (g->e[p]->max_it == it - 1 && it >= 2) o.cohort.push_back(p);
+        }
+        // inside the optimize loop the noise / params rows are copied out of the pregen buffer
+        // (pregen blocks enqueued past a stop overwrite the ping-pong buffers), the weights read
+        // d_noise
+        for (int p : o.main)
+            if (g->e[p]->pre_it != it) return gfail(g, STOMP_E_INVALID, "group pregen rows out of step");
+        StepLaunch L;
+        if (int rc = stage_step(g, a, o.main, o.cohort, it, false, true, L)) return rc;
+        L.clists = take_models(a, g, o.cohort.data(), (int)o.cohort.size());
+        L.lists = lists.get(a, g, o.main);
+        if (a.overflowed()) return gfail(g, STOMP_E_INVALID, "group optimize staging overflow");
+        L.track_it = it >= 2 ? it - 2 : -1;
+        for (int p : o.main)
+            if (g->e[p]->Kr > 0) o.after[p][it - 1] = {g->e[p]->reused_next, g->e[p]->extra_added, g->e[p]->row_set};
+        o.steps.push_back(L);
+    }
+    o.next = end;
+    return 0;
+}
+
+// one chunk of steps staged into `slot`, uploaded and enqueued, then the mirror's read-back
+int optimize_enqueue_chunk(OptimizeLoop& o, int slot)
+{
+    stomp_group* g = o.g;
+    const int P = (int)g->e.size();
+    Arena a{g->h_opt + (size_t)slot * g->opt_slot, g->d_opt + (size_t)slot * g->opt_slot, g->opt_slot};
+    if (int rc = optimize_stage_chunk(o, a)) return rc;
+    if (int rc = upload(g, a, nullptr)) return rc;
+    for (const StepLaunch& L : o.steps) launch_step(g, L);
+    if (hipMemcpyAsync(g->h_mirror + (size_t)slot * 2 * P, g->d_mirror, sizeof(int) * 2 * P, hipMemcpyDeviceToHost,
+                       g->stream) != hipSuccess ||
+        hipEventRecord(g->opt_ev[slot], g->stream) != hipSuccess)
+        return gfail(g, STOMP_E_DEVICE, "group read-back failed");
+    return 0;
+}
+
+// The loop is over (rc: how): pipeline state reset, every engine's DevTrack read back, its
+// generateRollouts state put back to the iteration it stopped at, cost histories and stats out.
+int optimize_finish(OptimizeLoop& o, int rc, stomp_stats* stats, double* costs_per_iteration, int32_t costs_stride)
+{
+    stomp_group* g = o.g;
+    const int P = (int)g->e.size();
+    hipStream_t s = g->stream;
+    // the steps enqueued past an engine's stop were no-ops; the engines stopped at different
+    // iterations, so every engine leaves with no pregen rows held and nothing pending (the next
+    // run, the group's or the engine's own, makes its rows with a standalone pregen launch)
+    for (stomp_engine* e : g->e) {
+        e->pending_member = -1;
+        e->pre_it = -1;
+        e->rows_in_pre = false;
+    }
+    hipError_t err = hipGetLastError();
+    if (!rc && err != hipSuccess) rc = gfail(g, STOMP_E_DEVICE, hipGetErrorString(err));
+    for (int p = 0; p < P && !rc; ++p)
+        if (hipMemcpyAsync(&g->e[p]->h_track[2], g->e[p]->d_track, sizeof(DevTrack), hipMemcpyDeviceToHost, s) != hipSuccess)
+            rc = gfail(g, STOMP_E_DEVICE, "group read-back failed");
+    // later launches (iterate / run / eval) are not gated
+    launch_track_start_group(g->d_track_all, P, true, s);
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = gfail(g, STOMP_E_DEVICE, "group synchronize failed");
+    if (rc) return rc;
+    for (int p = 0; p < P; ++p) {
+        stomp_engine* e = g->e[p];
+        const DevTrack& t = e->h_track[2];
+        if (e->Kr > 0 && t.iterations > 0) {
+            // the steps staged past the engine's stop were no-ops on the device
+            const OptimizeLoop::HostState& h = o.after[p][t.iterations - 1];
+            e->reused_next = h.reused_next;
+            e->extra_added = h.extra_added;
+            if (e->row_set != h.row_set) swap_row_sets(e);
+        }
+        if (costs_per_iteration && t.iterations > 0 &&
+            hipMemcpy(costs_per_iteration + (size_t)p * costs_stride, e->d_opt_costs, sizeof(double) * t.iterations,
+                      hipMemcpyDeviceToHost) != hipSuccess)
+            return gfail(g, STOMP_E_DEVICE, "group cost history read-back failed");
+        stats[p] = stats_from_track(e, t);
+    }
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -209,17 +587,8 @@ void stomp_group_destroy(stomp_group* g)
         hipEventSynchronize(g->staged);
         hipEventDestroy(g->staged);
     }
-    if (g->d_models) hipFree(g->d_models);
-    if (g->d_tmodels) hipFree(g->d_tmodels);
-    if (g->d_args) hipFree(g->d_args);
-    if (g->h_args) hipHostFree(g->h_args);
-    if (g->d_opt) hipFree(g->d_opt);
-    if (g->h_opt) hipHostFree(g->h_opt);
-    if (g->d_mirror) hipFree(g->d_mirror);
-    if (g->h_mirror) hipHostFree(g->h_mirror);
-    if (g->d_track_all) hipFree(g->d_track_all);
-    if (g->d_rt) hipFree(g->d_rt);
-    if (g->h_rt) hipHostFree(g->h_rt);
+    free_device(g->d_models, g->d_tmodels, g->d_args, g->d_opt, g->d_mirror, g->d_track_all, g->d_rt);
+    free_pinned(g->h_args, g->h_opt, g->h_mirror, g->h_rt);
     for (hipEvent_t ev : g->opt_ev)
         if (ev) hipEventDestroy(ev);
     delete g;
@@ -267,12 +636,7 @@ int stomp_group_create_flags(stomp_engine* const* engines, int32_t n, uint32_t a
         if (e->world != 1 || !e->pre_on || (e->terms_on && !state_terms) || e->split_modes || e->gather ||
             (e->use_cum && !cumulative) || e->J > 16)
             return gfail(nullptr, STOMP_E_UNSUPPORTED,
-                         cumulative ? (state_terms ? "groups run single-device engines of at most 16 joints"
-                                                   : "groups run single-device engines of at most 16 joints without "
-                                                     "state-cost terms")
-                         : state_terms ? "groups run single-device engines of at most 16 joints without cumulative costs"
-                                       : "groups run single-device engines of at most 16 joints without state-cost "
-                                         "terms or cumulative costs");
+                         refusal_text(state_terms, cumulative));
         if (e->use_cum && cumulative_group_rows(e->N) <= 0)
             return gfail(nullptr, STOMP_E_UNSUPPORTED, "groups with cumulative costs take at most 256 time steps");
         if (e->Kr > 0) {
@@ -292,9 +656,11 @@ int stomp_group_create_flags(stomp_engine* const* engines, int32_t n, uint32_t a
     DeviceGuard dg(e0->device);
     stomp_group* g = new stomp_group();
     g->e.assign(engines, engines + n);
+    for (int p = 0; p < n; ++p) g->all.push_back(p);
     g->device = e0->device;
     g->stream = e0->stream;
     g->nt = nt;
+    g->shape = noise_args(e0, 1);
     if (compact >= 0) g->compact = compact != 0;
     else if (const char* c = getenv("STOMP_DEBUG_GROUP_COMPACT")) g->compact = c[0] == '1';
     g->state_terms = state_terms;
@@ -322,17 +688,20 @@ int stomp_group_create_flags(stomp_engine* const* engines, int32_t n, uint32_t a
             return gfail(nullptr, STOMP_E_DEVICE, "group allocation failed");
         }
     }
-    if (getenv("STOMP_DEBUG_LEAN_PRINT"))   // the group's own choices (read-only: tests and tables)
+    if (getenv("STOMP_DEBUG_LEAN_PRINT")) {
+        // the group's own choices and the launches launch_terms_group / launch_cumulative_group
+        // take (read-only: tests and tables)
         fprintf(stderr, "stomp: group of %d engines J %d N %d K %d brick %d, %d weights tiles per engine, "
                         "weights %s\n", (int)n, e0->J, e0->N, e0->K_loc, e0->model.brick, nt,
                 weights_kernel_name(e0->K_loc, true, true));
-    if (state_terms && getenv("STOMP_DEBUG_LEAN_PRINT"))   // the launch launch_terms_group takes (read-only)
-        fprintf(stderr, "stomp: group terms k_terms_group<%d>, LDS %zu B, opt-in %d, engines with terms %d of %d\n",
-                e0->N <= 128 ? 128 : 256, g->terms_lds, g->terms_lds > 64 * 1024 ? 1 : 0, g->nterms, (int)n);
-    if (g->ncum > 0 && getenv("STOMP_DEBUG_LEAN_PRINT"))   // the launch launch_cumulative_group takes (read-only)
-        fprintf(stderr, "stomp: group cumulative k_cumulative_group<%d>, rows per workgroup %d, LDS %zu B, engines "
-                        "with cumulative costs %d of %d\n", cumulative_group_rows(e0->N), cumulative_group_rows(e0->N),
-                cumulative_group_lds_bytes(e0->N), g->ncum, (int)n);
+        if (state_terms)
+            fprintf(stderr, "stomp: group terms k_terms_group<%d>, LDS %zu B, opt-in %d, engines with terms %d of %d\n",
+                    e0->N <= 128 ? 128 : 256, g->terms_lds, g->terms_lds > 64 * 1024 ? 1 : 0, g->nterms, (int)n);
+        if (g->ncum > 0)
+            fprintf(stderr, "stomp: group cumulative k_cumulative_group<%d>, rows per workgroup %d, LDS %zu B, "
+                            "engines with cumulative costs %d of %d\n", cumulative_group_rows(e0->N),
+                    cumulative_group_rows(e0->N), cumulative_group_lds_bytes(e0->N), g->ncum, (int)n);
+    }
     *out = g;
     return 0;
 }
@@ -376,94 +745,27 @@ int stomp_group_run(stomp_group* g, int32_t first, int32_t count)
             (e->Kr > 0 && (e->reused_next != e0->reused_next || e->extra_added != e0->extra_added)))
             return gfail(g, STOMP_E_INVALID, "the engines of a group are not at the same iteration state");
     }
-    const size_t szc = align256(sizeof(CostArgs) * P), szw = align256(sizeof(WeightArgs) * P),
-                 szu = align256(sizeof(UpdateArgs) * P),
-                 szr = e0->Kr > 0 ? align256(sizeof(ReuseRowArgs) * P) : 0,
-                 szt = g->nterms > 0 ? align256(sizeof(TermsArgs) * P) : 0, per = szc + szw + szu + szr + szt;
-    const size_t bytes = per * (size_t)count;
+    const size_t bytes = step_bytes(g, P, 0, false, false) * (size_t)count;
     if (int rc = sync_model_flags(g)) return rc;
-    if (g->staged && hipEventSynchronize(g->staged) != hipSuccess)   // h_args free again
-        return gfail(g, STOMP_E_DEVICE, "group staging wait failed");
-    if (bytes > g->h_cap) {
-        if (g->h_args) hipHostFree(g->h_args);
-        g->h_args = nullptr;
-        g->h_cap = 0;
-        if (hipHostMalloc((void**)&g->h_args, bytes) != hipSuccess) return gfail(g, STOMP_E_DEVICE, "hipHostMalloc failed");
-        g->h_cap = bytes;
-    }
-    if (bytes > g->d_cap) {
-        if (g->d_args) {
-            hipStreamSynchronize(g->stream);
-            hipFree(g->d_args);
-        }
-        g->d_args = nullptr;
-        g->d_cap = 0;
-        if (hipMalloc(&g->d_args, bytes) != hipSuccess) return gfail(g, STOMP_E_DEVICE, "hipMalloc failed");
-        g->d_cap = bytes;
-    }
-    std::vector<StagedIteration> steps(count);
+    if (int rc = reserve_args(g, bytes)) return rc;
+    Arena a{g->h_args, g->d_args, bytes};
+    std::vector<StepLaunch> steps(count);
     std::vector<char> pregen_first(P, 0);
     for (int i = 0; i < count; ++i) {
         const int it = first + i;
-        CostArgs* cas = (CostArgs*)(g->h_args + per * i);
-        WeightArgs* was = (WeightArgs*)(g->h_args + per * i + szc);
-        UpdateArgs* uas = (UpdateArgs*)(g->h_args + per * i + szc + szw);
-        ReuseRowArgs* ras = (ReuseRowArgs*)(g->h_args + per * i + szc + szw + szu);
-        TermsArgs* tas = (TermsArgs*)(g->h_args + per * i + szc + szw + szu + szr);
         for (int p = 0; p < P; ++p) {
-            stomp_engine* e = g->e[p];
-            if (e->pre_it != it) {
-                if (i > 0) return gfail(g, STOMP_E_INVALID, "group pregen rows out of step");
-                pregen_first[p] = 1;
-            }
-            const StagedIteration st = stage_iteration(e, it, true, cas[p], was[p], uas[p], ras + p);
-            if (szt) tas[p] = terms_args(e, cas[p]);
-            if (p == 0) steps[i] = st;
-            else if (st.nro != steps[i].nro || st.ntot != steps[i].ntot || st.reuse != steps[i].reuse)
-                return gfail(g, STOMP_E_INVALID, "group engines out of step");
+            if (g->e[p]->pre_it == it) continue;
+            if (i > 0) return gfail(g, STOMP_E_INVALID, "group pregen rows out of step");
+            pregen_first[p] = 1;
         }
+        if (int rc = stage_step(g, a, g->all, {}, it, true, false, steps[i])) return rc;
+        steps[i].lists = {g->d_models, g->d_tmodels, g->nterms};
     }
-    hipStream_t s = g->stream;
     for (int p = 0; p < P; ++p)
-        if (pregen_first[p]) launch_pregen(pregen_args(g->e[p], first), g->e[p]->K_loc, s);
-    hipError_t err = hipMemcpyAsync(g->d_args, g->h_args, bytes, hipMemcpyHostToDevice, s);
-    if (err == hipSuccess) err = hipEventRecord(g->staged, s);
-    if (err != hipSuccess) return gfail(g, STOMP_E_DEVICE, "group argument upload failed");
-    const int J = e0->J, N = e0->N, K = e0->K_loc;
-    const NoiseArgs shape = noise_args(e0, first);   // J, N, Nall of the reuse launches
-    for (int i = 0; i < count; ++i) {
-        unsigned char* base = g->d_args + per * i;
-        // with timing on for the group's first engine, its timers hold the group's launches
-        {
-            Timed tm(e0, T_COST, s);
-            launch_cost_group(e0->model, g->d_models, (const CostArgs*)base, P, steps[i].nro, K + steps[i].ntot, s);
-        }
-        if (szt) {
-            // every engine's state-cost terms on the rollouts just evaluated, before the reuse
-            // ranking, the weights (and the next flush's bookkeeping) read them
-            Timed tm(e0, T_TERMS, s);
-            launch_terms_group(g->d_tmodels, (const TermsArgs*)(base + szc + szw + szu + szr), P, steps[i].nro, N,
-                               g->terms_lds, s);
-        }
-        if (steps[i].reuse) {
-            // every engine's reuse step (an engine on its own records its reused rows' launch on
-            // this timer too)
-            Timed tm(e0, T_NOISE, s);
-            launch_reuse_rows_group(shape, (const ReuseRowArgs*)(base + szc + szw + szu), P, e0->K, e0->Kr, s);
-        }
-        {
-            // the cumulative rows of the engines that use them, on the control costs the reuse
-            // launch re-priced, in the weights' scope as an engine's own launch_cumulative
-            Timed tm(e0, T_WEIGHTS, s);
-            if (g->ncum > 0) launch_cumulative_group((const WeightArgs*)(base + szc), P, J, N, K, s);
-            launch_weights_group((const WeightArgs*)(base + szc), P, J, N, K, s);
-        }
-        {
-            Timed tm(e0, T_UPDATE, s);
-            launch_update_group(J, N, (const UpdateArgs*)(base + szc + szw), P, s);
-        }
-    }
-    err = hipGetLastError();
+        if (pregen_first[p]) launch_pregen(pregen_args(g->e[p], first), g->e[p]->K_loc, g->stream);
+    if (int rc = upload(g, a, g->staged)) return rc;
+    for (const StepLaunch& L : steps) launch_step(g, L);
+    const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return gfail(g, STOMP_E_DEVICE, hipGetErrorString(err));
     return 0;
 }
@@ -474,33 +776,22 @@ int stomp_group_synchronize(stomp_group* g)
     DeviceGuard dg(g->device);
     const int P = (int)g->e.size();
     if (int rc = sync_model_flags(g)) return rc;
-    bool all = true;
-    for (stomp_engine* e : g->e) all = all && e->pending_member >= 0 && !e->tracking;
-    if (all) {
-        // every engine's pending noiseless rollout in one launch (one workgroup per engine)
-        const size_t szc = align256(sizeof(CostArgs) * P);
-        const size_t bytes = szc + (g->nterms > 0 ? align256(sizeof(TermsArgs) * P) : 0);
+    bool pending = true;
+    for (stomp_engine* e : g->e) pending = pending && e->pending_member >= 0 && !e->tracking;
+    const size_t cap = std::min(g->h_cap, g->d_cap);
+    if (pending && step_bytes(g, 0, P, false, false) <= cap) {
+        // every engine's pending noiseless rollout in one step of the flush cohort alone, staged in
+        // a run's buffers (no run has sized them yet: the per-engine flushes below); its rollout
+        // launch is on no timer, as an engine's own flush here
         if (g->staged && hipEventSynchronize(g->staged) != hipSuccess)
             return gfail(g, STOMP_E_DEVICE, "group staging wait failed");
-        if (bytes > g->h_cap || bytes > g->d_cap) {
-            all = false;   // the arrays of a run are larger; no run yet: per-engine flushes
-        } else {
-            CostArgs* cas = (CostArgs*)g->h_args;
-            TermsArgs* tas = (TermsArgs*)(g->h_args + szc);
-            for (int p = 0; p < P; ++p) {
-                cas[p] = noiseless_args(g->e[p]);
-                if (g->nterms > 0) tas[p] = terms_args(g->e[p], cas[p]);
-            }
-            hipError_t err = hipMemcpyAsync(g->d_args, g->h_args, bytes, hipMemcpyHostToDevice, g->stream);
-            if (err == hipSuccess) err = hipEventRecord(g->staged, g->stream);
-            if (err != hipSuccess) return gfail(g, STOMP_E_DEVICE, "group argument upload failed");
-            launch_cost_group(g->e[0]->model, g->d_models, (const CostArgs*)g->d_args, P, 1, 0, g->stream);
-            if (g->nterms > 0) {
-                Timed tm(g->e[0], T_TERMS, g->stream);
-                launch_terms_group(g->d_tmodels, (const TermsArgs*)(g->d_args + szc), P, 1, g->e[0]->N, g->terms_lds,
-                                   g->stream);
-            }
-        }
+        Arena a{g->h_args, g->d_args, cap};
+        StepLaunch L;
+        if (int rc = stage_step(g, a, {}, g->all, 0, false, false, L)) return rc;
+        L.clists = {g->d_models, g->d_tmodels, g->nterms};
+        L.time_flush = false;
+        if (int rc = upload(g, a, g->staged)) return rc;
+        launch_step(g, L);
     }
     for (stomp_engine* e : g->e) flush_noiseless(e);
     if (hipStreamSynchronize(g->stream) != hipSuccess) return gfail(g, STOMP_E_DEVICE, "group synchronize failed");
@@ -517,15 +808,14 @@ int32_t stomp_group_optimize_chunk(void) { return STOMP_GROUP_OPTIMIZE_CHUNK; }
 //   k_track_group(it - 2) over both sets, weights and update of the first set
 // so an engine whose own max_iterations ends the loop gets the flush and the bookkeeping that
 // stomp_engine_optimize ends with, in the step after its last iteration; the last step of all is
-// that flush alone.  The host reads the engines' (stop, iterations) mirror one chunk behind the
-// chunk it stages.  With g->compact it stages no arguments for an engine it has seen stopped;
-// otherwise a stopped engine's blocks stay in the launches and return at its stop flag (the
-// default: DESIGN.md 7 has the measurement).
+// that flush alone.  With g->compact no arguments are staged for an engine seen stopped; otherwise
+// its blocks stay in the launches and return at its stop flag (the default: DESIGN.md 7).
 int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_iteration, int32_t costs_stride)
 {
     if (!g) return gfail(nullptr, STOMP_E_INVALID, "null group");
     if (!stats) return gfail(g, STOMP_E_INVALID, "null stats");
     const int P = (int)g->e.size();
+    stomp_engine* e0 = g->e[0];
     int maxcap = 0;
     for (stomp_engine* e : g->e) {
         if (e->tracking) return gfail(g, STOMP_E_INVALID, "an engine of the group is inside its own optimize loop");
@@ -534,235 +824,29 @@ int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_i
     if (costs_per_iteration && costs_stride < maxcap)
         return gfail(g, STOMP_E_INVALID, "costs_stride is smaller than an engine's max_iterations");
     DeviceGuard dg(g->device);
-    hipStream_t s = g->stream;
-    stomp_engine* e0 = g->e[0];
-    const int J = e0->J, N = e0->N, K = e0->K_loc, chunk = STOMP_GROUP_OPTIMIZE_CHUNK;
-    // one step's arguments at most: both rollout launches' CostArgs and DevModel lists, the
-    // weights, update and track arguments
-    const size_t szc = align256(sizeof(CostArgs) * P), szw = align256(sizeof(WeightArgs) * P),
-                 szu = align256(sizeof(UpdateArgs) * P), szt = align256(sizeof(TrackArgs) * P),
-                 szm = align256(sizeof(DevModel) * P), szr = e0->Kr > 0 ? align256(sizeof(ReuseRowArgs) * P) : 0,
-                 // both rollout launches' TermsArgs and TermsModel lists
-                 szx = g->nterms > 0 ? 2 * (align256(sizeof(TermsArgs) * P) + align256(sizeof(TermsModel) * P)) : 0;
-    const size_t slot_bytes = (2 * szc + 2 * szm + szw + szu + szt + szr + szx) * (size_t)chunk;
-    auto track_args = [&](int p) {
-        stomp_engine* e = g->e[p];
-        return TrackArgs{e->d_track, e->d_total, e->d_cf, e->d_cs, e->d_opt_costs, e->d_last_traj, e->d_best_traj,
-                         e->max_it_cf, e->max_it, g->d_mirror + 2 * p};
-    };
-    if (!g->d_mirror) {
-        if (hipMalloc((void**)&g->d_mirror, sizeof(int) * 2 * P) != hipSuccess ||
-            hipHostMalloc((void**)&g->h_mirror, sizeof(int) * 4 * P) != hipSuccess ||
-            hipMalloc((void**)&g->d_track_all, sizeof(TrackArgs) * P) != hipSuccess ||
-            hipMalloc((void**)&g->d_opt, 2 * slot_bytes) != hipSuccess ||
-            hipHostMalloc((void**)&g->h_opt, 2 * slot_bytes) != hipSuccess ||
-            hipEventCreateWithFlags(&g->opt_ev[0], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&g->opt_ev[1], hipEventDisableTiming) != hipSuccess)
-            return gfail(g, STOMP_E_DEVICE, "group optimize allocation failed");
-        g->opt_slot = slot_bytes;
-        // every engine's track arguments, for the start and clear launches
-        std::vector<TrackArgs> ta(P);
-        for (int p = 0; p < P; ++p) ta[p] = track_args(p);
-        if (hipMemcpy(g->d_track_all, ta.data(), sizeof(TrackArgs) * P, hipMemcpyHostToDevice) != hipSuccess)
-            return gfail(g, STOMP_E_DEVICE, "group argument upload failed");
-    }
-    // the engines enter in any state: rows out of the pregen buffers, pending noiseless rollouts
-    // evaluated, the pregen rows of iteration 1 made where another iteration's are held.  With
-    // reuse they are at one point of generateRollouts (all reuse in iteration 1, or none does)
+    if (int rc = optimize_prepare(g)) return rc;
+    // with reuse the engines are at one point of generateRollouts (all reuse in iteration 1, or
+    // none does)
     for (stomp_engine* e : g->e)
         if (e->Kr > 0 && e->reused_next != e0->reused_next)
             return gfail(g, STOMP_E_INVALID, "the engines of a group are not at the same iteration state");
-    // host-side generateRollouts state after each staged iteration, to restore for every engine
-    // the one of the iteration the device stopped it at (stomp_engine_optimize's)
-    struct HostState { bool reused_next, extra_added; int row_set; };
-    std::vector<std::vector<HostState>> after(P);
+    OptimizeLoop o;
+    o.g = g;
+    o.after.resize(P);
     if (e0->Kr > 0)
-        for (int p = 0; p < P; ++p) after[p].resize((size_t)std::max(g->e[p]->max_it, 0));
-    const NoiseArgs shape = noise_args(e0, 1);   // J, N, Nall of the reuse launches
-    for (stomp_engine* e : g->e) {
-        materialize_rows(e);
-        flush_noiseless(e);
-        if (e->max_it > 0 && e->pre_it != 1) {
-            launch_pregen(pregen_args(e, 1), e->K_loc, s);
-            e->pre_it = 1;
-        }
-    }
-    launch_track_start_group(g->d_track_all, P, false, s);   // stomp_optimizer.cpp:251 start_time
-
-    std::vector<int> live;
+        for (int p = 0; p < P; ++p) o.after[p].resize((size_t)std::max(g->e[p]->max_it, 0));
     for (int p = 0; p < P; ++p)
-        if (!g->compact || g->e[p]->max_it > 0) live.push_back(p);
-    const int last_step = maxcap > 0 ? maxcap + 1 : 0;   // the flush of the engines that ran maxcap iterations
-    int next = 1;
-    // one chunk of steps staged into `slot`, uploaded and enqueued, then the mirror's read-back
-    auto enqueue_chunk = [&](int slot) -> int {
-        unsigned char* hb = g->h_opt + (size_t)slot * g->opt_slot;
-        unsigned char* db = g->d_opt + (size_t)slot * g->opt_slot;
-        size_t used = 0;
-        auto take = [&](size_t bytes) {
-            const size_t o = used;
-            used += align256(bytes);
-            return o;
-        };
-        struct Step {
-            int it, nm, nc, nro, ntot;
-            bool reuse;
-            size_t cas, was, uas, tas, ccs, mms, cms, ras;
-            const DevModel* m0;
-            // the terms launches after the rollout launch and after the flush: arguments, models,
-            // engines with terms among the launch's (0: no launch)
-            size_t xas, xms, cxas, cxms;
-            int nx, ncx;
-        };
-        std::vector<Step> steps;
-        std::vector<int> prev_main;
-        size_t prev_mms = 0, prev_xms = 0;
-        int prev_nx = 0;
-        const int end = std::min(next + chunk, last_step + 1);
-        for (int it = next; it < end; ++it) {
-            Step st{};
-            st.it = it;
-            std::vector<int> main, cohort;
-            for (int p : live) {
-                if (g->e[p]->max_it >= it) main.push_back(p);
-                else if (g->e[p]->max_it == it - 1 && it >= 2) cohort.push_back(p);
-            }
-            st.nm = (int)main.size();
-            st.nc = (int)cohort.size();
-            st.cas = take(sizeof(CostArgs) * st.nm);
-            st.was = take(sizeof(WeightArgs) * st.nm);
-            st.uas = take(sizeof(UpdateArgs) * st.nm);
-            st.tas = take(sizeof(TrackArgs) * (st.nm + st.nc));
-            st.ccs = take(sizeof(CostArgs) * st.nc);
-            st.cms = take(sizeof(DevModel) * st.nc);
-            st.ras = e0->Kr > 0 ? take(sizeof(ReuseRowArgs) * st.nm) : 0;
-            const bool terms = g->nterms > 0;
-            st.xas = terms ? take(sizeof(TermsArgs) * st.nm) : 0;
-            st.cxas = terms ? take(sizeof(TermsArgs) * st.nc) : 0;
-            st.cxms = terms ? take(sizeof(TermsModel) * st.nc) : 0;
-            // the DevModel list of the rollout launch: once per chunk, again where an engine's
-            // max_iterations takes it out within the chunk
-            if (st.nm > 0 && main != prev_main) {
-                prev_mms = take(sizeof(DevModel) * st.nm);
-                DevModel* ms = (DevModel*)(hb + prev_mms);
-                for (int k = 0; k < st.nm; ++k) ms[k] = g->e[main[k]]->model;
-                if (terms) {
-                    prev_xms = take(sizeof(TermsModel) * st.nm);
-                    TermsModel* xs = (TermsModel*)(hb + prev_xms);
-                    prev_nx = 0;
-                    for (int k = 0; k < st.nm; ++k) {
-                        xs[k] = g->e[main[k]]->terms;
-                        prev_nx += g->e[main[k]]->terms_on ? 1 : 0;
-                    }
-                }
-                prev_main = main;
-            }
-            st.mms = prev_mms;
-            st.xms = prev_xms;
-            st.nx = st.nm > 0 ? prev_nx : 0;
-            if (st.nm > 0) st.m0 = &g->e[main[0]]->model;
-            CostArgs* cas = (CostArgs*)(hb + st.cas);
-            WeightArgs* was = (WeightArgs*)(hb + st.was);
-            UpdateArgs* uas = (UpdateArgs*)(hb + st.uas);
-            TrackArgs* tas = (TrackArgs*)(hb + st.tas);
-            ReuseRowArgs* ras = (ReuseRowArgs*)(hb + st.ras);
-            TermsArgs* xas = (TermsArgs*)(hb + st.xas);
-            for (int k = 0; k < st.nm; ++k) {
-                stomp_engine* e = g->e[main[k]];
-                // inside the optimize loop the noise / params rows are copied out of the pregen
-                // buffer (pregen blocks enqueued past a stop overwrite the ping-pong buffers), the
-                // weights read d_noise
-                if (e->pre_it != it) return gfail(g, STOMP_E_INVALID, "group pregen rows out of step");
-                const StagedIteration si = stage_iteration(e, it, false, cas[k], was[k], uas[k], ras + k);
-                if (terms) xas[k] = terms_args(e, cas[k]);
-                if (k == 0) {
-                    st.nro = si.nro;
-                    st.ntot = si.ntot;
-                    st.reuse = si.reuse;
-                } else if (si.nro != st.nro || si.ntot != st.ntot || si.reuse != st.reuse) {
-                    return gfail(g, STOMP_E_INVALID, "group engines out of step");
-                }
-                if (e->Kr > 0) after[main[k]][it - 1] = {e->reused_next, e->extra_added, e->row_set};
-                tas[k] = track_args(main[k]);
-            }
-            CostArgs* ccs = (CostArgs*)(hb + st.ccs);
-            DevModel* cms = (DevModel*)(hb + st.cms);
-            TermsArgs* cxas = (TermsArgs*)(hb + st.cxas);
-            TermsModel* cxms = (TermsModel*)(hb + st.cxms);
-            for (int k = 0; k < st.nc; ++k) {
-                stomp_engine* e = g->e[cohort[k]];
-                ccs[k] = noiseless_args(e);   // with K_r > 0 the extra rollout's rows too
-                cms[k] = e->model;
-                if (terms) {
-                    cxas[k] = terms_args(e, ccs[k]);
-                    cxms[k] = e->terms;
-                    st.ncx += e->terms_on ? 1 : 0;
-                }
-                tas[st.nm + k] = track_args(cohort[k]);
-            }
-            steps.push_back(st);
-        }
-        next = end;
-        if (used > g->opt_slot) return gfail(g, STOMP_E_INVALID, "group optimize staging overflow");
-        if (used && hipMemcpyAsync(db, hb, used, hipMemcpyHostToDevice, s) != hipSuccess)
-            return gfail(g, STOMP_E_DEVICE, "group argument upload failed");
-        for (const Step& st : steps) {
-            // with timing on for the group's first engine, its timers hold the group's launches
-            if (st.nc > 0) {
-                Timed tm(e0, T_NOISELESS, s);
-                launch_cost_group(g->e[0]->model, (const DevModel*)(db + st.cms), (const CostArgs*)(db + st.ccs), st.nc,
-                                  1, 0, s);
-            }
-            if (st.ncx > 0) {
-                Timed tm(e0, T_TERMS, s);
-                launch_terms_group((const TermsModel*)(db + st.cxms), (const TermsArgs*)(db + st.cxas), st.nc, 1, N,
-                                   g->terms_lds, s);
-            }
-            if (st.nm > 0) {
-                Timed tm(e0, T_COST, s);
-                launch_cost_group(*st.m0, (const DevModel*)(db + st.mms), (const CostArgs*)(db + st.cas), st.nm, st.nro,
-                                  K + st.ntot, s);
-            }
-            // the state-cost terms of both launches before the bookkeeping reads the noiseless
-            // rollouts' totals and constraints-satisfied flags
-            if (st.nx > 0) {
-                Timed tm(e0, T_TERMS, s);
-                launch_terms_group((const TermsModel*)(db + st.xms), (const TermsArgs*)(db + st.xas), st.nm, st.nro, N,
-                                   g->terms_lds, s);
-            }
-            // before this step's weights / update: a break decided on the previous iteration's
-            // noiseless rollout leaves theta where the reference leaves it
-            if (st.it >= 2) launch_track_group((const TrackArgs*)(db + st.tas), st.nm + st.nc, st.it - 2, J * N, s);
-            if (st.nm > 0) {
-                if (st.reuse) {
-                    // after the bookkeeping, as the engine's own loop: a stopped engine's reused
-                    // rows stay the ones of the iteration it stopped at
-                    Timed tm(e0, T_NOISE, s);
-                    launch_reuse_rows_group(shape, (const ReuseRowArgs*)(db + st.ras), st.nm, e0->K, e0->Kr, s);
-                }
-                {
-                    // (the step's own list: compacted, or a stopped engine a no-op at its flag)
-                    Timed tm(e0, T_WEIGHTS, s);
-                    if (g->ncum > 0) launch_cumulative_group((const WeightArgs*)(db + st.was), st.nm, J, N, K, s);
-                    launch_weights_group((const WeightArgs*)(db + st.was), st.nm, J, N, K, s);
-                }
-                {
-                    Timed tm(e0, T_UPDATE, s);
-                    launch_update_group(J, N, (const UpdateArgs*)(db + st.uas), st.nm, s);
-                }
-            }
-        }
-        if (hipMemcpyAsync(g->h_mirror + (size_t)slot * 2 * P, g->d_mirror, sizeof(int) * 2 * P, hipMemcpyDeviceToHost,
-                           s) != hipSuccess ||
-            hipEventRecord(g->opt_ev[slot], s) != hipSuccess)
-            return gfail(g, STOMP_E_DEVICE, "group read-back failed");
-        return 0;
-    };
+        if (!g->compact || g->e[p]->max_it > 0) o.live.push_back(p);
+    o.last_step = maxcap > 0 ? maxcap + 1 : 0;
+    optimize_enter(g);
+
+    // two chunks in flight: the host stages and enqueues one while the device runs the other, and
+    // reads the mirror of the older one
     int rc = 0, inflight = 0, head = 0;
     bool all_stopped = false;
     while (!all_stopped) {
-        while (inflight < 2 && next <= last_step) {
-            if ((rc = enqueue_chunk((head + inflight) & 1))) break;
+        while (inflight < 2 && o.next <= o.last_step) {
+            if ((rc = optimize_enqueue_chunk(o, (head + inflight) & 1))) break;
             ++inflight;
         }
         if (rc || inflight == 0) break;
@@ -773,61 +857,12 @@ int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_i
         const int* hm = g->h_mirror + (size_t)head * 2 * P;
         all_stopped = true;
         for (int p = 0; p < P; ++p) all_stopped = all_stopped && hm[2 * p] != 0;
-        if (g->compact) {
-            // the engines seen stopped leave every chunk staged from here on
-            std::vector<int> keep;
-            for (int p : live)
-                if (!hm[2 * p]) keep.push_back(p);
-            live.swap(keep);
-        }
+        if (g->compact)   // the engines seen stopped leave every chunk staged from here on
+            o.live.erase(std::remove_if(o.live.begin(), o.live.end(), [hm](int p) { return hm[2 * p] != 0; }), o.live.end());
         head ^= 1;
         --inflight;
     }
-    // the steps enqueued past an engine's stop were no-ops; the engines stopped at different
-    // iterations, so every engine leaves with no pregen rows held and nothing pending (the next
-    // run, the group's or the engine's own, makes its rows with a standalone pregen launch)
-    for (stomp_engine* e : g->e) {
-        e->pending_member = -1;
-        e->pre_it = -1;
-        e->rows_in_pre = false;
-    }
-    hipError_t err = hipGetLastError();
-    if (!rc && err != hipSuccess) rc = gfail(g, STOMP_E_DEVICE, hipGetErrorString(err));
-    for (int p = 0; p < P && !rc; ++p)
-        if (hipMemcpyAsync(&g->e[p]->h_track[2], g->e[p]->d_track, sizeof(DevTrack), hipMemcpyDeviceToHost, s) != hipSuccess)
-            rc = gfail(g, STOMP_E_DEVICE, "group read-back failed");
-    // later launches (iterate / run / eval) are not gated
-    launch_track_start_group(g->d_track_all, P, true, s);
-    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = gfail(g, STOMP_E_DEVICE, "group synchronize failed");
-    if (rc) return rc;
-    for (int p = 0; p < P; ++p) {
-        stomp_engine* e = g->e[p];
-        const DevTrack& t = e->h_track[2];
-        if (e->Kr > 0 && t.iterations > 0) {
-            // the steps staged past the engine's stop were no-ops on the device
-            const HostState& h = after[p][t.iterations - 1];
-            e->reused_next = h.reused_next;
-            e->extra_added = h.extra_added;
-            if (e->row_set != h.row_set) swap_row_sets(e);
-        }
-        if (costs_per_iteration && t.iterations > 0 &&
-            hipMemcpy(costs_per_iteration + (size_t)p * costs_stride, e->d_opt_costs, sizeof(double) * t.iterations,
-                      hipMemcpyDeviceToHost) != hipSuccess)
-            return gfail(g, STOMP_E_DEVICE, "group cost history read-back failed");
-        stomp_stats st;
-        st.iterations = t.iterations;
-        st.success = t.success;
-        st.success_iteration = t.success_iteration;
-        st.collision_success_iteration = t.collision_success_iteration;
-        st.last_improvement_iteration = t.last_improvement_iteration;
-        st.best_cost = t.best;
-        const double tick_s = e->wall_khz > 0 ? 1.0 / (1000.0 * e->wall_khz) : 0.0;
-        st.success_duration = t.success_iteration >= 0 ? (double)(t.t_success - t.t0) * tick_s : 0.0;
-        st.collision_success_duration =
-            t.collision_success_iteration >= 0 ? (double)(t.t_collision_success - t.t0) * tick_s : 0.0;
-        stats[p] = st;
-    }
-    return 0;
+    return optimize_finish(o, rc, stats, costs_per_iteration, costs_stride);
 }
 
 }  // extern "C"

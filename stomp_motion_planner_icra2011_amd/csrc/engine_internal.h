@@ -5,7 +5,8 @@
 //   engine.cpp           release, the launch helpers, enqueue_iteration, the C-ABI entry points
 //   engine_create.cpp    descriptor validation and stomp_engine_create's stages
 //   engine_exchange.cpp  the in-process group, the RCCL path, the collectives, calibration
-//   engine_group.cpp     stomp_group
+//   engine_group.cpp     stomp_group: one launcher of a grouped step (launch_step) and one arena of
+//                        staged arguments behind run, synchronize and optimize
 //   engine_retarget.cpp  stomp_engine_retarget and the part of it stomp_group_retarget shares
 //   sdf_build.cpp        the distance-field builders (does not include this header)
 #pragma once
@@ -340,6 +341,27 @@ struct Timed {
         }
     }
 };
+
+// staged argument arrays start at multiples of 256 bytes (engine_group.cpp's arena, the retarget
+// staging)
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// STOMPStatistics of an optimize loop from the engine's device-resident bookkeeping, read back
+inline stomp_stats stats_from_track(const stomp_engine* e, const DevTrack& t)
+{
+    stomp_stats s;
+    s.iterations = t.iterations;
+    s.success = t.success;
+    s.success_iteration = t.success_iteration;
+    s.collision_success_iteration = t.collision_success_iteration;
+    s.last_improvement_iteration = t.last_improvement_iteration;
+    s.best_cost = t.best;
+    const double tick_s = e->wall_khz > 0 ? 1.0 / (1000.0 * e->wall_khz) : 0.0;
+    s.success_duration = t.success_iteration >= 0 ? (double)(t.t_success - t.t0) * tick_s : 0.0;
+    s.collision_success_duration =
+        t.collision_success_iteration >= 0 ? (double)(t.t_collision_success - t.t0) * tick_s : 0.0;
+    return s;
+}
 
 // generateRollouts' sampling arguments of iteration it (policy_improvement_loop.cpp:155-160:
 // sigma_d * decay_d^(it - 1))

@@ -9,10 +9,6 @@
 
 using namespace stomp;
 
-namespace {
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-}  // namespace
-
 namespace stomp {
 
 size_t retarget_stage_bytes(int P, int J)

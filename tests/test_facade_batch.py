@@ -9,7 +9,8 @@ import pytest
 
 from oracle import pyoracle as po
 from tests import facade_util as fu
-from tests.test_gpu_group_optimize import INT_STATS, recipe
+from tests.group_util import INT_STATS
+from tests.test_gpu_group_optimize import recipe
 
 pytestmark = pytest.mark.gpu
 

@@ -13,7 +13,7 @@ from oracle import pyoracle as po
 from tests import facade_util as fu
 from tests.test_facade_batch import build_batch_driver
 from tests.test_gpu_group_cumulative import recipe
-from tests.test_gpu_group_optimize import INT_STATS
+from tests.group_util import INT_STATS
 
 pytestmark = pytest.mark.gpu
 

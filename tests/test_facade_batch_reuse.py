@@ -10,7 +10,7 @@ import pytest
 from oracle import pyoracle as po
 from tests import facade_util as fu
 from tests.test_facade_batch import build_batch_driver
-from tests.test_gpu_group_optimize import INT_STATS
+from tests.group_util import INT_STATS
 from tests.test_gpu_group_reuse import recipe
 
 pytestmark = pytest.mark.gpu

@@ -14,7 +14,7 @@ import pytest
 from oracle import pyoracle as po
 from stomp_motion_planner_icra2011_amd import problem as pb
 from tests import facade_util as fu
-from tests.test_gpu_group_optimize import INT_STATS
+from tests.group_util import INT_STATS
 from tests.test_gpu_group_terms import UPRIGHT_TOL, upright
 
 pytestmark = pytest.mark.gpu

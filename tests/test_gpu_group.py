@@ -11,25 +11,13 @@ from stomp_motion_planner_icra2011_amd import engine as eng
 from stomp_motion_planner_icra2011_amd import problem as pb
 from oracle import pyoracle as po
 from tests import model_zoo as mz
+from tests.group_util import FIELDS, Group, advance, assert_same, shelf_problems, state, variants
 
 pytestmark = pytest.mark.gpu
 
 
 def problems(P, K=64, grid=64):
-    base = pb.make_problem(grid_n=grid, num_rollouts=K, num_reused_rollouts=0)
-    rng = np.random.default_rng(5)
-    d = rng.uniform(-0.15, 0.15, (P, 2, base.J))
-    out = []
-    for i in range(P):
-        p = pb.make_problem(grid_n=grid, num_rollouts=K, num_reused_rollouts=0, seed=base.seed + 1 + i,
-                            start=list(base.start + d[i, 0]), goal=list(base.goal + d[i, 1]))
-        out.append(p)
-    return out
-
-
-def state(e):
-    return dict(theta=e.theta(), last=e.last_trajectory(), prob=e.rollouts("probabilities"),
-                state=e.rollouts("state_costs"), noise=e.rollouts("noise"), params=e.rollouts("params"))
+    return shelf_problems(P, K, 0, grid)
 
 
 @pytest.mark.parametrize("P,chunks", [(3, [(1, 4), (5, 3)]), (8, [(1, 6)])])
@@ -50,9 +38,8 @@ def test_group_matches_single_engines_and_oracles(P, chunks):
         o = po.Oracle(p)
         for it in range(1, total + 1):
             o.iterate(it)
-        a, b = state(ge), state(se)
-        for k in a:
-            np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+        a = state(ge, FIELDS)
+        assert_same(a, state(se, FIELDS), "against its own run,")
         np.testing.assert_array_equal(a["theta"], o.theta())
         np.testing.assert_array_equal(a["last"], o.last_trajectory())
         np.testing.assert_array_equal(a["prob"], o.rollouts("probabilities"))
@@ -100,30 +87,9 @@ def test_group_refusals():
 # can pick, update_body's ring over N, the bricked rollout kernel at both block widths, other robots,
 # engines with their own robots, fields and parameters, and the lifecycle of a group.
 
-FIELDS = ("theta", "last", "prob", "state", "noise", "params")
 # K -> the kernel of launch_weights_group (a group takes the row tiles at every K)
 GROUP_WEIGHTS = {12: "rows<256,8,4>", 20: "rows<256,8,4>", 65: "rows<256,8,4>", 128: "rows<256,8,4>",
                  129: "rows<256,4,4>", 257: "rows<512,4,4>", 513: "rows<512,4,8>", 1025: "rows<256,4,32>"}
-
-
-def variants(make, P, **kw):
-    """P distinct problems of one builder: own noise seed, start and goal offsets (none on a joint
-    whose limits coincide)."""
-    rng = np.random.default_rng(7)
-    out = []
-    for i in range(P):
-        p = make(**kw)
-        free = np.array([not (j.has_limits and j.min == j.max) for j in p.robot.joints], np.float64)
-        p.seed = p.seed + 1 + i
-        p.start = p.start + free * rng.uniform(-0.1, 0.1, p.J)
-        p.goal = p.goal + free * rng.uniform(-0.1, 0.1, p.J)
-        out.append(p)
-    return out
-
-
-def oracle_state(o):
-    return dict(theta=o.theta(), last=o.last_trajectory(), prob=o.rollouts("probabilities"),
-                state=o.rollouts("state_costs"), noise=o.rollouts("noise"), params=o.rollouts("params"))
 
 
 def group_line(capfd):
@@ -133,33 +99,9 @@ def group_line(capfd):
     return lines[-1]
 
 
-def advance(oracles, first, count):
-    for o in oracles:
-        for it in range(first, first + count):
-            o.iterate(it)
-
-
 def assert_against_oracles(engines, oracles):
     for i, (e, o) in enumerate(zip(engines, oracles)):
-        a, c = state(e), oracle_state(o)
-        for k in FIELDS:
-            np.testing.assert_array_equal(a[k], c[k], err_msg=f"engine {i} {k}")
-
-
-class Group:
-    """Engines of `ps` on one stream and their group."""
-
-    def __init__(self, ps):
-        self.ps = ps
-        self.stream = eng.Stream()
-        self.engines = [eng.Engine(p, stream=self.stream.ptr) for p in ps]
-        self.group = eng.EngineGroup(self.engines)
-
-    def close(self):
-        self.group.close()
-        for e in self.engines:
-            e.close()
-        self.stream.close()
+        assert_same(state(e, FIELDS), state(o, FIELDS), f"engine {i}")
 
 
 def assert_members(ps, engines, chunks, threads=1, oracles=None):
@@ -171,19 +113,16 @@ def assert_members(ps, engines, chunks, threads=1, oracles=None):
         for first, count in chunks:
             se.run(first, count)
         se.synchronize()
-        a, b = state(ge), state(se)
+        a = state(ge, FIELDS)
+        assert_same(a, state(se, FIELDS), f"engine {i} against its own run,")
         se.close()
-        for k in FIELDS:
-            np.testing.assert_array_equal(a[k], b[k], err_msg=f"engine {i} {k} against its own run")
         if oracles is None:
             o = po.Oracle(p, threads=threads)
             for it in range(1, total + 1):
                 o.iterate(it)
         else:
             o = oracles[i]
-        c = oracle_state(o)
-        for k in FIELDS:
-            np.testing.assert_array_equal(a[k], c[k], err_msg=f"engine {i} {k} against its oracle")
+        assert_same(a, state(o, FIELDS), f"engine {i} against its oracle,")
 
 
 def run_group(ps, chunks, threads=1):

@@ -16,51 +16,26 @@ import numpy as np
 import pytest
 
 from stomp_motion_planner_icra2011_amd import engine as eng
-from stomp_motion_planner_icra2011_amd import problem as pb
 from oracle import pyoracle as po
 from tests import model_zoo as mz
-from tests.test_gpu_group import FIELDS, advance, variants
-from tests.test_gpu_group_optimize import (assert_group, assert_spread, assert_twin, iterations, optimize_oracles)
+from tests import group_util as gu
+from tests.group_util import (CHUNKS, FIELDS, X_ROWS, advance, assert_group, assert_same, assert_spread, assert_twin,
+                              iterations, optimize_oracles, oracle_skips, shelf_problems, variants)
 
 pytestmark = pytest.mark.gpu
 
-ROWS = dict(prob="probabilities", state="state_costs", noise="noise", params="params", control="control_costs")
-X_ROWS = dict(x_params="x_params", x_noise="x_noise", x_control="x_control_costs", x_state="x_state_costs")
-assert set(FIELDS) <= set(ROWS) | {"theta", "last"}
+ROWS = FIELDS + ("control",)
 
 
-class Group:
+def Group(ps, state_terms=False, compact=None):
     """Engines of `ps` on one stream and their group, created accepting cumulative costs."""
-
-    def __init__(self, ps, state_terms=False, compact=None):
-        self.ps = ps
-        self.stream = eng.Stream()
-        self.engines = [eng.Engine(p, stream=self.stream.ptr) for p in ps]
-        self.group = eng.EngineGroup(self.engines, state_terms=state_terms, compact=compact, cumulative_costs=True)
-
-    def close(self):
-        self.group.close()
-        for e in self.engines:
-            e.close()
-        self.stream.close()
+    return gu.Group(ps, state_terms=state_terms, compact=compact, cumulative_costs=True)
 
 
 def state(x, reuse):
     """theta, the FIELDS rows and the control costs of an engine or an oracle; with K_r > 0 also the
     extra rollout's rows."""
-    out = dict(theta=x.theta(), last=x.last_trajectory())
-    for k, which in ROWS.items():
-        out[k] = x.rollouts(which)
-    if reuse:
-        for k, which in X_ROWS.items():
-            out[k] = x.rollouts(which)
-    return out
-
-
-def assert_same(a, b, tag):
-    assert set(a) == set(b)
-    for k in a:
-        np.testing.assert_array_equal(a[k], b[k], err_msg=f"{tag} {k}")
+    return gu.state(x, ROWS + X_ROWS if reuse else ROWS)
 
 
 def numpy_cumulative(e):
@@ -86,42 +61,19 @@ def cumulative(p):
     return bool(p.params.use_cumulative_costs)
 
 
-CHUNKS = [(1, 1), (2, 2), (4, 3)]   # the generate-all iteration alone; the second starts with a reusing one
-
-
 def run_in_chunks(ps, chunks=CHUNKS, threads=1, state_terms=False):
-    """After each chunk and a synchronize: every engine against a twin that made the same run calls
-    on its own and against its oracle after the same iterations; the cumulative rows of the engines
-    that have them against the twin's and numpy's."""
-    reuse = ps[0].params.num_reused_rollouts > 0
-    g = Group(ps, state_terms=state_terms)
-    twins = [eng.Engine(p) for p in ps]
-    oracles = [po.Oracle(p, threads=threads) for p in ps]
-    for first, count in chunks:
-        g.group.run(first, count)
-        g.group.synchronize()
-        advance(oracles, first, count)
-        for i, (p, ge, te, o) in enumerate(zip(ps, g.engines, twins, oracles)):
-            te.run(first, count)
-            te.synchronize()
-            tag = f"after ({first}, {count}): engine {i}"
-            a = state(ge, reuse)
-            assert_same(a, state(te, reuse), tag + " against its own run,")
-            assert_same(a, state(o, reuse), tag + " against its oracle,")
-            if cumulative(p):
-                assert_cumulative(ge, te, tag)
-    for t in twins:
-        t.close()
-    return g
+    """gu.run_in_chunks, and the cumulative rows of the engines that have them against the twin's
+    and numpy's."""
+    def cumulative_rows(p, ge, te, tag):
+        if cumulative(p):
+            assert_cumulative(ge, te, tag)
+    return gu.run_in_chunks(ps, chunks, threads, lambda qs: Group(qs, state_terms=state_terms), oracle_skips,
+                            cumulative_rows)
 
 
 def shelf(P, K, Kr, grid=64, **kw):
-    """tests/test_gpu_group_reuse.py's `problems` (the PR2 shelf), with cumulative costs."""
-    base = pb.make_problem(grid_n=grid, num_rollouts=K, num_reused_rollouts=Kr)
-    d = np.random.default_rng(5).uniform(-0.15, 0.15, (P, 2, base.J))
-    return [pb.make_problem(grid_n=grid, num_rollouts=K, num_reused_rollouts=Kr, seed=base.seed + 1 + i,
-                            start=list(base.start + d[i, 0]), goal=list(base.goal + d[i, 1]),
-                            use_cumulative_costs=True, **kw) for i in range(P)]
+    """The PR2 shelf problems of the run tests, with cumulative costs."""
+    return shelf_problems(P, K, Kr, grid, use_cumulative_costs=True, **kw)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -199,12 +151,11 @@ def freeze(d):
 def recipe(K=20, Kr=10, mixed=False):
     """tests/test_gpu_group_reuse.py's 16-problem recipe with cumulative costs (mixed: on for the even
     indices only); shared between the tests, never written."""
-    base = pb.make_problem(grid_n=64, num_rollouts=K, num_reused_rollouts=Kr)
-    d = np.random.default_rng(11).uniform(-0.15, 0.15, (16, 2, base.J))
-    return tuple(pb.make_problem(grid_n=64, num_rollouts=K, num_reused_rollouts=Kr, seed=base.seed + 1 + i,
-                                 start=list(base.start + d[i, 0]), goal=list(base.goal + d[i, 1]), max_iterations=60,
-                                 max_iterations_after_collision_free=2,
-                                 use_cumulative_costs=(i % 2 == 0) if mixed else True) for i in range(16))
+    ps = shelf_problems(16, K, Kr, rng_seed=11, max_iterations=60, max_iterations_after_collision_free=2,
+                        use_cumulative_costs=True)
+    for p in ps[1::2] if mixed else ():
+        p.params.use_cumulative_costs = False
+    return tuple(ps)
 
 
 @functools.lru_cache(maxsize=None)

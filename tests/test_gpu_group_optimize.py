@@ -4,7 +4,7 @@ lockstep through the grouped launches.  Every engine must end exactly where the 
 optimize() of its problem ends and where its own stomp_engine_optimize leaves it, bit for bit, with
 and without the compaction that takes stopped engines out of the launches.
 
-The PR2 recipe is tests/test_gpu_group.py's `problems` with default_rng(11): its 16 problems stop
+The PR2 recipe is tests/group_util.py's `shelf_problems` with default_rng(11): its 16 problems stop
 at well-spread iterations (each test asserts the spread it needs on the oracle's own counts)."""
 import functools
 
@@ -12,56 +12,23 @@ import numpy as np
 import pytest
 
 from stomp_motion_planner_icra2011_amd import engine as eng
-from stomp_motion_planner_icra2011_amd import problem as pb
-from oracle import pyoracle as po
 from tests import model_zoo as mz
+from tests.group_util import (FIELDS, Group, assert_group, assert_results_equal, assert_spread, assert_states_equal,
+                              assert_twin, continue_against_oracle, iterations, optimize_oracles, shelf_problems,
+                              twins_of, variants)
 
 pytestmark = pytest.mark.gpu
 
-INT_STATS = ("iterations", "success", "success_iteration", "collision_success_iteration",
-             "last_improvement_iteration")
-FIELDS = ("theta", "last", "prob", "state", "noise", "params")
+# what a K_r = 0 engine is compared on with its twin, and with its oracle after each further iteration
+# (at K_r = 0 the oracle holds no extra rollout's params / noise / control rows)
+TWIN_ROWS = FIELDS + ("best", "x_state")
+ITER_ROWS = FIELDS + ("control",)
 
 
 @functools.lru_cache(maxsize=None)
 def recipe(K, max_it, P=16):
     """The 16 PR2 shelf problems (shared between the tests, never written)."""
-    base = pb.make_problem(grid_n=64, num_rollouts=K, num_reused_rollouts=0)
-    d = np.random.default_rng(11).uniform(-0.15, 0.15, (P, 2, base.J))
-    return tuple(pb.make_problem(grid_n=64, num_rollouts=K, num_reused_rollouts=0, seed=base.seed + 1 + i,
-                                 start=list(base.start + d[i, 0]), goal=list(base.goal + d[i, 1]),
-                                 max_iterations=max_it, max_iterations_after_collision_free=2) for i in range(P))
-
-
-def variants(make, P, **kw):
-    """As tests/test_gpu_group.py: P distinct problems of one builder."""
-    rng = np.random.default_rng(7)
-    out = []
-    for i in range(P):
-        p = make(**kw)
-        free = np.array([not (j.has_limits and j.min == j.max) for j in p.robot.joints], np.float64)
-        p.seed = p.seed + 1 + i
-        p.start = p.start + free * rng.uniform(-0.1, 0.1, p.J)
-        p.goal = p.goal + free * rng.uniform(-0.1, 0.1, p.J)
-        out.append(p)
-    return out
-
-
-def snapshot(o):
-    """The oracle's optimize() of its problem, as read-only results."""
-    st, costs = o.optimize()
-    snap = dict(stats=tuple(int(getattr(st, k)) for k in INT_STATS), best_cost=float(st.best_cost),
-                costs=np.array(costs), best=o.best_trajectory(), last=o.last_trajectory(), theta=o.theta(),
-                x_state=o.rollouts("x_state_costs"))
-    for v in snap.values():
-        if isinstance(v, np.ndarray):
-            v.setflags(write=False)
-    return snap
-
-
-def optimize_oracles(ps):
-    oracles = [po.Oracle(p, threads=8) for p in ps]
-    return oracles, [snapshot(o) for o in oracles]
+    return tuple(shelf_problems(P, K, 0, rng_seed=11, max_iterations=max_it, max_iterations_after_collision_free=2))
 
 
 @functools.lru_cache(maxsize=None)
@@ -75,73 +42,6 @@ def pr2(K, max_it, idx):
 
 
 ALL16 = tuple(range(16))
-
-
-def iterations(snaps):
-    return [s["stats"][0] for s in snaps]
-
-
-def assert_spread(snaps, max_it):
-    its = iterations(snaps)
-    below = {n for n in its if n < max_it}
-    assert len(below) >= 4 and max_it in its, its
-
-
-class Group:
-    def __init__(self, ps):
-        self.ps = ps
-        self.stream = eng.Stream()
-        self.engines = [eng.Engine(p, stream=self.stream.ptr) for p in ps]
-        self.group = eng.EngineGroup(self.engines)
-
-    def close(self):
-        self.group.close()
-        for e in self.engines:
-            e.close()
-        self.stream.close()
-
-
-def assert_result(e, res, snap, tag):
-    st, costs = res
-    print(tag, "iterations", st.iterations, "oracle", snap["stats"][0])
-    assert tuple(int(getattr(st, k)) for k in INT_STATS) == snap["stats"], tag
-    assert st.best_cost == snap["best_cost"], tag
-    np.testing.assert_array_equal(costs, snap["costs"], err_msg=tag)
-    np.testing.assert_array_equal(e.best_trajectory(), snap["best"], err_msg=tag)
-    np.testing.assert_array_equal(e.last_trajectory(), snap["last"], err_msg=tag)
-    np.testing.assert_array_equal(e.theta(), snap["theta"], err_msg=tag)
-    np.testing.assert_array_equal(e.rollouts("x_state_costs"), snap["x_state"], err_msg=tag)
-
-
-def assert_group(g, results, snaps):
-    assert len(results) == len(snaps)
-    for i, (e, res, snap) in enumerate(zip(g.engines, results, snaps)):
-        assert_result(e, res, snap, f"engine {i}")
-
-
-def state(e):
-    return dict(theta=e.theta(), last=e.last_trajectory(), prob=e.rollouts("probabilities"),
-                state=e.rollouts("state_costs"), noise=e.rollouts("noise"), params=e.rollouts("params"),
-                best=e.best_trajectory(), x_state=e.rollouts("x_state_costs"))
-
-
-def assert_twin(ge, gres, te, tres, tag):
-    for k in INT_STATS + ("best_cost",):
-        assert getattr(gres[0], k) == getattr(tres[0], k), (tag, k)
-    np.testing.assert_array_equal(gres[1], tres[1], err_msg=tag)
-    a, b = state(ge), state(te)
-    for k in a:
-        np.testing.assert_array_equal(a[k], b[k], err_msg=f"{tag} {k}")
-
-
-def continue_against_oracle(o, e, first, count):
-    for it in range(first, first + count):
-        oc, ec = o.iterate(it), e.iterate(it)
-        assert ec[0] == oc[0] and ec[1] == oc[1], (it, ec, oc)
-        for f in ("params", "noise", "control_costs", "state_costs", "probabilities"):
-            np.testing.assert_array_equal(e.rollouts(f), o.rollouts(f), err_msg=f"iteration {it} {f}")
-        np.testing.assert_array_equal(e.theta(), o.theta(), err_msg=f"theta after iteration {it}")
-        np.testing.assert_array_equal(e.last_trajectory(), o.last_trajectory())
 
 
 def test_spread_by_collisions():
@@ -159,10 +59,10 @@ def test_spread_by_collisions():
     picks += [i for i in range(16) if i not in picks][: 4 - len(picks)]
     for i in picks:
         twin = eng.Engine(ps[i])
-        assert_twin(g.engines[i], results[i], twin, twin.optimize(), f"engine {i} against its twin")
+        assert_twin(g.engines[i], results[i], twin, twin.optimize(), f"engine {i} against its twin", TWIN_ROWS)
         twin.close()
     for i, (o, e) in enumerate(zip(oracles, g.engines)):
-        continue_against_oracle(o, e, its[i] + 1, 2)
+        continue_against_oracle(o, e, its[i] + 1, 2, ITER_ROWS)
     g.close()
 
 
@@ -209,24 +109,6 @@ def test_everyone_stops_early():
 LIFECYCLE = (1, 2, 8, 11)
 
 
-def twins_of(ps):
-    return [eng.Engine(p) for p in ps]
-
-
-def assert_states_equal(g, twins, tag):
-    for i, (ge, te) in enumerate(zip(g.engines, twins)):
-        a, b = state(ge), state(te)
-        for k in a:
-            np.testing.assert_array_equal(a[k], b[k], err_msg=f"{tag}: engine {i} {k}")
-
-
-def assert_results_equal(gres, tres, tag):
-    for i, (a, b) in enumerate(zip(gres, tres)):
-        for k in INT_STATS + ("best_cost",):
-            assert getattr(a[0], k) == getattr(b[0], k), (tag, i, k)
-        np.testing.assert_array_equal(a[1], b[1], err_msg=f"{tag}: engine {i} costs")
-
-
 def test_lifecycle_run_then_optimize():
     ps = [recipe(20, 60)[i] for i in LIFECYCLE]
     g, twins = Group(ps), twins_of(ps)
@@ -236,7 +118,7 @@ def test_lifecycle_run_then_optimize():
         t.run(1, 3)
     tres = [t.optimize() for t in twins]
     assert_results_equal(gres, tres, "run then optimize")
-    assert_states_equal(g, twins, "run then optimize")
+    assert_states_equal(g, twins, "run then optimize", TWIN_ROWS)
     g.close()
 
 
@@ -251,7 +133,7 @@ def test_lifecycle_optimize_then_run():
         t.run(61, 2)
         t.synchronize()
     assert_results_equal(gres, tres, "optimize then run")
-    assert_states_equal(g, twins, "optimize then run")
+    assert_states_equal(g, twins, "optimize then run", TWIN_ROWS)
     g.close()
 
 
@@ -263,7 +145,7 @@ def test_lifecycle_optimize_twice():
     t2 = [t.optimize() for t in twins]
     assert_results_equal(g1, t1, "first optimize")
     assert_results_equal(g2, t2, "second optimize")
-    assert_states_equal(g, twins, "optimize twice")
+    assert_states_equal(g, twins, "optimize twice", TWIN_ROWS)
     g.close()
 
 

@@ -14,71 +14,22 @@ import numpy as np
 import pytest
 
 from stomp_motion_planner_icra2011_amd import engine as eng
-from stomp_motion_planner_icra2011_amd import problem as pb
 from oracle import pyoracle as po
 from tests import model_zoo as mz
-from tests.test_gpu_group import FIELDS, Group, advance, variants
-from tests.test_gpu_group_optimize import (INT_STATS, assert_group, assert_results_equal, assert_spread, assert_twin,
-                                           iterations, optimize_oracles, twins_of)
+from tests.group_util import (FULL, ROW_NAMES, X_ROWS, Group, advance, assert_group, assert_results_equal, assert_same,
+                              assert_spread, assert_states_equal, assert_twin, close_all, continue_against_oracle,
+                              iterations, optimize_oracles, run_in_chunks, shelf_problems, state, twins_of, variants)
 
 pytestmark = pytest.mark.gpu
 
-ROWS = dict(theta=None, last=None, prob="probabilities", state="state_costs", noise="noise", params="params",
-            control="control_costs", x_params="x_params", x_noise="x_noise", x_control="x_control_costs",
-            x_state="x_state_costs")
-assert set(FIELDS) <= set(ROWS)
-
-
-def state(x):
-    """The six FIELDS of tests/test_gpu_group.py, the control costs and the extra rollout's rows, of
-    an engine or an oracle."""
-    out = dict(theta=x.theta(), last=x.last_trajectory())
-    for k, which in ROWS.items():
-        if which is not None:
-            out[k] = x.rollouts(which)
-    return out
-
-
-def assert_same(a, b, tag):
-    for k in ROWS:
-        np.testing.assert_array_equal(a[k], b[k], err_msg=f"{tag} {k}")
-
 
 def problems(P, K, Kr, grid=64):
-    """tests/test_gpu_group.py's `problems`, with reuse."""
-    base = pb.make_problem(grid_n=grid, num_rollouts=K, num_reused_rollouts=Kr)
-    d = np.random.default_rng(5).uniform(-0.15, 0.15, (P, 2, base.J))
-    return [pb.make_problem(grid_n=grid, num_rollouts=K, num_reused_rollouts=Kr, seed=base.seed + 1 + i,
-                            start=list(base.start + d[i, 0]), goal=list(base.goal + d[i, 1])) for i in range(P)]
-
-
-CHUNKS = [(1, 1), (2, 2), (4, 3)]   # the generate-all iteration alone; the second starts with a reusing one
-
-
-def run_in_chunks(ps, chunks=CHUNKS, threads=1):
-    """After each chunk and a synchronize: every engine against a twin that made the same run calls
-    on its own and against its oracle after the same iterations."""
-    g = Group(ps)
-    twins = [eng.Engine(p) for p in ps]
-    oracles = [po.Oracle(p, threads=threads) for p in ps]
-    for first, count in chunks:
-        g.group.run(first, count)
-        g.group.synchronize()
-        advance(oracles, first, count)
-        for i, (ge, te, o) in enumerate(zip(g.engines, twins, oracles)):
-            te.run(first, count)
-            te.synchronize()
-            a = state(ge)
-            assert_same(a, state(te), f"after ({first}, {count}): engine {i} against its own run,")
-            assert_same(a, state(o), f"after ({first}, {count}): engine {i} against its oracle,")
-    for t in twins:
-        t.close()
-    g.close()
+    return shelf_problems(P, K, Kr, grid)
 
 
 @pytest.mark.parametrize("K,Kr", [(20, 10), (10, 5), (12, 11), (12, 1), (65, 8)])
 def test_run_matches_single_engines_and_oracles(K, Kr):
-    run_in_chunks(problems(3, K, Kr), threads=8 if K > 20 else 1)
+    run_in_chunks(problems(3, K, Kr), threads=8 if K > 20 else 1).close()
 
 
 @pytest.mark.parametrize("name,waypoints", [("chain5", 40), ("fork12", 40), ("hand9", 40), ("chain5", 10),
@@ -88,7 +39,7 @@ def test_reuse_kernel_shapes(name, waypoints):
     # 128, then 129 (the first 1024-thread instantiation) and 199
     ps = variants(mz.ZOO[name], 3, waypoints=waypoints)
     assert (ps[0].params.num_rollouts, ps[0].params.num_reused_rollouts) == (12, 5) and ps[0].N == waypoints - 1
-    run_in_chunks(ps)
+    run_in_chunks(ps).close()
 
 
 def test_one_reuse_launch_per_iteration_not_one_per_engine():
@@ -114,11 +65,7 @@ def test_one_reuse_launch_per_iteration_not_one_per_engine():
 @functools.lru_cache(maxsize=None)
 def recipe(K=20, Kr=10, max_it=60, P=16):
     """tests/test_gpu_group_optimize.py's recipe with reuse (shared between the tests, never written)."""
-    base = pb.make_problem(grid_n=64, num_rollouts=K, num_reused_rollouts=Kr)
-    d = np.random.default_rng(11).uniform(-0.15, 0.15, (P, 2, base.J))
-    return tuple(pb.make_problem(grid_n=64, num_rollouts=K, num_reused_rollouts=Kr, seed=base.seed + 1 + i,
-                                 start=list(base.start + d[i, 0]), goal=list(base.goal + d[i, 1]),
-                                 max_iterations=max_it, max_iterations_after_collision_free=2) for i in range(P))
+    return tuple(shelf_problems(P, K, Kr, rng_seed=11, max_iterations=max_it, max_iterations_after_collision_free=2))
 
 
 @functools.lru_cache(maxsize=None)
@@ -131,8 +78,6 @@ def pr2(idx):
 
 
 ALL16 = tuple(range(16))
-X_ROWS = ("x_params", "x_noise", "x_control_costs", "x_state_costs")
-ITER_ROWS = ("params", "noise", "control_costs", "state_costs", "probabilities") + X_ROWS
 
 
 def assert_stops_spread(snaps):
@@ -144,19 +89,7 @@ def assert_stops_spread(snaps):
 
 
 def full_state(e):
-    out = state(e)
-    out["best"] = e.best_trajectory()
-    return out
-
-
-def continue_against_oracle(o, e, first, count):
-    for it in range(first, first + count):
-        oc, ec = o.iterate(it), e.iterate(it)
-        assert ec[0] == oc[0] and ec[1] == oc[1], (it, ec, oc)
-        for f in ITER_ROWS:
-            np.testing.assert_array_equal(e.rollouts(f), o.rollouts(f), err_msg=f"iteration {it} {f}")
-        np.testing.assert_array_equal(e.theta(), o.theta(), err_msg=f"theta after iteration {it}")
-        np.testing.assert_array_equal(e.last_trajectory(), o.last_trajectory())
+    return state(e, FULL)
 
 
 def test_optimize_stops_spread():
@@ -176,9 +109,6 @@ def test_optimize_stops_spread():
         twin = eng.Engine(ps[i])
         tres = twin.optimize()
         assert_twin(g.engines[i], results[i], twin, tres, f"engine {i} against its twin")
-        a, b = full_state(g.engines[i]), full_state(twin)
-        for k in a:
-            np.testing.assert_array_equal(a[k], b[k], err_msg=f"engine {i} against its twin {k}")
         twin.close()
     # a wrongly restored row_set / reused_next / extra_added shows here
     for i, (o, e) in enumerate(zip(oracles, g.engines)):
@@ -201,7 +131,7 @@ def test_per_engine_caps(robot):
     assert_group(g, results, snaps)
     for i, (e, o) in enumerate(zip(g.engines, oracles)):
         for f in X_ROWS:   # the extra rollout's rows of the engines the flush of their cap ends
-            np.testing.assert_array_equal(e.rollouts(f), o.rollouts(f), err_msg=f"engine {i} {f}")
+            np.testing.assert_array_equal(e.rollouts(ROW_NAMES[f]), o.rollouts(ROW_NAMES[f]), err_msg=f"engine {i} {f}")
     g.close()
 
 
@@ -217,19 +147,6 @@ def test_compaction_on_and_off(monkeypatch, compact):
 
 
 LIFECYCLE = (1, 2, 8, 11)
-
-
-def assert_states_equal(g, twins, tag):
-    for i, (ge, te) in enumerate(zip(g.engines, twins)):
-        a, b = full_state(ge), full_state(te)
-        for k in a:
-            np.testing.assert_array_equal(a[k], b[k], err_msg=f"{tag}: engine {i} {k}")
-
-
-def close_all(g, twins):
-    for t in twins:
-        t.close()
-    g.close()
 
 
 def test_lifecycle_run_then_optimize():
@@ -286,9 +203,7 @@ def test_lifecycle_a_members_own_iteration_puts_the_group_out_of_step():
         g.group.run(5, 2)
     assert "error -1" in str(ei.value) and "not at the same iteration state" in str(ei.value), str(ei.value)
     for i, (e, b) in enumerate(zip(g.engines, before)):   # no engine touched
-        a = full_state(e)
-        for k in a:
-            np.testing.assert_array_equal(a[k], b[k], err_msg=f"engine {i} {k}")
+        assert_same(full_state(e), b, f"engine {i}")
     for t in twins:
         t.synchronize()
     assert_states_equal(g, twins, "after the refused run")

@@ -23,43 +23,19 @@ from stomp_motion_planner_icra2011_amd import engine as eng
 from stomp_motion_planner_icra2011_amd import problem as pb
 from oracle import pyoracle as po
 from tests import model_zoo as mz
-from tests.test_gpu_group import advance, variants
-from tests.test_gpu_group_optimize import (INT_STATS, assert_result, assert_results_equal, iterations,
-                                           optimize_oracles, twins_of)
-from tests.test_gpu_group_reuse import CHUNKS, ROWS, full_state, state
+from tests import group_util as gu
+from tests.group_util import (CHUNKS, FULL, Group, advance, assert_result, assert_results_equal, assert_same,
+                              assert_states_equal, close_all, distinct, iterations, optimize_oracles, oracle_skips, state,
+                              twins_of, variants)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# addExtraRollouts exists only with reuse: at K_r = 0 the oracle holds no extra rollout's
-# params / noise / control rows (the engines are still compared with their twins on them)
-NO_REUSE_ORACLE_SKIPS = ("x_params", "x_noise", "x_control")
 
 
-class TermsGroup:
+def TermsGroup(ps, compact=None):
     """Engines of `ps` on one stream and their group, created with state_terms = 1."""
-
-    def __init__(self, ps, compact=None):
-        self.ps = ps
-        self.stream = eng.Stream()
-        self.engines = [eng.Engine(p, stream=self.stream.ptr) for p in ps]
-        self.group = eng.EngineGroup(self.engines, state_terms=True, compact=compact)
-
-    def close(self):
-        self.group.close()
-        for e in self.engines:
-            e.close()
-        self.stream.close()
-
-
-def assert_same(a, b, tag, skip=()):
-    for k in ROWS:
-        if k not in skip:
-            np.testing.assert_array_equal(a[k], b[k], err_msg=f"{tag} {k}")
-
-
-def oracle_skips(p):
-    return NO_REUSE_ORACLE_SKIPS if p.params.num_reused_rollouts == 0 else ()
+    return Group(ps, state_terms=True, compact=compact)
 
 
 def terms_group_line(err):
@@ -70,24 +46,7 @@ def terms_group_line(err):
 
 
 def run_in_chunks(ps, chunks=CHUNKS, threads=1):
-    """After each chunk and a synchronize: every engine against a twin that made the same run calls
-    on its own and against its oracle after the same iterations."""
-    g = TermsGroup(ps)
-    twins = twins_of(ps)
-    oracles = [po.Oracle(p, threads=threads) for p in ps]
-    for first, count in chunks:
-        g.group.run(first, count)
-        g.group.synchronize()
-        advance(oracles, first, count)
-        for i, (ge, te, o) in enumerate(zip(g.engines, twins, oracles)):
-            te.run(first, count)
-            te.synchronize()
-            a = state(ge)
-            assert_same(a, state(te), f"after ({first}, {count}): engine {i} against its own run,")
-            assert_same(a, state(o), f"after ({first}, {count}): engine {i} against its oracle,", oracle_skips(ps[i]))
-    for t in twins:
-        t.close()
-    g.close()
+    gu.run_in_chunks(ps, chunks, threads, TermsGroup, oracle_skips).close()
 
 
 def terms_robot(name):
@@ -114,15 +73,8 @@ def test_run_matches_single_engines_and_oracles(name, Kr):
 def mixed4(K=12, Kr=5):
     kw = dict(K=K, Kr=Kr, max_iterations=12, max_iterations_after_collision_free=2)
     make = mz.TERMS_ZOO["chain5"]
-    ps = [make(torque=0.001, **kw), make(torque=0.0, **kw), make(torque=0.001, constrained=False, **kw),
-          make(torque=0.0, constrained=False, **kw)]
-    rng = np.random.default_rng(7)
-    for i, p in enumerate(ps):
-        free = np.array([not (j.has_limits and j.min == j.max) for j in p.robot.joints], np.float64)
-        p.seed = p.seed + 1 + i
-        p.start = p.start + free * rng.uniform(-0.1, 0.1, p.J)
-        p.goal = p.goal + free * rng.uniform(-0.1, 0.1, p.J)
-    return ps
+    return distinct([make(torque=0.001, **kw), make(torque=0.0, **kw), make(torque=0.001, constrained=False, **kw),
+                     make(torque=0.0, constrained=False, **kw)])
 
 
 def test_mixed_group_each_engine_its_own_terms(monkeypatch, capfd):
@@ -160,13 +112,8 @@ def test_mixed_group_each_engine_its_own_terms(monkeypatch, capfd):
     gres = g.group.optimize()
     tres = [t.optimize() for t in twins]
     assert_results_equal(gres, tres, "mixed optimize")
-    for i, (ge, te) in enumerate(zip(g.engines, twins)):
-        a, b = full_state(ge), full_state(te)
-        for k in a:
-            np.testing.assert_array_equal(a[k], b[k], err_msg=f"mixed optimize: engine {i} {k}")
-    for t in twins:
-        t.close()
-    g.close()
+    assert_states_equal(g, twins, "mixed optimize")
+    close_all(g, twins)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -326,9 +273,7 @@ def test_optimize_stop_rule_depends_on_the_constraints():
         twin = eng.Engine(ps[i])
         tres = twin.optimize()
         assert_results_equal([results[i]], [tres], f"engine {i} against its twin")
-        a, b = full_state(g.engines[i]), full_state(twin)
-        for k in a:
-            np.testing.assert_array_equal(a[k], b[k], err_msg=f"engine {i} against its twin {k}")
+        assert_same(state(g.engines[i], FULL), state(twin, FULL), f"engine {i} against its twin")
         np.testing.assert_array_equal(g.engines[i].best_torques(), twin.best_torques())
         twin.close()
     # the engines go on from where the loop left them (the restored reuse state shows here)
@@ -391,9 +336,7 @@ def test_torque_only_optimize_with_best_torques():
         assert np.all(tq > 0.0)
         np.testing.assert_array_equal(e.best_torques(), tq, err_msg=f"engine {i} best_torques")
         np.testing.assert_array_equal(t.best_torques(), tq, err_msg=f"twin {i} best_torques")
-        a, b = full_state(e), full_state(t)
-        for k in a:
-            np.testing.assert_array_equal(a[k], b[k], err_msg=f"engine {i} against its twin {k}")
+        assert_same(state(e, FULL), state(t, FULL), f"engine {i} against its twin")
         t.close()
     g.close()
 
@@ -423,19 +366,6 @@ def test_one_terms_launch_per_grouped_launch_not_one_per_engine():
 # ------------------------------------------------------------------------------------------------
 # 9. lifecycle
 
-def assert_states_equal(g, twins, tag):
-    for i, (ge, te) in enumerate(zip(g.engines, twins)):
-        a, b = full_state(ge), full_state(te)
-        for k in a:
-            np.testing.assert_array_equal(a[k], b[k], err_msg=f"{tag}: engine {i} {k}")
-
-
-def close_all(g, twins):
-    for t in twins:
-        t.close()
-    g.close()
-
-
 def lifecycle_problems():
     return variants(mz.TERMS_ZOO["chain5"], 3, max_iterations=10, max_iterations_after_collision_free=2)
 
@@ -447,14 +377,12 @@ def test_lifecycle_a_members_own_iteration_puts_the_group_out_of_step():
     for t in twins:
         t.run(1, 3)
     assert g.engines[2].iterate(4) == twins[2].iterate(4)      # its own k_terms
-    before = [full_state(e) for e in g.engines]
+    before = [state(e, FULL) for e in g.engines]
     with pytest.raises(RuntimeError) as ei:
         g.group.run(5, 2)
     assert "error -1" in str(ei.value) and "not at the same iteration state" in str(ei.value), str(ei.value)
     for i, (e, b) in enumerate(zip(g.engines, before)):   # no engine touched
-        a = full_state(e)
-        for k in a:
-            np.testing.assert_array_equal(a[k], b[k], err_msg=f"engine {i} {k}")
+        assert_same(state(e, FULL), b, f"engine {i}")
     # the others catch up with their own iterate, then the group runs again
     for i in (0, 1):
         assert g.engines[i].iterate(4) == twins[i].iterate(4)

@@ -16,13 +16,12 @@ from stomp_motion_planner_icra2011_amd import problem as pb
 from oracle import pyoracle as po
 from tests import model_zoo as mz
 from tests import rank_util as ru
+from tests.group_util import CHUNKS, INT_STATS, Group, assert_same
 
 pytestmark = pytest.mark.gpu
 
 ROWS = ("params", "noise", "control_costs", "state_costs", "probabilities")
 X_ROWS = ("x_params", "x_noise", "x_control_costs", "x_state_costs")
-INT_STATS = ("iterations", "success", "success_iteration", "collision_success_iteration",
-             "last_improvement_iteration")
 SHORT = dict(max_iterations=8, max_iterations_after_collision_free=2)
 
 
@@ -56,12 +55,6 @@ def rows(x, reuse):
     for k in ROWS + (X_ROWS if reuse else X_ROWS[-1:]):
         out[k] = x.rollouts(k)
     return out
-
-
-def assert_same(a, b, tag):
-    assert set(a) == set(b)
-    for k in a:
-        np.testing.assert_array_equal(a[k], b[k], err_msg=f"{tag}: {k}")
 
 
 def follow(x, reuse):
@@ -425,19 +418,6 @@ def test_with_state_terms_and_cumulative_costs(which):
 # ------------------------------------------------------------------------------------------------
 # 7. groups
 
-class Group:
-    def __init__(self, ps, **kw):
-        self.stream = eng.Stream()
-        self.engines = [eng.Engine(p, stream=self.stream.ptr) for p in ps]
-        self.group = eng.EngineGroup(self.engines, **kw)
-
-    def close(self):
-        self.group.close()
-        for e in self.engines:
-            e.close()
-        self.stream.close()
-
-
 def strip(q, terms=False, cumulative=False):
     if terms:
         q = dataclasses.replace(q, orientation_constraints=[],
@@ -471,7 +451,6 @@ def group_problems(variant, Kr):
 
 
 GROUP_CASES = [("plain", 0), ("plain", 5), ("terms", 5), ("cumulative", 5), ("cumulative", 0), ("zoo", 5)]
-CHUNKS = [(1, 1), (2, 2), (4, 3)]
 
 
 @pytest.mark.parametrize("variant,Kr", GROUP_CASES)
