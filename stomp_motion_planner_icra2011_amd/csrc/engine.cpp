@@ -174,6 +174,9 @@ int enqueue_iteration(stomp_engine* e, int it, bool pipelined)
 {
     if (e->comm_aborted) return fail(e, STOMP_E_COMM, "%s", e->comm_msg.c_str());
     e->cur_it = it;
+    // setRolloutCosts with the loop's weight (policy_improvement_loop.cpp:173): every row of this
+    // iteration is priced with it, and a stomp_pi_add_extra_rollouts after it prices with it too
+    e->pi_weight = e->w_smooth;
     const int member = it - 1;
     const bool fused = e->J <= 16;   // rollout_project: at most four 4-joint column groups
     // With fused noise the reuse step runs after the rollout launch: the generated rows go to
@@ -222,7 +225,7 @@ int enqueue_iteration(stomp_engine* e, int it, bool pipelined)
     // would lengthen the launch)
     const int spec_nro = num_gen + (e->pending_member >= 0 ? 1 : 0);
     const int spec_extra = (pre ? e->rows : 0) + e->K + (e->K + 1);
-    const bool spec = reuse_late && e->spec_on && e->world == 1 && launch_reuse_pick_ok(na, e->K, e->Kr) &&
+    const bool spec = reuse_late && e->spec_on && !e->x_foreign && e->world == 1 && launch_reuse_pick_ok(na, e->K, e->Kr) &&
                       spec_nro + spec_extra <= e->model.cus &&
                       rollout_split_pieces(e->model, spec_nro, spec_extra, true) > 0;
     // Task::execute for the generated rollouts of this shard (+ the pending noiseless rollout)
@@ -362,6 +365,7 @@ int enqueue_iteration(stomp_engine* e, int it, bool pipelined)
         // control rows (x_ctl) before the next reuse ranking reads them
         e->extra_added = true;
     }
+    e->x_foreign = false;   // the extra rollout is this iteration's noiseless rollout of theta
     hipError_t st = hipGetLastError();
     if (st != hipSuccess)
         return fail(e, STOMP_E_DEVICE, "kernel launch failed: %s%s%s", hipGetErrorString(st),
@@ -414,6 +418,7 @@ int stomp_engine_set_theta(stomp_engine* e, const double* theta)
     flush_noiseless(e);   // a pending noiseless rollout belongs to the theta being replaced
     HIP_TRY(e, hipMemcpyAsync(e->d_theta, theta, sizeof(double) * e->J * e->N, hipMemcpyHostToDevice, e->stream));
     SYNC_TRY(e);
+    e->x_foreign = true;   // the extra rollout keeps the parameters it was added with
     return 0;
 }
 
@@ -748,6 +753,7 @@ int stomp_pi_add_extra_rollouts(stomp_engine* e, int32_t num, const double* para
     HIP_TRY(e, hipGetLastError());
     SYNC_TRY(e);   // nz is a pageable host buffer
     e->extra_added = true;
+    e->x_foreign = true;
     return 0;
 }
 

@@ -322,6 +322,8 @@ StagedIteration stage_iteration(stomp_engine* e, int it, bool keep_in_pre, CostA
     ua_out = UpdateArgs{e->d_MT, e->d_u, e->d_theta, e->d_stop};
     e->pending_member = it - 1;
     if (e->Kr > 0) e->extra_added = true;   // addExtraRollouts: the noiseless rollout pending now
+    e->x_foreign = false;
+    e->pi_weight = e->w_smooth;   // (enqueue_iteration's)
     return StagedIteration{ca.num_noisy + (ca.x_params ? 1 : 0), ca.tot_rows, reuse};
 }
 

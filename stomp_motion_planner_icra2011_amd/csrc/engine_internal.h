@@ -156,6 +156,10 @@ struct stomp_engine {
     double *d_Rb = nullptr, *d_RinvT = nullptr;
     unsigned char *h_rt = nullptr, *d_rt = nullptr;
     bool reused_next = false, extra_added = false;
+    // the extra rollout's params are not the current theta (stomp_engine_set_theta after its
+    // noiseless rollout, stomp_pi_add_extra_rollouts with rows of the caller's): the next reuse step
+    // cannot price that candidate ahead as theta + 0 and takes the reused rows' kernel
+    bool x_foreign = false;
     int pending_member = -1;   // iteration_ of a noiseless rollout of theta not evaluated yet
     double *d_mm = nullptr, *d_psum_part = nullptr, *d_psum_all = nullptr, *d_u_part = nullptr, *d_u_all = nullptr;
     int K_gen = 0;

@@ -82,6 +82,7 @@ int retarget_engines(stomp_engine* const* es, int P, const double* starts, const
         e->rows_eps = nullptr;
         e->reused_next = false;
         e->extra_added = false;
+        e->x_foreign = false;
         e->K_gen = 0;
         e->pi_weight = e->w_smooth;
         e->cur_it = -1;

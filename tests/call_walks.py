@@ -1,0 +1,969 @@
+"""Seeded call-sequence walks (tests/CALL_WALKS.md): scripts over the public API, the bookkeeping that
+keeps them valid, and the pairs that give one script to an engine (or a group, or two ranks) and to
+the CPU oracle.  A plain module like group_util.py: it holds no test and no cached oracle.
+
+A script is a list of plain tuples, e.g. ("run", 3, 2) or ("execute", rows_seed, nrows, member).
+make_script(mode, seed, length) makes one from numpy.random.default_rng; it uses no GPU and no oracle
+and tracks only what keeps the calls valid (the classes Book / GroupBook / RankBook below).  The walk
+is biased towards ordered pairs of op kinds that the scripts of the seeds before it have not shown,
+so a mode's census (tests/test_call_walks.py) closes in few seeds: make_script(mode, s) therefore
+walks the seeds 0 .. s in turn and returns the last script.
+
+replay(mode, script, pair) runs a literal script.  A pair compares only what an op returns
+(assert_array_equal / ==, no tolerance); state is read by the `observe` ops alone, at the random
+points where the walk put them.  Every assertion message carries the mode, the failing op's index
+and the script up to that op as a Python literal.
+"""
+import copy
+import ctypes as C
+import dataclasses
+
+import numpy as np
+
+from oracle import pyoracle as po
+from stomp_motion_planner_icra2011_amd import problem as pb
+from tests import group_util as gu
+from tests import model_zoo as mz
+from tests import pi_steps_util as su
+
+try:   # the CPU tests make scripts and run oracles without the engine library
+    from stomp_motion_planner_icra2011_amd import engine as eng
+except Exception:   # pragma: no cover
+    eng = None
+
+# ---------------------------------------------------------------------------- what observe reads
+X_KEYS = ("x_params", "x_noise", "x_control", "x_state")
+ROW_KEYS = ("prob", "state", "noise", "params", "control")
+ALWAYS = ("theta", "last", "best")          # defined from creation on (tests/RETARGET.md: created())
+OBS_ORDER = ALWAYS + ROW_KEYS + X_KEYS + ("cumulative",)
+FLUSHING = ("last", "best") + X_KEYS        # reads that evaluate a pending noiseless rollout first
+
+
+def _get(x, key):
+    if key == "theta":
+        return x.theta()
+    if key == "last":
+        return x.last_trajectory()
+    if key == "best":
+        return x.best_trajectory()
+    return x.rollouts(gu.ROW_NAMES[key])
+
+
+def numpy_cumulative(e):
+    """GROUP_CUMULATIVE.md: one add per element, then the suffix sums t = N - 2 .. 0, on the engine's
+    own state and control rows."""
+    c = e.rollouts("state_costs")[:, None, :] + e.rollouts("control_costs")
+    for t in range(c.shape[2] - 2, -1, -1):
+        c[:, :, t] += c[:, :, t + 1]
+    return c
+
+
+def moved(p, k, span=0.3):
+    """problem p with another start, goal and seed (no offset on a joint whose limits coincide)."""
+    rng = np.random.default_rng(4100 + k)
+    f = np.array([not (j.has_limits and j.min == j.max) for j in p.robot.joints], np.float64)
+    return dataclasses.replace(p, start=p.start + f * rng.uniform(-span, span, p.J),
+                               goal=p.goal + f * rng.uniform(-span, span, p.J), seed=p.seed + 2000 + k)
+
+
+def scene_objects(p, extra):
+    """The problem's boxes as collision objects; extra: one more box beside the default trajectory."""
+    objs = [pb.SceneObject(pb.SHAPE_BOX, tuple(b.center), (0.0, 0.0, 0.0, 1.0), tuple(b.dims)) for b in p.boxes]
+    if extra:
+        mid = pb.sphere_positions(p.robot, p.spheres, 0.5 * (p.start + p.goal))[len(p.spheres) // 3]
+        objs.append(pb.SceneObject(pb.SHAPE_BOX, tuple(mid + np.array([0.03, -0.02, 0.05])), (0.0, 0.0, 0.0, 1.0),
+                                   (0.09, 0.07, 0.11)))
+    return objs
+
+
+def has_terms(p):
+    return bool(p.orientation_constraints) or p.params.torque_cost_weight > 1e-9
+
+
+# ---------------------------------------------------------------------------- modes
+def _chain5(K, Kr, max_iterations, **kw):
+    return lambda: mz.chain5(K=K, Kr=Kr, max_iterations=max_iterations, max_iterations_after_collision_free=1000, **kw)
+
+
+def _terms_cum():
+    return mz.TERMS_ZOO["chain5"](K=12, Kr=5, use_cumulative_costs=True, max_iterations=4,
+                                  max_iterations_after_collision_free=1000)
+
+
+def _group_plain(K, Kr):
+    def make():
+        ps = gu.variants(mz.chain5, 4, K=K, Kr=Kr, max_iterations_after_collision_free=1000)
+        return [dataclasses.replace(p, params=dataclasses.replace(p.params, max_iterations=3 + (i % 2)))
+                for i, p in enumerate(ps)]
+    return make
+
+
+def _group_mixed():
+    """Four problems of one shape: terms on 0 and 3, cumulative costs on 1 and 2, max_iterations 4 .. 7."""
+    ps = gu.variants(mz.TERMS_ZOO["chain5"], 4, use_cumulative_costs=True, max_iterations_after_collision_free=1000)
+    out = []
+    for i, p in enumerate(ps):
+        prm = dataclasses.replace(p.params, max_iterations=4 + i, use_cumulative_costs=i in (1, 2),
+                                  torque_cost_weight=p.params.torque_cost_weight if i in (0, 3) else 0.0)
+        out.append(dataclasses.replace(p, params=prm, orientation_constraints=p.orientation_constraints if i in (0, 3) else []))
+    return out
+
+
+def _ranks():
+    return mz.chain5(K=128, Kr=0, max_iterations=3, max_iterations_after_collision_free=1000)
+
+
+# kind: "single" / "group" / "ranks"; make: the problem(s); env: set before creation; expect: pieces
+# the engine's own `stomp: model` line (STOMP_DEBUG_LEAN_PRINT) must hold; length: ops per script;
+# seeds: scripts per mode, the smallest count at which the census of tests/test_call_walks.py holds
+MODES = {
+    "reuse_fused": dict(kind="single", make=_chain5(12, 5, 4), env={"STOMP_DEBUG_NO_SPEC": "0", "STOMP_DEBUG_NO_PICK_FUSE": "0"},
+                        expect=["J 5 N 39 ", "pregen 1 fused_noise 1 brick 0", "launch of 13 rollouts: split,"]),
+    "reuse_no_spec": dict(kind="single", make=_chain5(12, 5, 5), env={"STOMP_DEBUG_NO_SPEC": "1", "STOMP_DEBUG_NO_PICK_FUSE": "0"},
+                          expect=["pregen 1 fused_noise 1", "launch of 13 rollouts: split,"]),
+    "reuse_no_pick_fuse": dict(kind="single", make=_chain5(12, 5, 3), env={"STOMP_DEBUG_NO_SPEC": "0", "STOMP_DEBUG_NO_PICK_FUSE": "1"},
+                               expect=["pregen 1 fused_noise 1", "launch of 13 rollouts: split,"]),
+    "pregen": dict(kind="single", make=_chain5(20, 0, 6), env={},
+                   expect=["pregen 1 fused_noise 1", "launch of 21 rollouts: "]),
+    "unfused": dict(kind="single", make=lambda: mz.chain17(K=12, Kr=5, max_iterations=4, max_iterations_after_collision_free=1000),
+                    env={}, expect=["J 17 N 39 ", "pregen 0 fused_noise 0"]),
+    "slot_loop": dict(kind="single", make=_chain5(260, 0, 3), env={}, threads=8, length=20, purity=False,
+                      expect=["lean 0 ", "launch of 261 rollouts: slot loop,"]),
+    "slot_loop_lean": dict(kind="single", make=_chain5(260, 0, 3), env={"STOMP_DEBUG_LEAN": "1"}, threads=8, length=20,
+                           purity=False, expect=["lean 1 ", "launch of 261 rollouts: lean slot loop,"]),
+    "phased": dict(kind="single", make=_chain5(12, 5, 5), env={"STOMP_DEBUG_SPLIT_MAX": "1"},
+                   expect=["launch of 13 rollouts: phased,"]),
+    "terms_cum": dict(kind="single", make=_terms_cum, env={}, threads=8, expect=["J 5 N 39 ", "launch of 13 rollouts: "]),
+    "device_brick": dict(kind="single", make=_chain5(12, 5, 4, shape=(66, 66, 66)), env={"STOMP_SDF_LAYOUT": "brick"},
+                         device_field=True, expect=["brick 1,"]),
+    "group_reuse": dict(kind="group", make=_group_plain(12, 5), env={}, expect=["group of 4 engines J 5 N 39 K 12 "]),
+    "group_pregen": dict(kind="group", make=_group_plain(20, 0), env={}, expect=["group of 4 engines J 5 N 39 K 20 "]),
+    "group_mixed": dict(kind="group", make=_group_mixed, env={}, threads=8, length=30,
+                        group=dict(state_terms=True, cumulative_costs=True, compact=False),
+                        expect=["group of 4 engines J 5 N 39 K 12 ", "engines with terms 2 of 4",
+                                "engines with cumulative costs 2 of 4"]),
+    "group_mixed_compact": dict(kind="group", make=_group_mixed, env={}, threads=8, length=30,
+                                group=dict(state_terms=True, cumulative_costs=True, compact=True),
+                                expect=["group of 4 engines J 5 N 39 K 12 ", "engines with terms 2 of 4",
+                                        "engines with cumulative costs 2 of 4"]),
+    "ranks_partials": dict(kind="ranks", make=_ranks, env={}, shard="partials", threads=8, length=20,
+                           expect=["launch of 65 rollouts: "]),
+    "ranks_gather": dict(kind="ranks", make=_ranks, env={}, shard="gather", threads=8, length=20,
+                         expect=["launch of 65 rollouts: "]),
+}
+DEFAULT_LENGTH = 40
+# scripts per mode: see tests/CALL_WALKS.md for how they were found (test_call_walks.py asserts that
+# the census holds at these counts and fails one seed earlier)
+SEEDS = {
+    "reuse_fused": 12, "reuse_no_spec": 14, "reuse_no_pick_fuse": 12, "pregen": 13, "unfused": 13, "slot_loop": 28,
+    "slot_loop_lean": 25, "phased": 18, "terms_cum": 15, "device_brick": 16, "group_reuse": 5, "group_pregen": 4,
+    "group_mixed": 18, "group_mixed_compact": 8, "ranks_partials": 4, "ranks_gather": 4,
+}
+
+
+def length_of(mode):
+    return MODES[mode].get("length", DEFAULT_LENGTH)
+
+
+# ---------------------------------------------------------------------------- single-engine bookkeeping
+FUSED = ("iterate", "run", "optimize")
+STEP = ("pi_get_rollouts", "pi_set_rollout_costs", "pi_improve_policy", "pi_add_extra_rollout", "pi_reset")
+NEUTRAL = ("observe", "execute", "set_timing", "refuse")     # ops that change no state the model has
+SINGLE_KINDS = FUSED + ("synchronize", "observe", "set_theta", "execute") + STEP + ("retarget", "set_timing", "refuse")
+REFUSALS = ("nan_goal", "extra_num0", "null_sigma")
+
+
+class Book:
+    """What the generator knows of one engine: the next iteration number, the step round's phase
+    (closed -> pi_get_rollouts -> got -> pi_set_rollout_costs -> costed -> pi_improve_policy -> closed),
+    whether a setRolloutCosts has been called since creation / retarget, whether a noiseless rollout
+    may be pending, and which fields both sides define (`valid`).
+
+    Orders excluded (tests/CALL_WALKS.md): between pi_get_rollouts and pi_improve_policy no fused
+    iteration, no second pi_get_rollouts and no pi_add_extra_rollout; pi_improve_policy only after a
+    pi_set_rollout_costs of the same round; pi_add_extra_rollout only after the first
+    pi_set_rollout_costs; refresh_field only with no noiseless rollout pending."""
+
+    def __init__(self, problem_info):
+        self.Kr, self.cum, self.device = problem_info["Kr"], problem_info["cum"], problem_info.get("device", False)
+        self.max_it = problem_info["max_it"]
+        self.kinds = SINGLE_KINDS + (("refresh_field",) if self.device else ())
+        self.reset()
+
+    def reset(self):
+        self.next_it, self.phase, self.costed_once, self.pending = 1, "closed", False, False
+        self.valid = set(ALWAYS)
+        self.extra_box = False
+
+    def allowed(self, kind):
+        closed = self.phase == "closed"
+        if kind in FUSED or kind == "pi_get_rollouts":
+            return closed
+        if kind == "pi_add_extra_rollout":
+            return closed and self.costed_once
+        if kind == "pi_set_rollout_costs":
+            return self.phase in ("got", "costed")
+        if kind == "pi_improve_policy":
+            return self.phase == "costed"
+        if kind == "refresh_field":
+            return self.device and not self.pending
+        return kind in self.kinds
+
+    def _iterated(self):
+        self.valid |= set(ROW_KEYS) | {"x_state"}
+        if self.Kr > 0:
+            self.valid |= set(X_KEYS)
+        else:   # the oracle's iteration writes the extra rollout's rows, the engine's only with reuse
+            self.valid -= set(gu.NO_REUSE_ORACLE_SKIPS)
+        if self.cum:
+            self.valid.add("cumulative")
+
+    def apply(self, op):
+        kind = op[0]
+        assert self.allowed(kind), (kind, self.phase)
+        if kind == "iterate":
+            assert op[1] >= 1
+            self.next_it, self.pending = op[1] + 1, False
+            self._iterated()
+        elif kind == "run":
+            assert op[1] >= 1 and 1 <= op[2] <= 4
+            self.next_it, self.pending = op[1] + op[2], True
+            self._iterated()
+        elif kind == "optimize":
+            self.next_it, self.pending = self.max_it + 1, False
+            self._iterated()
+        elif kind in ("synchronize", "set_theta"):
+            self.pending = False
+        elif kind == "observe":
+            assert op[1] and set(op[1]) <= self.valid, (op, sorted(self.valid))
+            if set(op[1]) & set(FLUSHING):
+                self.pending = False
+        elif kind == "pi_get_rollouts":
+            assert op[1] >= 1
+            self.next_it, self.pending, self.phase = op[1] + 1, False, "got"
+            self.valid -= {"state", "control", "prob", "cumulative"}
+            self.valid |= {"params", "noise"}
+        elif kind == "pi_set_rollout_costs":
+            assert op[1] in (1, 2)
+            self.phase, self.costed_once = "costed", True
+            self.valid |= {"state", "control"}
+        elif kind == "pi_improve_policy":
+            self.phase = "closed"
+            self.valid.add("prob")
+            if self.cum:
+                self.valid.add("cumulative")
+        elif kind == "pi_add_extra_rollout":
+            self.pending = False
+            self.valid |= set(X_KEYS)
+        elif kind == "retarget":
+            box = self.extra_box
+            self.reset()
+            self.extra_box = box
+        elif kind == "refresh_field":
+            assert op[1] != self.extra_box, "one more or one fewer box"
+            self.extra_box = op[1]
+        elif kind == "refuse":
+            assert op[1] in REFUSALS
+        else:
+            assert kind in ("execute", "set_timing", "pi_reset"), kind
+
+    def final_observe(self):
+        return ("observe", tuple(k for k in OBS_ORDER if k in self.valid))
+
+
+def _single_op(book, kind, rng):
+    if kind == "iterate":
+        r = rng.random()
+        nxt = book.next_it
+        it = nxt if r < 0.7 else (max(nxt - 1, 1) if r < 0.8 else (nxt + int(rng.integers(1, 3)) if r < 0.9 else max(nxt - 2, 1)))
+        return ("iterate", it)
+    if kind == "run":
+        first = book.next_it if rng.random() < 0.8 else max(book.next_it + int(rng.integers(-1, 2)), 1)
+        return ("run", first, int(rng.integers(1, 5)))
+    if kind == "observe":
+        valid = [k for k in OBS_ORDER if k in book.valid]
+        pick = [k for k in valid if rng.random() < 0.4] or [valid[int(rng.integers(len(valid)))]]
+        return ("observe", tuple(pick))
+    if kind == "set_theta":
+        return ("set_theta", int(rng.integers(1 << 20)))
+    if kind == "execute":
+        return ("execute", int(rng.integers(1 << 20)), int(rng.integers(1, 4)), int(rng.integers(0, 3)))
+    if kind == "pi_get_rollouts":
+        return ("pi_get_rollouts", book.next_it if rng.random() < 0.8 else max(book.next_it - 1, 1))
+    if kind == "pi_set_rollout_costs":
+        return ("pi_set_rollout_costs", int(rng.integers(1, 3)))
+    if kind == "pi_add_extra_rollout":
+        return ("pi_add_extra_rollout", None if rng.random() < 0.5 else int(rng.integers(1 << 20)))
+    if kind == "retarget":
+        return ("retarget", int(rng.integers(1, 50)), bool(rng.random() < 0.3))
+    if kind == "refresh_field":
+        return ("refresh_field", not book.extra_box)
+    if kind == "set_timing":
+        return ("set_timing", bool(rng.random() < 0.5))
+    if kind == "refuse":
+        return ("refuse", REFUSALS[int(rng.integers(len(REFUSALS)))])
+    return (kind,)
+
+
+# ---------------------------------------------------------------------------- group bookkeeping
+GROUP_KINDS = ("g_run", "g_run_refused", "g_synchronize", "g_optimize", "g_retarget", "observe", "m_set_theta",
+               "m_execute", "m_retarget", "m_iterate")
+
+
+class GroupBook:
+    """What the generator knows of a group of P engines: per member the fields stomp_group_run
+    compares before it accepts a run (a pending noiseless rollout's member, the iteration whose rows
+    were made ahead, and with reuse the two generateRollouts flags), the fields both sides define,
+    and the next iteration number.  The group is in lockstep when the members' tuples agree."""
+
+    def __init__(self, info):
+        self.P, self.Kr, self.cums, self.max_its = info["P"], info["Kr"], info["cums"], info["max_its"]
+        self.kinds = GROUP_KINDS
+        self.sig = [(-1, -1, False) for _ in range(self.P)]     # (pending member, pre_it, reused_next = extra_added)
+        self.valid = [set(ALWAYS) for _ in range(self.P)]
+        self.next_it = 1
+        self.lead = None      # (member, it): a member's own iterate the others have not followed yet
+        self.refused = False  # the refused group.run of this excursion was made
+
+    def lockstep(self):
+        return all(s == self.sig[0] for s in self.sig)
+
+    def _behind(self):
+        """members that have not made the leader's iterate yet"""
+        return [m for m in range(self.P) if self.sig[m] != self.sig[self.lead[0]]] if self.lead else []
+
+    def allowed(self, kind):
+        if kind == "g_run":
+            return self.lockstep()
+        if kind == "g_run_refused":
+            return self.lead is not None and not self.lockstep() and not self.refused
+        if kind == "g_optimize":
+            return self.lockstep()
+        if kind == "m_iterate":
+            # one member leaves lockstep; until the others have followed, only they may iterate
+            return self.lockstep() or (self.lead is not None and bool(self._behind()))
+        if kind == "m_retarget":
+            return self.lead is None      # (inside an excursion the followers are told by their tuples)
+        return kind in self.kinds
+
+    def _iterated(self, m):
+        self.valid[m] |= set(ROW_KEYS) | set(X_KEYS)
+        if self.cums[m]:
+            self.valid[m].add("cumulative")
+
+    def apply(self, op):
+        kind = op[0]
+        assert self.allowed(kind), (op, self.sig)
+        reuse = self.Kr > 0
+        if kind == "g_run":
+            first, count = op[1], op[2]
+            assert first >= 1 and 1 <= count <= 4
+            for m in range(self.P):
+                self.sig[m] = (first + count - 2, first + count, reuse)
+                self._iterated(m)
+            self.next_it, self.lead = first + count, None
+        elif kind == "g_run_refused":
+            self.refused = True
+        elif kind == "g_synchronize":
+            self.sig = [(-1,) + s[1:] for s in self.sig]
+        elif kind == "g_optimize":
+            for m in range(self.P):
+                self.sig[m] = (-1, -1, reuse)
+                self._iterated(m)
+            self.next_it, self.lead = max(self.max_its) + 1, None
+        elif kind == "g_retarget":
+            self.sig = [(-1, -1, False) for _ in range(self.P)]
+            self.valid = [set(ALWAYS) for _ in range(self.P)]
+            self.next_it, self.lead = 1, None
+        elif kind == "observe":
+            members = range(self.P) if op[1] < 0 else [op[1]]
+            for m in members:
+                assert op[2] and set(op[2]) <= self.valid[m], (op, sorted(self.valid[m]))
+                if set(op[2]) & set(FLUSHING):
+                    self.sig[m] = (-1,) + self.sig[m][1:]
+        elif kind == "m_set_theta":
+            self.sig[op[1]] = (-1,) + self.sig[op[1]][1:]
+        elif kind == "m_retarget":
+            self.sig[op[1]] = (-1, -1, False)
+            self.valid[op[1]] = set(ALWAYS)
+        elif kind == "m_iterate":
+            m, it = op[1], op[2]
+            if self.lead is None or self.lockstep():
+                self.lead, self.refused = (m, it), False
+            else:
+                assert m in self._behind() and it == self.lead[1], (op, self.lead)
+            self.sig[m] = (-1, it + 1, reuse)
+            self._iterated(m)
+            if self.lockstep():
+                self.next_it, self.lead = it + 1, None
+        else:
+            assert kind == "m_execute", kind
+        if self.lead is not None and self.lockstep():
+            self.lead = None
+
+    def final_ops(self):
+        ops = [("g_synchronize",)]
+        for m in range(self.P):
+            ops.append(("observe", m, tuple(k for k in OBS_ORDER if k in self.valid[m])))
+        return ops
+
+
+def _group_op(book, kind, rng):
+    P = book.P
+    m = int(rng.integers(P))
+    if kind in ("g_run", "g_run_refused"):
+        first = book.next_it if rng.random() < 0.8 else max(book.next_it + int(rng.integers(-1, 2)), 1)
+        return (kind, first, int(rng.integers(1, 5)))
+    if kind == "g_retarget":
+        return ("g_retarget", int(rng.integers(1, 50)), bool(rng.random() < 0.3))
+    if kind == "observe":
+        who = -1 if rng.random() < 0.3 else m
+        common = set.intersection(*book.valid) if who < 0 else book.valid[who]
+        valid = [k for k in OBS_ORDER if k in common]
+        pick = [k for k in valid if rng.random() < 0.4] or [valid[int(rng.integers(len(valid)))]]
+        return ("observe", who, tuple(pick))
+    if kind == "m_set_theta":
+        return ("m_set_theta", m, int(rng.integers(1 << 20)))
+    if kind == "m_execute":
+        return ("m_execute", m, int(rng.integers(1 << 20)), int(rng.integers(1, 4)), int(rng.integers(0, 3)))
+    if kind == "m_retarget":
+        return ("m_retarget", m, int(rng.integers(1, 50)), bool(rng.random() < 0.3))
+    if kind == "m_iterate":
+        if book.lead is not None and not book.lockstep():
+            behind = book._behind()
+            return ("m_iterate", behind[int(rng.integers(len(behind)))], book.lead[1])
+        return ("m_iterate", m, book.next_it)
+    return (kind,)
+
+
+# ---------------------------------------------------------------------------- rank bookkeeping
+RANK_KINDS = ("iterate", "run", "synchronize", "observe", "set_theta", "execute", "optimize", "refuse")
+RANK_REFUSALS = ("pi_get_rollouts", "pi_set_rollout_costs", "pi_improve_policy", "pi_add_extra_rollout", "pi_reset",
+                 "retarget")
+
+
+class RankBook(Book):
+    """Two ranks of one problem: the calls ranks accept; the step API and retarget only refused."""
+
+    def __init__(self, info):
+        super().__init__(info)
+        self.kinds = RANK_KINDS
+
+    def allowed(self, kind):
+        return kind in self.kinds
+
+    def apply(self, op):
+        if op[0] == "refuse":
+            assert op[1] in RANK_REFUSALS
+        else:
+            super().apply(op)
+
+
+def _rank_op(book, kind, rng):
+    if kind == "refuse":
+        return ("refuse", RANK_REFUSALS[int(rng.integers(len(RANK_REFUSALS)))])
+    return _single_op(book, kind, rng)
+
+
+# ---------------------------------------------------------------------------- generation
+_INFO = {}
+
+
+def mode_info(mode):
+    """What the bookkeeping needs of a mode's problems (built once: generation reads them only)."""
+    if mode not in _INFO:
+        spec = MODES[mode]
+        made = spec["make"]()
+        if spec["kind"] == "group":
+            _INFO[mode] = dict(P=len(made), Kr=made[0].params.num_reused_rollouts,
+                               cums=[bool(p.params.use_cumulative_costs) for p in made],
+                               max_its=[p.params.max_iterations for p in made])
+        else:
+            _INFO[mode] = dict(Kr=made.params.num_reused_rollouts, cum=bool(made.params.use_cumulative_costs),
+                               max_it=made.params.max_iterations, device=spec.get("device_field", False))
+    return _INFO[mode]
+
+
+def new_book(mode):
+    kind = MODES[mode]["kind"]
+    return {"single": Book, "group": GroupBook, "ranks": RankBook}[kind](mode_info(mode))
+
+
+def kinds_of(mode):
+    return new_book(mode).kinds
+
+
+def _walk(mode, rng, length, seen):
+    book = new_book(mode)
+    make_op = {"single": _single_op, "group": _group_op, "ranks": _rank_op}[MODES[mode]["kind"]]
+    script, prev = [], None
+    for _ in range(length):
+        kinds = [k for k in book.kinds if book.allowed(k)]
+        ops, w = [], []
+        for k in kinds:
+            # a candidate op of every kind the bookkeeping allows; its weight: 1, a hundred more for
+            # a pair of kinds no script of this mode has shown yet, and five more for every such
+            # pair that could follow it
+            op = make_op(book, k, rng)
+            after = copy.deepcopy(book)
+            after.apply(op)
+            ahead = sum(1 for k2 in after.kinds if after.allowed(k2) and (k, k2) not in seen)
+            ops.append(op)
+            w.append(1.0 + (100.0 if prev is not None and (prev, k) not in seen else 0.0) + 5.0 * ahead)
+        w = np.array(w)
+        op = ops[int(rng.choice(len(ops), p=w / w.sum()))]
+        book.apply(op)
+        if prev is not None:
+            seen.add((prev, op[0]))
+        script.append(op)
+        prev = op[0]
+    return script
+
+
+_SCRIPTS = {}
+
+
+def make_script(mode, seed, length=None):
+    """The script of (mode, seed): the walks of the seeds 0 .. seed in turn, each steered away from
+    the pairs of op kinds the ones before it showed (kept per process; the result depends on the
+    arguments alone)."""
+    length = length_of(mode) if length is None else length
+    ident = sorted(MODES).index(mode)
+    made, seen = _SCRIPTS.setdefault((mode, length), ([], set()))
+    while len(made) <= seed:
+        made.append(_walk(mode, np.random.default_rng([ident, len(made), length]), length, seen))
+    return list(made[seed])
+
+
+def final_ops(mode, script):
+    """The full observe of everything both sides define after the script (groups and ranks: after a
+    synchronize)."""
+    book = new_book(mode)
+    for op in script:
+        book.apply(op)
+    if MODES[mode]["kind"] == "group":
+        return book.final_ops()
+    if MODES[mode]["kind"] == "ranks":
+        return [("synchronize",), book.final_observe()]
+    return [book.final_observe()]
+
+
+# Ordered pairs of kinds that no valid script holds, with the rule that excludes them.  The census
+# asserts that exactly these are missing.
+def impossible_pairs(mode):
+    kind = MODES[mode]["kind"]
+    out = {}
+    if kind == "single":
+        kinds = kinds_of(mode)
+        opens = ("pi_get_rollouts", "pi_set_rollout_costs")     # leave a step round open
+        closes = FUSED + ("pi_improve_policy", "pi_add_extra_rollout", "retarget")   # leave it closed
+        for a in opens:
+            for b in FUSED + ("pi_get_rollouts", "pi_add_extra_rollout"):
+                out[(a, b)] = "between pi_get_rollouts and pi_improve_policy the oracle's rows hold no control costs yet"
+        out[("pi_get_rollouts", "pi_improve_policy")] = "pi_improve_policy needs the round's pi_set_rollout_costs"
+        for a in closes:
+            out[(a, "pi_set_rollout_costs")] = "pi_set_rollout_costs needs a pi_get_rollouts since the last fused iteration"
+            out[(a, "pi_improve_policy")] = "pi_improve_policy needs the round's pi_set_rollout_costs"
+        out[("retarget", "pi_add_extra_rollout")] = "a fresh PolicyImprovement has no control cost weight yet"
+        if "refresh_field" in kinds:
+            out[("run", "refresh_field")] = "the pending noiseless rollout would read the new field"
+    elif kind == "group":
+        for b in ("g_run", "g_optimize"):
+            out[("g_run_refused", b)] = "the group is out of lockstep until every member has followed the leader"
+        for a in ("g_run", "g_optimize", "g_retarget"):
+            out[(a, "g_run_refused")] = "a refused run needs a member ahead of the others"
+        out[("g_run_refused", "g_run_refused")] = "one refused run per excursion"
+        for pair in (("g_run_refused", "m_retarget"), ("m_retarget", "g_run_refused")):
+            out[pair] = "no member retargets while the others still follow a member's own iterate"
+    return out
+
+
+# ---------------------------------------------------------------------------- pairs
+def _expect_refusal(fn, code, word):
+    try:
+        fn()
+    except RuntimeError as ex:
+        assert f"error {code}" in str(ex) and word in str(ex), str(ex)
+        return
+    raise AssertionError(f"the call was accepted; expected error {code} ({word})")
+
+
+def _assert_stats(a, b, tag):
+    """(stomp_stats, costs) of an optimize against another's: integer statistics, best_cost, history."""
+    for k in gu.INT_STATS:
+        assert int(getattr(a[0], k)) == int(getattr(b[0], k)), (tag, k, getattr(a[0], k), getattr(b[0], k))
+    assert a[0].best_cost == b[0].best_cost, (tag, a[0].best_cost, b[0].best_cost)
+    np.testing.assert_array_equal(a[1], b[1], err_msg=f"{tag} cost history")
+
+
+def _execute_rows(p, theta, op_seed, nrows):
+    return mz.execute_rows(p, theta, rows=nrows, seed=op_seed)
+
+
+def _oracle_execute(o, rows, member):
+    out = [o.execute(r, member) + (o.last_constraints_satisfied,) for r in rows]
+    return (np.stack([r[0] for r in out]), np.array([r[1] for r in out]), np.stack([r[2] for r in out]),
+            np.array([r[3] for r in out]))
+
+
+def _assert_execute(e, want, rows, member, terms, tag):
+    c, cf, tr = e.execute(rows, member)
+    np.testing.assert_array_equal(c, want[0], err_msg=f"{tag} costs")
+    np.testing.assert_array_equal(cf, want[1], err_msg=f"{tag} collision flags")
+    np.testing.assert_array_equal(tr, want[2], err_msg=f"{tag} trajectories")
+    if terms:
+        np.testing.assert_array_equal(e.last_constraints_satisfied, want[3], err_msg=f"{tag} constraints flags")
+
+
+class Pair:
+    """One engine (None: the oracle alone, for the CPU tests) and its oracle."""
+
+    def __init__(self, problem, engine=None, threads=1, field=None):
+        self.p0 = self.p = problem
+        self.e, self.threads, self.field = engine, threads, field
+        self.cur_sdf = np.array(problem.sdf, np.uint16)
+        self.o = self._oracle(problem)
+        self.it, self.K_gen = 1, problem.params.num_rollouts
+
+    def _oracle(self, p):
+        # a field of its own: Oracle.refresh_field writes the array it was created on
+        return po.Oracle(dataclasses.replace(p, sdf=self.cur_sdf.copy()), threads=self.threads)
+
+    def close(self):
+        if self.e is not None:
+            self.e.close()
+        if self.field is not None:
+            self.field.free()
+
+    # -------------------------------------------------------------- ops
+    def op_iterate(self, it):
+        self.it = it
+        ro = self.o.iterate(it)
+        if self.e is not None:
+            re_ = self.e.iterate(it)
+            assert re_ == ro, (re_, ro)
+            if has_terms(self.p):
+                assert self.e.last_constraints_satisfied == bool(self.o.last_constraints_satisfied)
+
+    def op_run(self, first, count):
+        for it in range(first, first + count):
+            self.o.iterate(it)
+        self.it = first + count - 1
+        if self.e is not None:
+            self.e.run(first, count)
+
+    def op_synchronize(self):
+        if self.e is not None:
+            self.e.synchronize()
+
+    def op_observe(self, keys):
+        for k in keys:
+            if k == "cumulative":
+                if self.e is not None:
+                    cum = self.e.rollouts("cumulative_costs")
+                    np.testing.assert_array_equal(cum, numpy_cumulative(self.e), err_msg="cumulative_costs against numpy")
+                continue
+            want = _get(self.o, k)
+            if self.e is not None:
+                np.testing.assert_array_equal(_get(self.e, k), want, err_msg=k)
+
+    def op_set_theta(self, seed):
+        th = su.walk(np.random.default_rng(seed), self.o.theta(), 0.01)
+        self.o.set_theta(th)
+        if self.e is not None:
+            self.e.set_theta(th)
+
+    def op_execute(self, seed, nrows, member):
+        rows = _execute_rows(self.p, self.o.theta(), seed, nrows)
+        want = _oracle_execute(self.o, rows, member)
+        if self.e is not None:
+            _assert_execute(self.e, want, rows, member, has_terms(self.p), "execute")
+
+    def op_pi_get_rollouts(self, it):
+        self.it = it
+        sig = su.sigma(self.p, it)
+        ro = self.o.pi_get_rollouts(it, sig)
+        self.K_gen = len(ro)
+        if self.e is not None:
+            re_ = self.e.pi_get_rollouts(it, sig)
+            assert len(re_) == len(ro), (len(re_), len(ro))
+            np.testing.assert_array_equal(re_, ro, err_msg="rollouts")
+
+    def op_pi_set_rollout_costs(self, mult):
+        rows = self.o.rollouts("params")[: self.K_gen]
+        costs = np.stack([self.o.execute(r, self.it - 1)[0] for r in rows])
+        w = mult * self.p.params.smoothness_cost_weight
+        to = self.o.pi_set_rollout_costs(costs, w)
+        if self.e is not None:
+            np.testing.assert_array_equal(self.e.pi_set_rollout_costs(costs, w), to, err_msg="totals")
+
+    def op_pi_improve_policy(self):
+        uo = self.o.pi_improve_policy()
+        if self.e is not None:
+            np.testing.assert_array_equal(self.e.pi_improve_policy(), uo, err_msg="update")
+
+    def op_pi_add_extra_rollout(self, seed):
+        th = self.o.theta()
+        xp = th if seed is None else su.walk(np.random.default_rng(seed), th)
+        xc = self.o.execute(xp, max(self.it - 1, 0))[0]
+        self.o.pi_add_extra_rollout(xp, xc)
+        if self.e is not None:
+            self.e.pi_add_extra_rollout(xp, xc)
+
+    def op_pi_reset(self):
+        self.o.pi_reset()
+        if self.e is not None:
+            self.e.pi_reset()
+
+    def op_optimize(self):
+        ro = self.o.optimize()
+        self.it = self.p.params.max_iterations
+        if self.e is not None:
+            _assert_stats(self.e.optimize(), ro, "optimize")
+
+    def op_retarget(self, k, keep_seed):
+        q = moved(self.p0, k)
+        if keep_seed:
+            q = dataclasses.replace(q, seed=self.p.seed)
+        if self.e is not None:
+            self.e.retarget(q.start, q.goal, None if keep_seed else q.seed)
+            assert self.e.problem.seed == q.seed
+        self.p = q
+        self.o = self._oracle(q)
+        self.it, self.K_gen = 1, q.params.num_rollouts
+
+    def op_refresh_field(self, extra):
+        objs = scene_objects(self.p0, extra)
+        grid = self.p0.grid
+        if self.e is not None:
+            eng.sdf_build_objects_device(grid, objs, self.field.ptr)
+            new = self.field.to_numpy(np.uint16, tuple(grid.dims))
+            self.e.refresh_field()
+        else:
+            new = po.sdf_build_objects(grid, objs)[0]
+        assert not np.array_equal(new, self.cur_sdf), "the scene must change"
+        self.cur_sdf = new.copy()
+        self.o.refresh_field(new)
+
+    def op_set_timing(self, on):
+        if self.e is not None:
+            self.e.set_timing(on)
+
+    def op_refuse(self, what):
+        e = self.e
+        if e is None:
+            return
+        l = eng.load_library()
+        if what == "nan_goal":
+            before = e.problem
+            goal = np.array(self.p.goal, np.float64)
+            goal[self.p.J // 2] = np.nan
+            _expect_refusal(lambda: e.retarget(self.p.start, goal), -1, "not finite")
+            assert e.problem is before
+        elif what == "extra_num0":
+            th = np.ascontiguousarray(self.o.theta())
+            assert l.stomp_pi_add_extra_rollouts(e.h, 0, eng._dp(th), eng._dp(np.zeros(self.p.N))) == -1
+            assert b"one extra rollout" in l.stomp_engine_last_error(e.h)
+        else:
+            n = C.c_int32(-7)
+            out = np.zeros((e.K, e.J, e.N))
+            assert l.stomp_pi_get_rollouts(e.h, self.it + 1, None, eng._dp(out), C.byref(n)) == -1
+            assert b"null noise_stddev" in l.stomp_engine_last_error(e.h) and n.value == -7 and not out.any()
+
+    def apply(self, op):
+        getattr(self, "op_" + op[0])(*op[1:])
+
+    def full_state(self):
+        """Everything the oracle holds (the CPU purity test compares two oracles on it)."""
+        st = {k: _get(self.o, k) for k in ALWAYS + ROW_KEYS + X_KEYS}
+        st["reuse_log"] = self.o.reuse_log()
+        return st
+
+
+class GroupPair:
+    """A group on one stream, twins that make the equivalent single-engine calls, and the oracles."""
+
+    def __init__(self, problems, threads=1, **group_kw):
+        self.ps0 = list(problems)
+        self.ps = list(problems)
+        self.threads = threads
+        self.g = gu.Group(self.ps, **group_kw)
+        self.twins = gu.twins_of(self.ps)
+        self.os = [po.Oracle(p, threads=threads) for p in self.ps]
+
+    def close(self):
+        gu.close_all(self.g, self.twins)
+
+    def _refused_run(self, first, count):
+        try:
+            self.g.group.run(first, count)
+        except RuntimeError as ex:
+            assert "error -1" in str(ex) and "same iteration state" in str(ex), str(ex)
+            return
+        raise AssertionError("group.run was accepted with one member ahead of the others")
+
+    def op_g_run(self, first, count):
+        self.g.group.run(first, count)
+        gu.advance(self.os, first, count)
+        for t in self.twins:
+            t.run(first, count)
+
+    def op_g_run_refused(self, first, count):
+        self._refused_run(first, count)
+
+    def op_g_synchronize(self):
+        self.g.group.synchronize()
+        for t in self.twins:
+            t.synchronize()
+
+    def op_g_optimize(self):
+        res = self.g.group.optimize()
+        for i, (r, t, o) in enumerate(zip(res, self.twins, self.os)):
+            _assert_stats(r, o.optimize(), f"engine {i} against its oracle,")
+            _assert_stats(r, t.optimize(), f"engine {i} against its twin,")
+
+    def _moved(self, m, k, keep_seed):
+        q = moved(self.ps0[m], k + 50 * m)
+        return dataclasses.replace(q, seed=self.ps[m].seed) if keep_seed else q
+
+    def op_g_retarget(self, k, keep_seed):
+        qs = [self._moved(m, k, keep_seed) for m in range(len(self.ps))]
+        self.g.group.retarget([q.start for q in qs], [q.goal for q in qs], None if keep_seed else [q.seed for q in qs])
+        for m, q in enumerate(qs):
+            assert self.g.engines[m].problem.seed == q.seed
+            self.twins[m].retarget(q.start, q.goal, q.seed)
+            self.os[m] = po.Oracle(q, threads=self.threads)
+        self.ps = qs
+
+    def op_observe(self, who, keys):
+        for m in (range(len(self.ps)) if who < 0 else [who]):
+            ge, te, o, p = self.g.engines[m], self.twins[m], self.os[m], self.ps[m]
+            for k in keys:
+                if k == "cumulative":
+                    cum = ge.rollouts("cumulative_costs")
+                    np.testing.assert_array_equal(cum, numpy_cumulative(ge), err_msg=f"engine {m} cumulative_costs, numpy")
+                    np.testing.assert_array_equal(cum, te.rollouts("cumulative_costs"), err_msg=f"engine {m} cumulative_costs, twin")
+                    continue
+                got = _get(ge, k)
+                np.testing.assert_array_equal(got, _get(te, k), err_msg=f"engine {m} {k} against its twin")
+                if k not in gu.oracle_skips(p):
+                    np.testing.assert_array_equal(got, _get(o, k), err_msg=f"engine {m} {k} against its oracle")
+
+    def op_m_set_theta(self, m, seed):
+        th = su.walk(np.random.default_rng(seed), self.os[m].theta(), 0.01)
+        for x in (self.os[m], self.g.engines[m], self.twins[m]):
+            x.set_theta(th)
+
+    def op_m_execute(self, m, seed, nrows, member):
+        p = self.ps[m]
+        rows = _execute_rows(p, self.os[m].theta(), seed, nrows)
+        want = _oracle_execute(self.os[m], rows, member)
+        _assert_execute(self.g.engines[m], want, rows, member, has_terms(p), f"engine {m} execute")
+        _assert_execute(self.twins[m], want, rows, member, has_terms(p), f"twin {m} execute")
+
+    def op_m_retarget(self, m, k, keep_seed):
+        q = self._moved(m, k, keep_seed)
+        for x in (self.g.engines[m], self.twins[m]):
+            x.retarget(q.start, q.goal, None if keep_seed else q.seed)
+            assert x.problem.seed == q.seed
+        self.os[m] = po.Oracle(q, threads=self.threads)
+        self.ps[m] = q
+
+    def op_m_iterate(self, m, it):
+        ro = self.os[m].iterate(it)
+        assert self.g.engines[m].iterate(it) == ro, f"engine {m}"
+        assert self.twins[m].iterate(it) == ro, f"twin {m}"
+
+    def apply(self, op):
+        getattr(self, "op_" + op[0])(*op[1:])
+
+
+class RankPair:
+    """Two in-process ranks of one problem (tests/rank_util.py) beside one oracle of the whole K.
+    Every rank makes every call on a thread of its own and asserts nothing there: what the calls
+    returned is compared after the threads joined."""
+
+    def __init__(self, problem, ranks, threads=8):
+        from tests import rank_util as ru
+        self.ru = ru
+        self.p, self.ranks = problem, ranks
+        self.o = po.Oracle(problem, threads=threads)
+        self.K_loc = problem.params.num_rollouts // len(ranks)
+        self.it = 1
+
+    def close(self):
+        self.ru.close_all(self.ranks)
+
+    def _all(self, fn):
+        return self.ru.on_threads(self.ranks, lambda r, e: fn(e))
+
+    def op_iterate(self, it):
+        self.it = it
+        ro = self.o.iterate(it)
+        for r, got in enumerate(self._all(lambda e: e.iterate(it))):
+            assert got == ro, (r, got, ro)
+
+    def op_run(self, first, count):
+        for it in range(first, first + count):
+            self.o.iterate(it)
+        self.it = first + count - 1
+        self._all(lambda e: e.run(first, count))
+
+    def op_synchronize(self):
+        self._all(lambda e: e.synchronize())
+
+    def op_observe(self, keys):
+        got = self._all(lambda e: {k: _get(e, k) for k in keys})
+        for k in keys:
+            want = _get(self.o, k)
+            for r, rec in enumerate(got):
+                w = want[r * self.K_loc:(r + 1) * self.K_loc] if k in ROW_KEYS else want
+                np.testing.assert_array_equal(rec[k], w, err_msg=f"rank {r} {k}")
+
+    def op_set_theta(self, seed):
+        th = su.walk(np.random.default_rng(seed), self.o.theta(), 0.01)
+        self.o.set_theta(th)
+        self._all(lambda e: e.set_theta(th))
+
+    def op_execute(self, seed, nrows, member):
+        rows = _execute_rows(self.p, self.o.theta(), seed, nrows)
+        want = _oracle_execute(self.o, rows, member)
+        for r, (c, cf, tr) in enumerate(self._all(lambda e: e.execute(rows, member))):
+            np.testing.assert_array_equal(c, want[0], err_msg=f"rank {r} execute costs")
+            np.testing.assert_array_equal(cf, want[1], err_msg=f"rank {r} execute collision flags")
+            np.testing.assert_array_equal(tr, want[2], err_msg=f"rank {r} execute trajectories")
+
+    def op_optimize(self):
+        ro = self.o.optimize()
+        self.it = self.p.params.max_iterations
+        for r, got in enumerate(self._all(lambda e: e.optimize())):
+            _assert_stats(got, ro, f"rank {r} optimize")
+
+    def op_refuse(self, what):
+        p, th, sig = self.p, self.o.theta(), su.sigma(self.p, 1)
+        calls = dict(pi_get_rollouts=lambda e: e.pi_get_rollouts(self.it + 1, sig),
+                     pi_set_rollout_costs=lambda e: e.pi_set_rollout_costs(np.zeros((e.K, e.N)), 1.0),
+                     pi_improve_policy=lambda e: e.pi_improve_policy(),
+                     pi_add_extra_rollout=lambda e: e.pi_add_extra_rollout(th, np.zeros(p.N)),
+                     pi_reset=lambda e: e.pi_reset(),
+                     retarget=lambda e: e.retarget(p.start, p.goal, p.seed + 1))
+        for e in self.ranks:   # refused on the host before anything is posted: no thread needed
+            _expect_refusal(lambda: calls[what](e), -3, "single-rank")
+            assert e.problem is p
+
+    def apply(self, op):
+        getattr(self, "op_" + op[0])(*op[1:])
+
+
+# ---------------------------------------------------------------------------- replay
+def replay(mode, script, pair, seed=None, start=0):
+    """Runs the literal script on the pair.  A failure names the mode, the seed, the op's index and
+    the script up to that op, ready to paste into a regression test."""
+    for i, op in enumerate(script):
+        try:
+            pair.apply(op)
+        except AssertionError as ex:
+            raise AssertionError(f"walk {mode} seed {seed}: op {start + i} {op!r} failed\nscript = {script[: i + 1]!r}\n{ex}") from None
+        except Exception as ex:
+            raise AssertionError(f"walk {mode} seed {seed}: op {start + i} {op!r} raised {type(ex).__name__}: {ex}\n"
+                                 f"script = {script[: i + 1]!r}") from ex

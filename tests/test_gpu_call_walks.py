@@ -1,0 +1,97 @@
+"""GPU: seeded walks over the public API (tests/call_walks.py) -- one script drives an engine, an
+engine group with its single-engine twins, or two in-process ranks, and the CPU oracle.  Only what a
+call returns is compared as the walk goes; state is read where the walk put an `observe`, not after
+every call, so a stale pregen iteration, a dropped pending rollout or an unswapped row set that a
+read would have repaired stays visible to the next call.  Every comparison is bitwise.  Each case
+ends with a full observe of everything both sides define (groups and ranks: after a synchronize).
+
+tests/CALL_WALKS.md holds the alphabet, the modes, the census and what the walks found; the scripts
+that showed a bug stand below the walks as named regression tests.
+"""
+import numpy as np
+import pytest
+
+from stomp_motion_planner_icra2011_amd import engine as eng
+from tests import call_walks as cw
+from tests import rank_util as ru
+
+pytestmark = pytest.mark.gpu
+
+CASES = [(mode, seed) for mode in cw.MODES for seed in range(cw.SEEDS[mode])]
+
+
+def lines(capfd, prefix):
+    err = capfd.readouterr().err
+    out = [l for l in err.splitlines() if l.startswith(prefix)]
+    assert out, err
+    return out
+
+
+def make_pair(mode, monkeypatch, capfd):
+    """The mode's pair, created under its environment; the path it names asserted from the
+    engine's own STOMP_DEBUG_LEAN_PRINT lines."""
+    spec = cw.MODES[mode]
+    monkeypatch.setenv("STOMP_DEBUG_LEAN_PRINT", "1")
+    for k, v in spec["env"].items():
+        monkeypatch.setenv(k, v)
+    threads = spec.get("threads", 1)
+    made = spec["make"]()
+    capfd.readouterr()
+    if spec["kind"] == "single":
+        buf = None
+        if spec.get("device_field"):
+            buf = eng.DeviceBuffer(2 * made.grid.cells)
+            eng.sdf_build_objects_device(made.grid, cw.scene_objects(made, False), buf.ptr)
+            made.sdf = buf.to_numpy(np.uint16, tuple(made.grid.dims))
+        e = eng.Engine(made, sdf_device_ptr=buf.ptr if buf else None)
+        got = lines(capfd, "stomp: model ")[-1:]
+        pair = cw.Pair(made, e, threads=threads, field=buf)
+    elif spec["kind"] == "group":
+        pair = cw.GroupPair(made, threads=threads, **spec.get("group", {}))
+        got = lines(capfd, "stomp: group ")
+    else:
+        ranks = ru.make_ranks(made, 2, spec["shard"], monkeypatch)
+        got = lines(capfd, "stomp: model ")
+        pair = cw.RankPair(made, ranks, threads=threads)
+        assert [e.shard_mode for e in ranks] == [spec["shard"]] * 2 and [e.K_loc for e in ranks] == [64, 64]
+    for piece in spec["expect"]:
+        assert any(piece in l for l in got), (piece, got)
+    return pair
+
+
+def walk(mode, script, monkeypatch, capfd, seed=None):
+    pair = make_pair(mode, monkeypatch, capfd)
+    try:
+        cw.replay(mode, script, pair, seed)
+        cw.replay(mode, cw.final_ops(mode, script), pair, seed, start=len(script))
+    finally:
+        pair.close()
+
+
+@pytest.mark.parametrize("mode,seed", CASES, ids=[f"{m}-{s}" for m, s in CASES])
+def test_walk(monkeypatch, capfd, mode, seed):
+    walk(mode, cw.make_script(mode, seed), monkeypatch, capfd, seed)
+
+
+# ---------------------------------------------------------------------------- what the walks found
+# The shortest scripts that show each bug (tests/CALL_WALKS.md, "What the walks found").
+
+@pytest.mark.parametrize("mode", ["reuse_fused", "reuse_no_pick_fuse"])
+def test_set_theta_before_a_reusing_iteration(monkeypatch, capfd, mode):
+    # the extra rollout keeps the parameters it was added with (policy_improvement.cpp:446-449): after
+    # set_theta they are not theta, and the reuse step must rank and re-base that row, not theta + 0.
+    # The rollout launch that prices the candidates ahead took theta for it.  The first ranking of this
+    # script keeps the extra rollout (the oracle's reuse_log: [7, 3, -1, 1, 6]).
+    script = [("iterate", 1), ("set_theta", 503634), ("iterate", 2), ("observe", ("theta", "params", "noise")),
+              ("run", 3, 2), ("set_theta", 96949), ("run", 5, 1)]
+    walk(mode, script, monkeypatch, capfd)
+
+
+@pytest.mark.parametrize("mode", ["pregen", "reuse_fused", "unfused"])
+@pytest.mark.parametrize("fused", [("iterate", 2), ("run", 2, 2), ("optimize",)], ids=lambda op: op[0])
+def test_extra_rollout_after_a_fused_iteration_is_priced_with_its_weight(monkeypatch, capfd, mode, fused):
+    # runSingleIteration calls setRolloutCosts with the loop's weight (policy_improvement_loop.cpp:173),
+    # so an addExtraRollouts after it prices with that weight, not with the 2 w of the step round before
+    script = [("pi_get_rollouts", 1), ("pi_set_rollout_costs", 2), ("pi_improve_policy",), fused,
+              ("pi_add_extra_rollout", None), ("observe", ("x_control",))]
+    walk(mode, script, monkeypatch, capfd)
