@@ -26,6 +26,10 @@
  *   stomp_sdf_build_objects  the same fill by the reference's own rules: posed boxes and
  *                            cylinders sampled on its lattice, robot bodies, collision-map
  *                            points (stomp_collision_space.cpp:199-297, 564-650)
+ *   stomp_scene_*            that field kept in two layers between requests: a static layer built
+ *                            once, the robot bodies and sensor points replaced per request over
+ *                            the window around their marks (the reference refills the whole
+ *                            field in every setStartState)
  *
  * Conventions: plain pointers and sizes only; host buffers are caller-owned and
  * read/written during the call; device buffers are engine-owned.  Trajectories
@@ -379,6 +383,61 @@ int stomp_sdf_build_objects(int32_t nx, int32_t ny, int32_t nz, const double* or
                             double max_expansion, const stomp_shape* shapes, int32_t n_shapes,
                             const double* points, int64_t n_points, uint16_t* out_device, int64_t* marked,
                             void* stream);
+
+/* Scene layers: the field of stomp_sdf_build_objects kept in two layers over the caller's device
+ * buffer field_device (nx*ny*nz uint16, stomp_grid's layout and representation), for a caller
+ * whose scene is mostly the same from request to request.  The field is a capped squared
+ * distance, so for two sets of marks min(d2(A u B), cap^2) = min(min(d2(A), cap^2),
+ * min(d2(B), cap^2)) holds exactly: the static layer (A) is built once and kept, and a request's
+ * dynamic set (B: the robot's own bodies at the start state, the collision-map points) costs a
+ * transform over the bounding window of its marks grown by cap cells and a min merge there.
+ *   stomp_scene_create       records the grid and the buffer; touches no device.  stream NULL: a
+ *                            stream the scene owns, made with the first stomp_scene_set_static.
+ *   stomp_scene_set_static   the static layer from its objects and points, by the rules of
+ *                            stomp_sdf_build_objects; written to field_device, any dynamic set
+ *                            dropped: the field is then stomp_sdf_build_objects of these inputs.
+ *   stomp_scene_set_dynamic  replaces the dynamic set (it does not add to it): the field is then bit
+ *                            for bit what stomp_sdf_build_objects writes for the static objects and
+ *                            points followed by these; cells of the previous dynamic window the new
+ *                            one does not cover are back at the static layer's value; an empty set
+ *                            gives the static field.  Before any set_static: STOMP_E_INVALID.  The
+ *                            marking, the three passes, the merge and the restore run over the
+ *                            window only (one window per call around all dynamic inputs: a dynamic
+ *                            set scattered over the grid degenerates to the whole grid).
+ * All work goes on the scene's stream, after everything enqueued there before.  With marked NULL a
+ * set_* call does not wait for the device: the host inputs are copied into pinned staging of the
+ * scene before it returns.  With marked non-NULL it waits and returns the points that landed
+ * inside the grid, counted as stomp_sdf_build_objects counts (the static and the dynamic count add
+ * up to the full build's).  A call allocates only when its window or its input lists are larger
+ * than every earlier one (geometric growth); set_static's window is the grid.
+ *   stomp_scene_window       host only, no device: the window set_dynamic would use, inclusive cell
+ *                            bounds; empty (lo[0] > hi[0]) when nothing can land in the grid.
+ *   stomp_scene_info         waits for the stream.  info[0..2], info[3..5]: the last call's window
+ *                            (lo, hi); [6] its cells; [7] cells restored from the static layer in
+ *                            the last call; [8] dynamic marks so far that landed inside the grid but
+ *                            outside the window (a check on the bound: always 0); [9] allocations
+ *                            made inside set_dynamic so far.
+ * Errors, all checked before any device is touched (a machine without a GPU can make these calls)
+ * and leaving the scene and the field untouched: NULL scene, field, origin or out, sizes <= 0, a
+ * resolution that is not positive, negative counts, a count without its array, an unknown shape
+ * type, a degenerate mesh, a lattice too large: STOMP_E_INVALID; ceil(max_expansion / resolution)
+ * > 255: STOMP_E_UNSUPPORTED.  stomp_last_error() has the message.  Calls on one scene are
+ * serialised by the caller.  Engines reading field_device in place: the ordering contract is
+ * stomp_engine_refresh_field's (simplest: the scene on the engines' stream); engines with a bricked
+ * copy call stomp_engine_refresh_field after a set_* call, as after any in-place rebuild. */
+typedef struct stomp_scene stomp_scene;
+int stomp_scene_create(int32_t device, int32_t nx, int32_t ny, int32_t nz, const double* origin,
+                       double resolution, double max_expansion, uint16_t* field_device, void* stream,
+                       stomp_scene** out);
+int stomp_scene_set_static(stomp_scene* s, const stomp_shape* shapes, int32_t n_shapes, const double* points,
+                           int64_t n_points, int64_t* marked);
+int stomp_scene_set_dynamic(stomp_scene* s, const stomp_shape* shapes, int32_t n_shapes, const double* points,
+                            int64_t n_points, int64_t* marked);
+int stomp_scene_window(int32_t nx, int32_t ny, int32_t nz, const double* origin, double resolution,
+                       double max_expansion, const stomp_shape* shapes, int32_t n_shapes, const double* points,
+                       int64_t n_points, int32_t lo[3], int32_t hi[3]);
+int stomp_scene_info(stomp_scene* s, int64_t info[10]);
+void stomp_scene_destroy(stomp_scene* s);
 
 /* The differentiation stencils the engine is built on (DIFF_RULES of stomp_utils.h:49-56:
  * velocity, acceleration, jerk; 3 x 7 doubles, row-major).  Host only, no device needed. */

@@ -9,6 +9,8 @@
 //                        staged arguments behind run, synchronize and optimize
 //   engine_retarget.cpp  stomp_engine_retarget and the part of it stomp_group_retarget shares
 //   sdf_build.cpp        the distance-field builders (does not include this header)
+//   scene.cpp            stomp_scene: the field kept in a static and a dynamic layer (uses fail and
+//                        DeviceGuard only)
 #pragma once
 
 #include "stomp_engine.h"

@@ -525,6 +525,9 @@ struct SdfMarkArgs {
     double inv_res;              // 1.0 / res (VoxelGrid oo_resolution)
     unsigned char* occ;          // nx*ny*nz marks
     unsigned long long* marked;  // points that landed inside the grid
+    // the windowed marking only (launch_mark_*_window): occ holds the window's cells alone
+    int wlo[3], wn[3];           // the window's first cell and its cells per axis
+    unsigned long long* stray;   // marks inside the grid but outside the window (never written)
 };
 struct SdfLatticeJob {
     int type;
@@ -543,6 +546,30 @@ void launch_mark_lattice(const SdfLatticeJob& j, const double* axes, const SdfMa
 void launch_mark_points(const double* pts, long long np, const SdfMarkArgs& g, hipStream_t s);
 void launch_edt(int nx, int ny, int nz, int cap, const unsigned char* occ, unsigned short* a, unsigned short* b,
                 unsigned short* field, hipStream_t s);
+// The scene layers (scene.cpp): the same marking into a window-local occupancy, and the capped EDT
+// over a box of the grid merged with a kept static layer.
+struct SdfBox {
+    int lo[3], n[3];             // cells [lo, lo + n) per axis; empty when an n is 0
+};
+struct SdfWindowArgs {
+    int gn[3];                   // the grid
+    SdfBox w;                    // the window, in grid cells (inside the grid)
+    SdfBox m;                    // the bound of the marks, in grid cells (inside the window)
+    int cap;
+    const unsigned char* occ;    // [w.n] marks, window-local
+    unsigned short *a, *b;       // [w.n] each: the z and y passes' results
+    unsigned short* stat;        // [gn] the static layer
+    unsigned short* field;       // [gn] the caller's field
+};
+void launch_mark_lattice_window(const SdfLatticeJob& j, const double* axes, const SdfMarkArgs& g, hipStream_t s);
+void launch_mark_points_window(const double* pts, long long np, const SdfMarkArgs& g, hipStream_t s);
+// the three passes over the window: the z pass over m's x / y extent, the y pass over m's x extent,
+// the x pass over the whole window; each reads along its axis inside m only (everything else is
+// beyond the cap).  merge: field = min(stat, d2) over the window; otherwise stat = field = d2.
+void launch_edt_box(const SdfWindowArgs& A, bool merge, hipStream_t s);
+// field = stat over the cells of `prev` outside `now`
+void launch_restore_box(const int* gn, const SdfBox& prev, const SdfBox& now, const unsigned short* stat,
+                        unsigned short* field, hipStream_t s);
 // the [nx][ny][nz] field re-laid as 4^3 bricks (DevModel::brick) into dst, ceil(n / 4)^3 bricks;
 // voxels of the padding bricks past the grid are 0 (never read: the lookup's range test)
 void launch_sdf_bricks(const unsigned short* src, unsigned short* dst, int nx, int ny, int nz, hipStream_t s);

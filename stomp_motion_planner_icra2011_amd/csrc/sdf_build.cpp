@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "sdf_lattice.h"
 
 namespace stomp {
 int fail(stomp_engine* e, int code, const char* fmt, ...);   // engine.cpp; here always without an engine
@@ -309,106 +310,16 @@ static void mesh_box_sphere(const double* V, int nv, double* centre, double* rad
     *radius = std::sqrt(r2);
 }
 
-extern "C" {
+namespace stomp {
 
-int stomp_sdf_build(int32_t nx, int32_t ny, int32_t nz, const double* origin, double res, double max_expansion,
-                    const double* boxes, int32_t n_boxes, const double* cyl, int32_t n_cyl, uint16_t* out, void* stream)
+// StompCollisionSpace::setStartState's per-object lattices (stomp_collision_space.cpp:199-297,
+// 564-650): the environment objects' coordinate lists by the reference's own running-sum loops,
+// the robot bodies' and meshes' bounding-sphere lattices, the meshes' hull planes
+int lattice_setup(const stomp_shape* shapes, int n_shapes, double res, LatticeSetup& out)
 {
-    if (nx <= 0 || ny <= 0 || nz <= 0 || !(res > 0) || !out) return fail(nullptr, STOMP_E_INVALID, "invalid grid");
-    const int n[3] = {nx, ny, nz};
-    const double capd = std::ceil(max_expansion / res);
-    if (!(capd >= 0) || capd > 255) return fail(nullptr, STOMP_E_UNSUPPORTED, "max_expansion / resolution above 255 cells");
-    const int cap = (int)capd;
-    const int cap2 = cap * cap;
-    auto range = [&](double lo, double hi, int a, int& i0, int& i1) {
-        i0 = std::max((int)std::ceil((lo - origin[a]) / res), 0);
-        i1 = std::min((int)std::floor((hi - origin[a]) / res), n[a] - 1);
-    };
-    std::vector<int> br;
-    for (int b = 0; b < n_boxes; ++b) {
-        const double* q = boxes + 6 * b;
-        int r[6];
-        bool empty = false;
-        for (int a = 0; a < 3; ++a) {
-            range(q[a] - q[3 + a] / 2.0, q[a] + q[3 + a] / 2.0, a, r[2 * a], r[2 * a + 1]);
-            if (r[2 * a] > r[2 * a + 1]) empty = true;
-        }
-        if (!empty) br.insert(br.end(), r, r + 6);
-    }
-    const long long big = 1LL << 40;
-    std::vector<long long> cd2;
-    std::vector<int> cz;
-    for (int c = 0; c < n_cyl; ++c) {
-        const double* q = cyl + 5 * c;
-        int z0, z1;
-        range(q[2] - q[4] / 2.0, q[2] + q[4] / 2.0, 2, z0, z1);
-        if (z0 > z1) continue;
-        std::vector<std::pair<int, int>> disc;
-        for (int i = 0; i < nx; ++i) {
-            const double xs = origin[0] + i * res - q[0];
-            for (int j = 0; j < ny; ++j) {
-                const double ys = origin[1] + j * res - q[1];
-                if (xs * xs + ys * ys <= q[3] * q[3]) disc.push_back({i, j});
-            }
-        }
-        if (disc.empty()) continue;
-        std::vector<long long> t((size_t)nx * ny, big);
-        for (int i = 0; i < nx; ++i)
-            for (int j = 0; j < ny; ++j) {
-                long long best = big;
-                for (auto& pq : disc) {
-                    long long dx = i - pq.first, dy = j - pq.second;
-                    long long v = dx * dx + dy * dy;
-                    if (v < best) best = v;
-                }
-                t[(size_t)i * ny + j] = std::min(best, (long long)cap2);
-            }
-        cd2.insert(cd2.end(), t.begin(), t.end());
-        cz.push_back(z0);
-        cz.push_back(z1);
-    }
-    hipStream_t s = (hipStream_t)stream;
-    int* d_b = nullptr;
-    long long* d_c = nullptr;
-    int* d_z = nullptr;
-    if (!br.empty() && hipMalloc(&d_b, br.size() * sizeof(int)) != hipSuccess) return fail(nullptr, STOMP_E_DEVICE, "hipMalloc");
-    if (!cd2.empty() && hipMalloc(&d_c, cd2.size() * sizeof(long long)) != hipSuccess) return fail(nullptr, STOMP_E_DEVICE, "hipMalloc");
-    if (!cz.empty() && hipMalloc(&d_z, cz.size() * sizeof(int)) != hipSuccess) return fail(nullptr, STOMP_E_DEVICE, "hipMalloc");
-    hipError_t cp = hipSuccess;
-    if (d_b) cp = hipMemcpyAsync(d_b, br.data(), br.size() * sizeof(int), hipMemcpyHostToDevice, s);
-    if (d_c && cp == hipSuccess) cp = hipMemcpyAsync(d_c, cd2.data(), cd2.size() * sizeof(long long), hipMemcpyHostToDevice, s);
-    if (d_z && cp == hipSuccess) cp = hipMemcpyAsync(d_z, cz.data(), cz.size() * sizeof(int), hipMemcpyHostToDevice, s);
-    if (cp != hipSuccess) {
-        if (d_b) hipFree(d_b);
-        if (d_c) hipFree(d_c);
-        if (d_z) hipFree(d_z);
-        return fail(nullptr, STOMP_E_DEVICE, "sdf build: %s", hipGetErrorString(cp));
-    }
-    launch_sdf_build(nx, ny, nz, cap2, d_b, (int)br.size() / 6, d_c, d_z, (int)cz.size() / 2, out, s);
-    hipError_t st = hipStreamSynchronize(s);
-    if (d_b) hipFree(d_b);
-    if (d_c) hipFree(d_c);
-    if (d_z) hipFree(d_z);
-    if (st != hipSuccess) return fail(nullptr, STOMP_E_DEVICE, "sdf build: %s", hipGetErrorString(st));
-    return 0;
-}
-
-// StompCollisionSpace::setStartState's fill (stomp_collision_space.cpp:154-297, 564-650): the
-// per-object lattice is set up here (the environment objects' coordinate lists by the reference's
-// own running-sum loops), the marking and the EDT run on the device (k_sdf.hip)
-int stomp_sdf_build_objects(int32_t nx, int32_t ny, int32_t nz, const double* origin, double res,
-                            double max_expansion, const stomp_shape* shapes, int32_t n_shapes, const double* points,
-                            int64_t n_points, uint16_t* out, int64_t* marked, void* stream)
-{
-    if (nx <= 0 || ny <= 0 || nz <= 0 || !(res > 0) || !out || !origin || n_shapes < 0 || n_points < 0 ||
-        (n_shapes > 0 && !shapes) || (n_points > 0 && !points))
-        return fail(nullptr, STOMP_E_INVALID, "invalid grid or object list");
-    const double capd = std::ceil(max_expansion / res);
-    if (!(capd >= 0) || capd > 255) return fail(nullptr, STOMP_E_UNSUPPORTED, "max_expansion / resolution above 255 cells");
-    const int cap = (int)capd;
-    std::vector<double> axes;
-    std::vector<double> mesh_planes;   // every mesh's hull planes, 4 doubles each
-    std::vector<SdfLatticeJob> jobs;
+    std::vector<double>& axes = out.axes;
+    std::vector<double>& mesh_planes = out.mesh_planes;   // every mesh's hull planes, 4 doubles each
+    std::vector<SdfLatticeJob>& jobs = out.jobs;
     const long long kMaxLattice = 1LL << 31;
     for (int s = 0; s < n_shapes; ++s) {
         const stomp_shape& sh = shapes[s];
@@ -504,6 +415,122 @@ int stomp_sdf_build_objects(int32_t nx, int32_t ny, int32_t nz, const double* or
         }
         jobs.push_back(j);
     }
+    return 0;
+}
+
+void resolve_mesh_planes(std::vector<SdfLatticeJob>& jobs, const double* d_planes)
+{
+    for (SdfLatticeJob& j : jobs)
+        if (j.type == kBodyMesh) {
+            j.planes = d_planes + 4 * (size_t)j.off[0];
+            j.off[0] = 0;
+        }
+}
+
+}  // namespace stomp
+
+extern "C" {
+
+int stomp_sdf_build(int32_t nx, int32_t ny, int32_t nz, const double* origin, double res, double max_expansion,
+                    const double* boxes, int32_t n_boxes, const double* cyl, int32_t n_cyl, uint16_t* out, void* stream)
+{
+    if (nx <= 0 || ny <= 0 || nz <= 0 || !(res > 0) || !out) return fail(nullptr, STOMP_E_INVALID, "invalid grid");
+    const int n[3] = {nx, ny, nz};
+    const double capd = std::ceil(max_expansion / res);
+    if (!(capd >= 0) || capd > 255) return fail(nullptr, STOMP_E_UNSUPPORTED, "max_expansion / resolution above 255 cells");
+    const int cap = (int)capd;
+    const int cap2 = cap * cap;
+    auto range = [&](double lo, double hi, int a, int& i0, int& i1) {
+        i0 = std::max((int)std::ceil((lo - origin[a]) / res), 0);
+        i1 = std::min((int)std::floor((hi - origin[a]) / res), n[a] - 1);
+    };
+    std::vector<int> br;
+    for (int b = 0; b < n_boxes; ++b) {
+        const double* q = boxes + 6 * b;
+        int r[6];
+        bool empty = false;
+        for (int a = 0; a < 3; ++a) {
+            range(q[a] - q[3 + a] / 2.0, q[a] + q[3 + a] / 2.0, a, r[2 * a], r[2 * a + 1]);
+            if (r[2 * a] > r[2 * a + 1]) empty = true;
+        }
+        if (!empty) br.insert(br.end(), r, r + 6);
+    }
+    const long long big = 1LL << 40;
+    std::vector<long long> cd2;
+    std::vector<int> cz;
+    for (int c = 0; c < n_cyl; ++c) {
+        const double* q = cyl + 5 * c;
+        int z0, z1;
+        range(q[2] - q[4] / 2.0, q[2] + q[4] / 2.0, 2, z0, z1);
+        if (z0 > z1) continue;
+        std::vector<std::pair<int, int>> disc;
+        for (int i = 0; i < nx; ++i) {
+            const double xs = origin[0] + i * res - q[0];
+            for (int j = 0; j < ny; ++j) {
+                const double ys = origin[1] + j * res - q[1];
+                if (xs * xs + ys * ys <= q[3] * q[3]) disc.push_back({i, j});
+            }
+        }
+        if (disc.empty()) continue;
+        std::vector<long long> t((size_t)nx * ny, big);
+        for (int i = 0; i < nx; ++i)
+            for (int j = 0; j < ny; ++j) {
+                long long best = big;
+                for (auto& pq : disc) {
+                    long long dx = i - pq.first, dy = j - pq.second;
+                    long long v = dx * dx + dy * dy;
+                    if (v < best) best = v;
+                }
+                t[(size_t)i * ny + j] = std::min(best, (long long)cap2);
+            }
+        cd2.insert(cd2.end(), t.begin(), t.end());
+        cz.push_back(z0);
+        cz.push_back(z1);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    int* d_b = nullptr;
+    long long* d_c = nullptr;
+    int* d_z = nullptr;
+    if (!br.empty() && hipMalloc(&d_b, br.size() * sizeof(int)) != hipSuccess) return fail(nullptr, STOMP_E_DEVICE, "hipMalloc");
+    if (!cd2.empty() && hipMalloc(&d_c, cd2.size() * sizeof(long long)) != hipSuccess) return fail(nullptr, STOMP_E_DEVICE, "hipMalloc");
+    if (!cz.empty() && hipMalloc(&d_z, cz.size() * sizeof(int)) != hipSuccess) return fail(nullptr, STOMP_E_DEVICE, "hipMalloc");
+    hipError_t cp = hipSuccess;
+    if (d_b) cp = hipMemcpyAsync(d_b, br.data(), br.size() * sizeof(int), hipMemcpyHostToDevice, s);
+    if (d_c && cp == hipSuccess) cp = hipMemcpyAsync(d_c, cd2.data(), cd2.size() * sizeof(long long), hipMemcpyHostToDevice, s);
+    if (d_z && cp == hipSuccess) cp = hipMemcpyAsync(d_z, cz.data(), cz.size() * sizeof(int), hipMemcpyHostToDevice, s);
+    if (cp != hipSuccess) {
+        if (d_b) hipFree(d_b);
+        if (d_c) hipFree(d_c);
+        if (d_z) hipFree(d_z);
+        return fail(nullptr, STOMP_E_DEVICE, "sdf build: %s", hipGetErrorString(cp));
+    }
+    launch_sdf_build(nx, ny, nz, cap2, d_b, (int)br.size() / 6, d_c, d_z, (int)cz.size() / 2, out, s);
+    hipError_t st = hipStreamSynchronize(s);
+    if (d_b) hipFree(d_b);
+    if (d_c) hipFree(d_c);
+    if (d_z) hipFree(d_z);
+    if (st != hipSuccess) return fail(nullptr, STOMP_E_DEVICE, "sdf build: %s", hipGetErrorString(st));
+    return 0;
+}
+
+// StompCollisionSpace::setStartState's fill (stomp_collision_space.cpp:154-297, 564-650): the
+// per-object lattice is set up on the host (lattice_setup), the marking and the EDT run on the
+// device (k_sdf.hip)
+int stomp_sdf_build_objects(int32_t nx, int32_t ny, int32_t nz, const double* origin, double res,
+                            double max_expansion, const stomp_shape* shapes, int32_t n_shapes, const double* points,
+                            int64_t n_points, uint16_t* out, int64_t* marked, void* stream)
+{
+    if (nx <= 0 || ny <= 0 || nz <= 0 || !(res > 0) || !out || !origin || n_shapes < 0 || n_points < 0 ||
+        (n_shapes > 0 && !shapes) || (n_points > 0 && !points))
+        return fail(nullptr, STOMP_E_INVALID, "invalid grid or object list");
+    const double capd = std::ceil(max_expansion / res);
+    if (!(capd >= 0) || capd > 255) return fail(nullptr, STOMP_E_UNSUPPORTED, "max_expansion / resolution above 255 cells");
+    const int cap = (int)capd;
+    LatticeSetup L;
+    if (int rc = lattice_setup(shapes, n_shapes, res, L)) return rc;
+    std::vector<double>& axes = L.axes;
+    std::vector<double>& mesh_planes = L.mesh_planes;
+    std::vector<SdfLatticeJob>& jobs = L.jobs;
     hipStream_t st = (hipStream_t)stream;
     const size_t cells = (size_t)nx * ny * nz;
     unsigned char* occ = nullptr;
@@ -527,11 +554,7 @@ int stomp_sdf_build_objects(int32_t nx, int32_t ny, int32_t nz, const double* or
         cleanup();
         return fail(nullptr, STOMP_E_DEVICE, "sdf build: hipMalloc");
     }
-    for (SdfLatticeJob& j : jobs)
-        if (j.type == kBodyMesh) {
-            j.planes = d_planes + 4 * (size_t)j.off[0];
-            j.off[0] = 0;
-        }
+    resolve_mesh_planes(jobs, d_planes);
     hipError_t err = hipMemsetAsync(occ, 0, cells, st);
     if (err == hipSuccess) err = hipMemsetAsync(d_marked, 0, sizeof(unsigned long long), st);
     if (err == hipSuccess && d_axes)

@@ -106,7 +106,8 @@ EXPORTED = ["stomp_engine_create", "stomp_engine_destroy", "stomp_engine_last_er
             "stomp_group_create_flags",
             "stomp_engine_shard_info", "stomp_shard_decide", "stomp_engine_source_hash",
             "stomp_engine_refresh_field", "stomp_device_selftest_trig", "stomp_engine_retarget",
-            "stomp_group_retarget"]
+            "stomp_group_retarget", "stomp_scene_create", "stomp_scene_set_static", "stomp_scene_set_dynamic",
+            "stomp_scene_window", "stomp_scene_info", "stomp_scene_destroy"]
 
 _lib = None
 
@@ -172,6 +173,16 @@ def load_library(path: Optional[str] = None):
     l.stomp_sdf_build_objects.argtypes = [C.c_int32, C.c_int32, C.c_int32, dp, C.c_double, C.c_double,
                                           C.POINTER(stomp_shape), C.c_int32, dp, C.c_int64, C.c_void_p,
                                           C.POINTER(C.c_int64), C.c_void_p]
+    l.stomp_scene_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, C.c_double, C.c_double,
+                                     C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    for f in (l.stomp_scene_set_static, l.stomp_scene_set_dynamic):
+        f.argtypes = [C.c_void_p, C.POINTER(stomp_shape), C.c_int32, dp, C.c_int64, C.POINTER(C.c_int64)]
+    l.stomp_scene_window.argtypes = [C.c_int32, C.c_int32, C.c_int32, dp, C.c_double, C.c_double,
+                                     C.POINTER(stomp_shape), C.c_int32, dp, C.c_int64, C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_int32)]
+    l.stomp_scene_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    l.stomp_scene_destroy.argtypes = [C.c_void_p]
+    l.stomp_scene_destroy.restype = None
     l.stomp_stream_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
     l.stomp_stream_destroy.argtypes = [C.c_void_p]
     l.stomp_group_create.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]
@@ -259,6 +270,76 @@ def sdf_build_objects_device(grid, objects, device_ptr: int, points=None, stream
                                      shape_array(objects), len(objects), _dp(pts if pts.size else np.zeros(3)),
                                      len(pts), C.c_void_p(device_ptr), C.byref(marked), C.c_void_p(stream)))
     return marked.value
+
+
+def _points(points):
+    pts = np.ascontiguousarray(points if points is not None else np.zeros((0, 3)), np.float64).reshape(-1, 3)
+    return pts, _dp(pts if pts.size else np.zeros(3))
+
+
+def scene_window(grid, objects, points=None):
+    """stomp_scene_window (host only): the window Scene.set_dynamic would use for these inputs on
+    problem.Grid `grid`, as inclusive cell bounds (lo, hi), or None when nothing can land in the grid."""
+    origin = np.array(grid.origin, np.float64)
+    pts, pp = _points(points)
+    lo, hi = (C.c_int32 * 3)(), (C.c_int32 * 3)()
+    _check(load_library().stomp_scene_window(grid.nx, grid.ny, grid.nz, _dp(origin), grid.resolution,
+                                             grid.max_expansion, shape_array(objects), len(objects), pp, len(pts),
+                                             lo, hi))
+    return None if lo[0] > hi[0] else (tuple(lo), tuple(hi))
+
+
+class Scene:
+    """stomp_scene: the field of sdf_build_objects_device kept in two layers over the device buffer
+    `device_ptr` (grid.cells uint16).  set_static builds the layer that stays (shelves, walls);
+    set_dynamic replaces the per-request set (the robot's own bodies, the sensor points) and costs
+    work over the window around its marks only.  After either the buffer holds, bit for bit,
+    sdf_build_objects_device of the static inputs followed by the dynamic ones.  stream: a HIP
+    stream (Stream.ptr; None: one the scene owns) -- everything is enqueued there and, unless
+    count=True, nothing waits for the device."""
+
+    def __init__(self, grid, device_ptr: int, device: int = 0, stream: Optional[int] = None):
+        self._h = None   # set before the call that may raise, so __del__ has nothing to free
+        self.grid = grid
+        origin = np.array(grid.origin, np.float64)
+        h = C.c_void_p()
+        _check(load_library().stomp_scene_create(device, grid.nx, grid.ny, grid.nz, _dp(origin), grid.resolution,
+                                                 grid.max_expansion, C.c_void_p(device_ptr),
+                                                 C.c_void_p(stream) if stream else None, C.byref(h)))
+        self._h = h
+
+    def _set(self, fn, objects, points, count):
+        pts, pp = _points(points)
+        marked = C.c_int64(0)
+        _check(fn(self._h, shape_array(objects), len(objects), pp, len(pts), C.byref(marked) if count else None))
+        return marked.value if count else None
+
+    def set_static(self, objects, points=None, count: bool = False):
+        """The static layer from problem.SceneObject list `objects` and collision-map points (P x 3);
+        any dynamic set is dropped.  count=True waits and returns the points that landed in the grid."""
+        return self._set(load_library().stomp_scene_set_static, objects, points, count)
+
+    def set_dynamic(self, objects, points=None, count: bool = False):
+        """Replaces the dynamic set (empty lists: the static field).  count as in set_static; the
+        static and dynamic counts add up to sdf_build_objects_device's of all inputs."""
+        return self._set(load_library().stomp_scene_set_dynamic, objects, points, count)
+
+    def info(self) -> dict:
+        """stomp_scene_info (waits for the stream): the last call's window (None when empty), its
+        cells, the cells restored from the static layer, the stray marks (a check on the window
+        bound: always 0) and the allocations set_dynamic has made."""
+        v = (C.c_int64 * 10)()
+        _check(load_library().stomp_scene_info(self._h, v))
+        return dict(window=None if v[0] > v[3] else (tuple(v[0:3]), tuple(v[3:6])), cells=v[6], restored=v[7],
+                    stray=v[8], allocations=v[9], raw=list(v))
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            load_library().stomp_scene_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        self.close()
 
 
 class Engine:
