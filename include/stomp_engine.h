@@ -19,6 +19,14 @@
  *   stomp_engine_get_theta / set_theta
  *                            replace CovariantTrajectoryPolicy::getParameters/setParameters
  *                            (covariant_trajectory_policy.h:200-227)
+ *   stomp_engine_retarget / stomp_engine_retarget_request
+ *                            replace the new StompOptimizer the planner node constructs per
+ *                            request (stomp_planner_node.cpp:228-230, 421-423) on a live engine:
+ *                            start, goal and seed; with a stomp_request also the request's collision
+ *                            points and path constraints
+ *   stomp_attached_collision_points
+ *                            replaces generateAttachedObjectCollisionPoints +
+ *                            populatePlanningGroupCollisionPoints (stomp_robot_model.cpp:377-496)
  *   stomp_sdf_build          builds the distance field that
  *                            StompCollisionSpace::setStartState + PropagationDistanceField
  *                            produce (stomp_collision_space.cpp:154-197), for box and
@@ -234,6 +242,64 @@ int stomp_engine_refresh_field(stomp_engine* e);
  * stomp_group_retarget (declared with the groups below) does the same for every engine of a group. */
 int stomp_engine_retarget(stomp_engine* e, const double* start, const double* goal, uint64_t seed);
 
+/* A whole planning request for a live engine: stomp_engine_retarget's start, goal and seed, and the
+ * two things the reference's node also sets per request -- the collision points
+ * (generateAttachedObjectCollisionPoints + populatePlanningGroupCollisionPoints after setStartState,
+ * stomp_planner_node.cpp:194-199, 386-392: a robot that has grasped something plans with extra
+ * spheres on the gripper link; stomp_attached_collision_points below makes the list) and the path
+ * constraints (motion_plan_request.path_constraints, handed to every request's StompOptimizer,
+ * stomp_planner_node.cpp:229-230, 421-423).
+ * Post-condition: the engine is bit for bit the engine stomp_engine_create returns for its
+ * descriptor with start, goal, seed, spheres and orientation constraints replaced -- retarget's
+ * post-condition extended: theta, last and best trajectory are theta_0; get_pad_positions has
+ * 12 x num_spheres x 3 entries of the new list; the padding-collision flag is the new model's; every
+ * later iterate / run / optimize / eval / stomp_pi_* / get_best_torques call gives what it gives on
+ * the fresh engine.  Iteration state is dropped exactly as retarget drops it.  Kept: the matrices,
+ * the segments, the joints, the torque chain, the field and its bricked copy, the timers, the stream.
+ * With both counts -1 the call is stomp_engine_retarget.
+ * The call plans the new model on the host (the FK program, the rollout kernel's layout for it --
+ * the layout a fresh engine of this process would get, environment overrides included -- and the
+ * terms model), then commits: one upload of one pinned staging block, one launch and one read-back
+ * of the flag on the engine's stream, after everything enqueued before (iterations still in flight
+ * read the old model); it waits for the stream.  Device memory that depends on the model is held
+ * with a capacity and reallocated only when a request needs more than every earlier one; a
+ * repeated request allocates nothing (stomp_engine_model_info, info[11]).
+ * Refusals leave the engine as it was, with creation's own messages where creation has one; a
+ * refusal writes nothing of the engine, not even its last-error text (stomp_last_error() has the
+ * message).  The NULL and struct_size refusals come before the engine is read (a machine without a
+ * GPU can make these calls); the others are made while the model is planned on the host, which reads
+ * the engine and asks the engine's device for the rollout kernels' attributes, and enqueues nothing.
+ * The "inside its optimize loop" refusal may be made from another host thread than the one running
+ * stomp_engine_optimize (it reads an atomic flag); every other use of one engine from two threads
+ * stays the caller's to serialise.  A STOMP_E_DEVICE failure during the commit (an allocation, the
+ * copy, the launch, the wait) frees what the call allocated and leaves every engine's host side as
+ * it was; what the device holds is then as after any device failure.
+ * STOMP_E_INVALID: NULL engine, request, start or goal; a struct_size other than
+ * sizeof(stomp_request); a count below -1, or >= 1 without its array; a value that is not finite;
+ * a sphere or constraint segment outside the tree; a radius or clearance creation would refuse; an
+ * engine inside its optimize loop.  STOMP_E_UNSUPPORTED: a sphere list not ordered by segment; a
+ * tree that then needs more saved frames than the FK program has; a rollout or state-terms kernel
+ * over its LDS limit; more than 65535 pair ids; a constraint segment deeper than the terms kernel's
+ * path; a sharded engine. */
+typedef struct stomp_request {
+    int32_t struct_size;                 /* sizeof(stomp_request) */
+    const double* start;                 /* J */
+    const double* goal;                  /* J */
+    uint64_t seed;
+    int32_t num_spheres;                 /* -1: keep the engine's collision points */
+    const stomp_sphere* spheres;         /* ordered by segment, as at creation */
+    int32_t num_orientation_constraints; /* -1: keep the engine's path constraints; 0: none */
+    const stomp_orientation_constraint* orientation_constraints;
+} stomp_request;
+int stomp_engine_retarget_request(stomp_engine* e, const stomp_request* r);
+/* What the engine's current model is, for tests and tables: info[0] spheres S, [1] FK program
+ * steps, [2] published frame slots, [3] saved branch-point frames, [4] most spheres of one run,
+ * [5] padding positions in LDS, [6] the LDS-lean layout (0, 1, 2), [7] the sincos pre-pass,
+ * [8] orientation constraints, [9] state-cost terms on, [10] model changes so far (retarget-request
+ * calls that replaced the collision points or the constraints), [11] device or pinned allocations
+ * made inside retarget-request calls so far.  Host only. */
+int stomp_engine_model_info(stomp_engine* e, int64_t info[12]);
+
 int stomp_engine_get_theta(stomp_engine* e, double* theta);
 int stomp_engine_set_theta(stomp_engine* e, const double* theta);
 
@@ -383,6 +449,25 @@ int stomp_sdf_build_objects(int32_t nx, int32_t ny, int32_t nz, const double* or
                             double max_expansion, const stomp_shape* shapes, int32_t n_shapes,
                             const double* points, int64_t n_points, uint16_t* out_device, int64_t* marked,
                             void* stream);
+
+/* The collision points of a robot holding attached bodies (generateAttachedObjectCollisionPoints +
+ * populatePlanningGroupCollisionPoints, stomp_robot_model.cpp:377-496), host only, no device.  An
+ * attached body is a STOMP_BODY_* shape posed in the frame of its owner segment (padding folded
+ * into dims, as for robot bodies); it becomes one sphere at its bounding sphere's centre, with that
+ * radius (bodies::*::computeBoundingSphere, the rule the robot bodies' lattices use) and the given
+ * clearance (collision_clearance_default_).  Each new sphere is placed after the base list's last
+ * sphere of a segment <= its own, bodies of one segment in input order, so the output is ordered by
+ * segment whenever the base list is.  out: capacity entries; *n_out: n_base + n_bodies.  A
+ * capacity that is too small: STOMP_E_INVALID with *n_out set to the size needed and out untouched.
+ * NULL out, n_out or a count without its array, a negative count, a shape that is no STOMP_BODY_*,
+ * a mesh without four vertices, a clearance that is not positive and finite: STOMP_E_INVALID. */
+typedef struct stomp_attached_body {
+    int32_t segment;
+    stomp_shape shape;
+} stomp_attached_body;
+int stomp_attached_collision_points(const stomp_sphere* base, int32_t n_base, const stomp_attached_body* bodies,
+                                    int32_t n_bodies, double clearance, stomp_sphere* out, int32_t capacity,
+                                    int32_t* n_out);
 
 /* Scene layers: the field of stomp_sdf_build_objects kept in two layers over the caller's device
  * buffer field_device (nx*ny*nz uint16, stomp_grid's layout and representation), for a caller
@@ -537,6 +622,20 @@ int32_t stomp_group_optimize_chunk(void);
  * STOMP_E_INVALID before any engine or device is touched; a refused call leaves every engine
  * untouched. */
 int stomp_group_retarget(stomp_group* g, const double* starts, const double* goals, const uint64_t* seeds);
+/* stomp_engine_retarget_request for every engine of the group at once: requests[p] is engine p's.
+ * All P models are planned first; the planned engines must again be of one shape (the same number
+ * of spheres, the same rollout LDS size and layout: STOMP_E_INVALID otherwise), and a request that
+ * gives an engine path constraints in a group created without STOMP_GROUP_ACCEPT_STATE_TERMS is
+ * STOMP_E_UNSUPPORTED.  Only then is anything committed: one upload, one launch and one read-back for
+ * the whole group, which also rewrite the group's own copies of the engines' models.  Requests may
+ * differ per engine in the spheres' values and in the constraints.  Every refusal of
+ * stomp_engine_retarget_request applies, before any engine or device is touched; a refused call
+ * leaves every engine untouched.
+ * An engine of a group whose model was changed on its own with stomp_engine_retarget_request leaves
+ * the group's copies stale: the next stomp_group_run / synchronize / optimize / retarget returns
+ * STOMP_E_INVALID naming the engine and touches nothing, until stomp_group_retarget_requests has
+ * brought the group back in step. */
+int stomp_group_retarget_requests(stomp_group* g, const stomp_request* requests /* P */);
 const char* stomp_group_last_error(const stomp_group* g);
 void stomp_group_destroy(stomp_group* g);
 

@@ -443,6 +443,25 @@ public:
     static bool retargetBatch(const std::vector<StompOptimizer*>& optimizers,
                               const std::vector<std::vector<double>>& starts,
                               const std::vector<std::vector<double>>& goals, const std::vector<uint64_t>& seeds);
+    // retarget() with the request's collision points and path constraints too
+    // (stomp_engine_retarget_request): what the reference's node sets per request with
+    // generateAttachedObjectCollisionPoints + populatePlanningGroupCollisionPoints
+    // (stomp_attached_collision_points makes the list) and with the path_constraints it hands to
+    // every request's StompOptimizer.  nullptr keeps the optimizer's; an empty list means none.
+    // Afterwards the optimizer is the one constructed for a robot model with these collision points
+    // and for these constraints; its own copies of both follow, and a PolicyImprovement whose
+    // rollout set lives in an engine of its own (onOwnEngine()) recreates that engine from the new
+    // model at its next getRollouts.  false with lastError() when refused; nothing is changed then.
+    bool retarget(const std::vector<double>& start, const std::vector<double>& goal, uint64_t seed,
+                  const std::vector<stomp_sphere>* collision_points, const Constraints* constraints);
+    // ... for several optimizers at once (collision_points[i], constraints[i] for optimizers[i],
+    // entries may be nullptr): one launch (stomp_group_retarget_requests); the optimizers must
+    // again be of one shape.
+    static bool retargetBatch(const std::vector<StompOptimizer*>& optimizers,
+                              const std::vector<std::vector<double>>& starts,
+                              const std::vector<std::vector<double>>& goals, const std::vector<uint64_t>& seeds,
+                              const std::vector<const std::vector<stomp_sphere>*>& collision_points,
+                              const std::vector<const Constraints*>& constraints);
     const STOMPStatistics& getStatistics() const { return stats_; }
 
     // Task (stomp_optimizer.cpp:1063-1165, 1167-1182)
@@ -494,6 +513,9 @@ private:
     bool check(int rc);
     bool finishOptimize(const stomp_stats& st);
     void followRetarget(const std::vector<double>& start, const std::vector<double>& goal, uint64_t seed);
+    void followModel(const std::vector<stomp_sphere>* collision_points, const Constraints* constraints);
+    stomp_request request(const std::vector<double>& start, const std::vector<double>& goal, uint64_t seed,
+                          const std::vector<stomp_sphere>* collision_points, const Constraints* constraints) const;
     // an engine of the same problem with other rollout counts / cumulative-cost setting (the
     // device rollout set of a PolicyImprovement that asks for them); nullptr and err on failure
     stomp_engine* createSibling(int num_rollouts, int num_reused_rollouts, bool use_cumulative_costs,
@@ -520,6 +542,7 @@ private:
     bool last_cs_ = true;
     STOMPStatistics stats_;
     std::string error_;
+    long long model_epoch_ = 0;         // retargets that replaced the collision points or the constraints
 };
 
 // policy_improvement.h:65-126 / policy_improvement.cpp:64-489.  Where the rollout set lives,
@@ -611,6 +634,8 @@ private:
     std::shared_ptr<HostRollouts> host_;
     uint64_t seed_ = 0x53544F4D50000000ull;
     int J_ = 0, N_ = 0, K_ = 0, K_gen_ = 0, noise_iteration_ = 1;
+    int Kr_ = 0;                        // the device rollout set's reused rollouts
+    long long own_epoch_ = 0;           // the optimizer's model epoch own_ was made from
     bool use_cumulative_ = false;
     bool initialized_ = false;
     std::string error_;

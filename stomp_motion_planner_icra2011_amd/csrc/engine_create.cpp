@@ -14,57 +14,66 @@ namespace {
 // getCollisionPointPotentialGradient (stomp_collision_space.h:193-228) as thresholds on a voxel's
 // squared cell distance d2, whose distance is sqrt((double)d2) * res (the field's sqrt_table_):
 //   potential == 0  <=>  d2 >= zero_lim      in collision  <=>  d2 < col_lim
-// Every d2 a 16-bit voxel can hold is priced with the reference's expressions (one rounding per
-// operation, as the kernel's), and each predicate is checked to switch exactly once, so the
-// kernel's integer compares give the same answers as the potential itself.
+// A d2 is priced with the reference's expressions (one rounding per operation, as the kernel's).
+// Each predicate switches at most once over the d2 a 16-bit voxel can hold: sqrt, the product with
+// a positive res and the difference with radius are each monotone under rounding to nearest, so
+// dist and dist - radius never decrease with d2.  The first d2 at which a predicate holds is
+// therefore found by bisection (a request re-plans every sphere on the host: 17 evaluations per
+// threshold instead of 65536), and the kernel's integer compares give the same answers as the
+// potential itself.
+template <class Pred>
+int first_d2(Pred pred)   // the first d2 in [0, 65535] with pred(d2), or 65536
+{
+    int lo = 0, hi = 65536;
+    while (lo < hi) {
+        const int mid = (lo + hi) / 2;
+        if (pred(mid)) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
 bool sphere_thresholds(double radius, double clearance, double res, int* zero_lim, int* col_lim)
 {
     if (!(radius >= 0.0 && clearance > 0.0 && std::isfinite(radius) && std::isfinite(clearance))) return false;
-    int zl = 65536, cl = 65536;
-    bool zseen = false, cseen = false;
-    for (int d2 = 0; d2 <= 65535; ++d2) {
-        const double dist = std::sqrt((double)d2) * res;
-        const double dd = dist - radius;
-        const bool zero = dd >= clearance;
-        const bool col = dist <= radius;
-        if (zero && !zseen) { zl = d2; zseen = true; }
-        if (!zero && zseen) return false;
-        if (!col && !cseen) { cl = d2; cseen = true; }
-        if (col && cseen) return false;
-    }
-    *zero_lim = zl;
-    *col_lim = cl;
+    *zero_lim = first_d2([&](int d2) { return std::sqrt((double)d2) * res - radius >= clearance; });
+    *col_lim = first_d2([&](int d2) { return !(std::sqrt((double)d2) * res <= radius); });
     return true;
 }
 
 // FK program: frames of the segments that carry spheres or are their ancestors, in
 // DFS order, each composed from its parent's live slot; sphere runs emitted in list
 // order right after their segment's frame (requires sphere segments non-decreasing).
-int plan_fk(stomp_engine* e, const stomp_engine_desc* d, std::vector<FkOp>& ops)
+int plan_fk(stomp_engine* e, const std::vector<DevSegment>& segs, int N, const stomp_sphere* spheres, int S,
+            ModelTables& t)
 {
-    const int ns = d->num_segments;
+    const int ns = (int)segs.size();
+    std::vector<FkOp>& ops = t.ops;
+    ops.clear();
+    t.nslots = 0;
+    t.sphere_slot.assign(std::max(S, 1), 0);
     std::vector<char> needed(ns, 0);
     int prev = -1;
-    for (int j = 0; j < d->num_spheres; ++j) {
-        int s = d->spheres[j].segment;
+    for (int j = 0; j < S; ++j) {
+        int s = spheres[j].segment;
         if (s < prev)
             return fail(e, STOMP_E_UNSUPPORTED,
                         "sphere list must be ordered by segment (sphere %d on segment %d after segment %d)", j, s, prev);
         prev = s;
-        for (int a = s; a >= 0 && !needed[a]; a = d->segments[a].parent) needed[a] = 1;
+        for (int a = s; a >= 0 && !needed[a]; a = segs[a].parent) needed[a] = 1;
     }
     // DFS order: the next needed segment after s is its first needed child, so a chain
     // continues from the running frame C; a segment with several needed children is saved
     // and its later children start from the saved copy.
     std::vector<int> remaining(ns, 0), slot_of(ns, -1);
     for (int s = 0; s < ns; ++s)
-        if (needed[s] && d->segments[s].parent >= 0) remaining[d->segments[s].parent]++;
+        if (needed[s] && segs[s].parent >= 0) remaining[segs[s].parent]++;
     bool used[kSaves] = {false, false};
-    const int runmax = run_max(d->num_time_steps);
+    const int runmax = run_max(N);
     int sph = 0, cur = -1;
     for (int s = 0; s < ns; ++s) {
         if (!needed[s]) continue;
-        const int p = d->segments[s].parent;
+        const int p = segs[s].parent;
         int base;
         if (p < 0) base = kBaseRoot;
         else if (p == cur) base = kBaseChain;
@@ -83,9 +92,9 @@ int plan_fk(stomp_engine* e, const stomp_engine_desc* d, std::vector<FkOp>& ops)
         }
         cur = s;
         int b = sph;
-        while (sph < d->num_spheres && d->spheres[sph].segment == s) ++sph;
-        const int slot = sph > b ? e->nslots++ : -1;
-        for (int j = b; j < sph; ++j) e->sphere_slot[j] = slot;
+        while (sph < S && spheres[sph].segment == s) ++sph;
+        const int slot = sph > b ? t.nslots++ : -1;
+        for (int j = b; j < sph; ++j) t.sphere_slot[j] = slot;
         bool first = true;
         for (int a = b; a < sph || first; a += runmax) {
             FkOp o;
@@ -152,16 +161,156 @@ void oc_nominal_inverse(const double* q, double* O)
     O[6] = co2 * sc; O[7] = cof(0, 1, 2, 0) * sc; O[8] = cof(0, 0, 1, 1) * sc;
 }
 
+}  // namespace
+
+// The stages that depend on the collision points and the path constraints.  Creation runs them on
+// the engine under construction and stomp_engine_retarget_request on a live one (e: the engine
+// whose scalars, kinematic tree and joint limits they read; err: where a refusal's message goes,
+// null on a live engine, which must stay as it was).  None of them touches a device.
+namespace stomp {
+
+int validate_spheres(const stomp_sphere* spheres, int n, int num_segments, double resolution)
+{
+    for (int j = 0; j < n; ++j) {
+        if (spheres[j].segment < 0 || spheres[j].segment >= num_segments)
+            return fail(nullptr, STOMP_E_INVALID, "sphere %d: bad segment", j);
+        int zl, cl;
+        if (!sphere_thresholds(spheres[j].radius, spheres[j].clearance, resolution, &zl, &cl))
+            return fail(nullptr, STOMP_E_INVALID, "sphere %d: radius / clearance not finite and positive", j);
+    }
+    return 0;
+}
+
+int validate_constraints(const stomp_orientation_constraint* oc, int n, int num_segments)
+{
+    if (n < 0 || (n > 0 && !oc)) return fail(nullptr, STOMP_E_INVALID, "invalid orientation constraints");
+    for (int c = 0; c < n; ++c)
+        if (oc[c].segment < 0 || oc[c].segment >= num_segments)
+            return fail(nullptr, STOMP_E_INVALID, "orientation constraint %d: bad segment", c);
+    return 0;
+}
+
+// the FK program, the spheres as the kernels hold them, each published frame slot's first sphere
+int plan_model_tables(stomp_engine* err, const stomp_engine* e, const stomp_sphere* spheres, int S, ModelTables& t)
+{
+    t.S = S;
+    if (int rc = plan_fk(err, e->h_segs, e->N, spheres, S, t)) return rc;
+    t.sph.assign(std::max(S, 1), DevSphere{});
+    for (int j = 0; j < S; ++j) {
+        const stomp_sphere& g = spheres[j];
+        DevSphere& o = t.sph[j];
+        o.slot = t.sphere_slot[j];
+        o.radius = g.radius; o.clearance = g.clearance;
+        o.inv_clearance = 1.0 / g.clearance;   // stomp_collision_point.cpp:50
+        std::memcpy(o.pos, g.pos, sizeof g.pos);
+        sphere_thresholds(g.radius, g.clearance, e->model.res, &o.zero_lim, &o.col_lim);
+        o.pad_ = 0;
+    }
+    // slots are numbered in sphere order, so each slot owns a contiguous sphere range
+    t.slot_sph.assign(t.nslots + 1, S);
+    for (int j = S - 1; j >= 0; --j) t.slot_sph[t.sphere_slot[j]] = j;
+    return 0;
+}
+
+// the path constraints (OrientationConstraintEvaluator) as k_terms holds them
+int plan_constraints(stomp_engine* err, const stomp_engine* e, const stomp_orientation_constraint* ocs, int n,
+                     std::vector<OcDev>& oc)
+{
+    oc.assign(std::max(n, 0), OcDev{});
+    for (int c = 0; c < n; ++c) {
+        const stomp_orientation_constraint& in = ocs[c];
+        OcDev& o = oc[c];
+        std::vector<int> path;
+        for (int sgi = in.segment; sgi >= 0; sgi = e->h_segs[sgi].parent) path.push_back(sgi);
+        if ((int)path.size() > kMaxChain)
+            return fail(err, STOMP_E_UNSUPPORTED, "constraint segment deeper than %d", kMaxChain);
+        std::reverse(path.begin(), path.end());
+        o.seg = in.segment; o.body_fixed = in.body_fixed ? 1 : 0; o.path_len = (int)path.size();
+        for (size_t k = 0; k < path.size(); ++k) o.path[k] = path[k];
+        oc_nominal_inverse(in.orientation, o.ninv);
+        o.tol[0] = in.absolute_roll_tolerance; o.tol[1] = in.absolute_pitch_tolerance;
+        o.tol[2] = in.absolute_yaw_tolerance; o.weight = in.weight;
+        o.rw = o.pw = o.yw = 1.0;   // constraint_evaluator.cpp:66-72
+        if (o.tol[1] >= M_PI) o.pw = 0.0;
+        if (o.tol[0] >= M_PI) o.rw = 0.0;
+        if (o.tol[2] >= M_PI) o.yw = 0.0;
+    }
+    return 0;
+}
+
+// what every terms model holds besides its chain and its constraints; the kernel's LDS limit for
+// an engine whose terms run (terms_on)
+int plan_terms(stomp_engine* err, const stomp_engine* e, TermsModel& t, bool terms_on)
+{
+    t.J = e->J; t.N = e->N;
+    const double invTime = 1.0 / e->disc, invTime2 = 1.0 / (e->disc * e->disc);   // stomp_trajectory.h:289, 301
+    for (int k = 0; k < 7; ++k) {
+        t.cv[k] = invTime * kDiffRules[0][k];
+        t.ca[k] = invTime2 * kDiffRules[1][k];
+    }
+    t.start = e->d_start; t.goal = e->d_goal;
+    t.w_con = e->w_con; t.w_tq = e->w_tq;
+    if (terms_on && terms_lds_bytes(t) > 160 * 1024)
+        return fail(err, STOMP_E_UNSUPPORTED, "state-terms kernel needs %zu B of LDS", terms_lds_bytes(t));
+    return 0;
+}
+
+// the rollout kernel's LDS table image for a model (RolloutLds from .sph on, padding positions last)
+RolloutLds model_image_layout(const stomp_engine* e, const DevModel& m)
+{
+    return rollout_lds(e->J, e->N, m.S, m.sph_chunk, m.nsaves, m.nseg, m.nops, m.nslots, 1);
+}
+
+size_t model_image_bytes(const stomp_engine* e, const DevModel& m)
+{
+    const RolloutLds L = model_image_layout(e, m);
+    return L.total - L.sph;
+}
+
+// the image's tables (everything before the padding positions), [0, L.pad - L.sph)
+std::vector<unsigned char> build_model_image(const stomp_engine* e, const ModelTables& t, const DevModel& m)
+{
+    const int J = e->J;
+    const RolloutLds L = model_image_layout(e, m);
+    std::vector<unsigned char> img(L.pad - L.sph, 0);
+    auto put = [&](size_t off, const void* src, size_t bytes) {
+        if (bytes) std::memcpy(img.data() + (off - L.sph), src, bytes);
+    };
+    std::vector<double> jlim(2 * (size_t)J);
+    for (int j = 0; j < J; ++j) { jlim[2 * j] = e->h_jmin[j]; jlim[2 * j + 1] = e->h_jmax[j]; }
+    put(L.sph, t.sph.data(), sizeof(DevSphere) * t.S);
+    put(L.seg, e->h_segs.data(), sizeof(DevSegment) * e->h_segs.size());
+    put(L.ops, t.ops.data(), sizeof(FkOp) * t.ops.size());
+    put(L.slot, t.slot_sph.data(), sizeof(int) * t.slot_sph.size());
+    put(L.hl, e->h_has_lim.data(), sizeof(int) * J);
+    put(L.jlim, jlim.data(), sizeof(double) * jlim.size());
+    return img;
+}
+
+// the model's pointers into its image at d_img (every one of them moves with S)
+void point_model_into_image(const stomp_engine* e, DevModel& m, unsigned long long* d_img)
+{
+    const RolloutLds L = model_image_layout(e, m);
+    const unsigned char* base = (const unsigned char*)d_img;
+    m.img = d_img;
+    m.img_words = (int)(((m.pad_lds ? L.total : L.pad) - L.sph) / 8);
+    m.sph = (const DevSphere*)(base + (L.sph - L.sph));
+    m.segs = (const DevSegment*)(base + (L.seg - L.sph));
+    m.ops = (const FkOp*)(base + (L.ops - L.sph));
+    m.slot_sph = (const int*)(base + (L.slot - L.sph));
+    m.pad_pos = (const double*)(base + (L.pad - L.sph));
+}
+
+}  // namespace stomp
+
+namespace {
+
 // The host tables several stages read, alive until creation's last synchronisation (they are
-// pageable sources of asynchronous uploads): the transposed setup matrices, the kinematic tree and
-// the spheres as the kernels hold them, each published frame slot's first sphere, the joint limits.
+// pageable sources of asynchronous uploads): the transposed setup matrices.  (The kinematic tree,
+// the joint limits and the sphere tables stay with the engine: h_segs, h_has_lim, h_jmin / h_jmax, mt.)
 struct HostTables {
     std::vector<double> LT, MT, QT;
     std::vector<double> Rb, RinvT;   // stomp_engine_retarget's tables (engine_internal.h)
-    std::vector<DevSegment> segs;
-    std::vector<DevSphere> sph;
-    std::vector<int> slot_sph, has_lim;
-    std::vector<double> jmin, jmax;
 };
 
 // Owner of the engine under construction: a stage that fails leaves its message in the engine,
@@ -189,11 +338,8 @@ int validate_desc(const stomp_engine_desc* d)
     if (d->num_rollouts <= 0) return fail(nullptr, STOMP_E_INVALID, "num_rollouts must be positive");
     if (d->num_reused_rollouts < 0 || d->num_reused_rollouts >= d->num_rollouts)
         return fail(nullptr, STOMP_E_INVALID, "Number of reused rollouts must be strictly less than number of rollouts.");
-    if (d->num_orientation_constraints < 0 || (d->num_orientation_constraints > 0 && !d->orientation_constraints))
-        return fail(nullptr, STOMP_E_INVALID, "invalid orientation constraints");
-    for (int c = 0; c < d->num_orientation_constraints; ++c)
-        if (d->orientation_constraints[c].segment < 0 || d->orientation_constraints[c].segment >= d->num_segments)
-            return fail(nullptr, STOMP_E_INVALID, "orientation constraint %d: bad segment", c);
+    if (int rc = validate_constraints(d->orientation_constraints, d->num_orientation_constraints, d->num_segments))
+        return rc;
     if (d->num_segments <= 0 || !d->segments || (d->num_spheres > 0 && !d->spheres) || !d->joints || !d->noise_stddev ||
         !d->noise_decay || !d->start || !d->goal || !d->grid.data)
         return fail(nullptr, STOMP_E_INVALID, "missing table pointer");
@@ -204,13 +350,7 @@ int validate_desc(const stomp_engine_desc* d)
     for (int s = 0; s < d->num_segments; ++s)
         if (d->segments[s].parent >= s || d->segments[s].q_index >= d->num_joints)
             return fail(nullptr, STOMP_E_INVALID, "segment %d: parent must precede it (DFS order), q_index < J", s);
-    for (int j = 0; j < d->num_spheres; ++j) {
-        if (d->spheres[j].segment < 0 || d->spheres[j].segment >= d->num_segments)
-            return fail(nullptr, STOMP_E_INVALID, "sphere %d: bad segment", j);
-        int zl, cl;
-        if (!sphere_thresholds(d->spheres[j].radius, d->spheres[j].clearance, d->grid.resolution, &zl, &cl))
-            return fail(nullptr, STOMP_E_INVALID, "sphere %d: radius / clearance not finite and positive", j);
-    }
+    if (int rc = validate_spheres(d->spheres, d->num_spheres, d->num_segments, d->grid.resolution)) return rc;
     if (d->torque_cost_weight > 1e-9) {
         std::vector<int> path;
         if (const char* why = torque_chain(d, path)) return fail(nullptr, STOMP_E_UNSUPPORTED, "%s", why);
@@ -245,6 +385,7 @@ int open_engine(stomp_engine* e, const stomp_engine_desc* d)
     e->world = world; e->rank = world > 1 ? d->rank : 0;
     e->K_loc = e->K / world; e->first = e->rank * e->K_loc;
     e->S = d->num_spheres; e->nseg = d->num_segments; e->seed = d->seed;
+    e->model.res = d->grid.resolution;   // (the sphere thresholds read it before finish_model)
     e->disc = d->discretization; e->w_smooth = d->smoothness_cost_weight; e->w_obs = d->obstacle_cost_weight;
     e->w_con = d->constraint_cost_weight; e->w_tq = d->torque_cost_weight;
     for (int r = 0; r < 3; ++r) e->smooth[r] = d->smoothness_costs[r];
@@ -312,8 +453,21 @@ int choose_decomposition(stomp_engine* e, const stomp_engine_desc* d, bool local
 // the host tables
 int setup_tables(stomp_engine* e, const stomp_engine_desc* d, HostTables& t)
 {
-    e->sphere_slot.assign(std::max(e->S, 1), 0);
-    if (int rc = plan_fk(e, d, e->ops)) return rc;
+    e->h_segs.resize(e->nseg);
+    for (int s = 0; s < e->nseg; ++s) {
+        const stomp_segment& g = d->segments[s];
+        DevSegment& o = e->h_segs[s];
+        o.parent = g.parent; o.q_index = g.q_index;
+        std::memcpy(o.rot, g.rot, sizeof g.rot);
+        // as the oracle's so_rot_identity: products with it are skipped on both sides
+        o.rot_identity = g.rot[0] == 1.0 && g.rot[1] == 0.0 && g.rot[2] == 0.0 && g.rot[3] == 0.0 &&
+                         g.rot[4] == 1.0 && g.rot[5] == 0.0 && g.rot[6] == 0.0 && g.rot[7] == 0.0 &&
+                         g.rot[8] == 1.0;
+        o.pad_ = 0;
+        std::memcpy(o.trans, g.trans, sizeof g.trans);
+        std::memcpy(o.axis, g.axis, sizeof g.axis);
+    }
+    if (int rc = plan_model_tables(e, e, d->spheres, e->S, e->mt)) return rc;
     SetupInput si;
     si.J = e->J; si.N = e->N; si.discretization = e->disc;
     for (int r = 0; r < 3; ++r) si.smoothness_costs[r] = e->smooth[r];
@@ -348,42 +502,14 @@ int setup_tables(stomp_engine* e, const stomp_engine_desc* d, HostTables& t)
         }
     for (int i = 0; i < N; ++i)
         for (int k = 0; k < N; ++k) t.RinvT[(size_t)k * N + i] = e->su.Rinv[(size_t)i * N + k];
-    t.segs.resize(e->nseg);
-    for (int s = 0; s < e->nseg; ++s) {
-        const stomp_segment& g = d->segments[s];
-        DevSegment& o = t.segs[s];
-        o.parent = g.parent; o.q_index = g.q_index;
-        std::memcpy(o.rot, g.rot, sizeof g.rot);
-        // as the oracle's so_rot_identity: products with it are skipped on both sides
-        o.rot_identity = g.rot[0] == 1.0 && g.rot[1] == 0.0 && g.rot[2] == 0.0 && g.rot[3] == 0.0 &&
-                         g.rot[4] == 1.0 && g.rot[5] == 0.0 && g.rot[6] == 0.0 && g.rot[7] == 0.0 &&
-                         g.rot[8] == 1.0;
-        o.pad_ = 0;
-        std::memcpy(o.trans, g.trans, sizeof g.trans);
-        std::memcpy(o.axis, g.axis, sizeof g.axis);
-    }
-    t.sph.resize(std::max(e->S, 1));
-    for (int j = 0; j < e->S; ++j) {
-        const stomp_sphere& g = d->spheres[j];
-        DevSphere& o = t.sph[j];
-        o.slot = e->sphere_slot[j];
-        o.radius = g.radius; o.clearance = g.clearance;
-        o.inv_clearance = 1.0 / g.clearance;   // stomp_collision_point.cpp:50
-        std::memcpy(o.pos, g.pos, sizeof g.pos);
-        sphere_thresholds(g.radius, g.clearance, d->grid.resolution, &o.zero_lim, &o.col_lim);
-        o.pad_ = 0;
-    }
-    t.has_lim.resize(J);
-    t.jmin.resize(J);
-    t.jmax.resize(J);
+    e->h_has_lim.resize(J);
+    e->h_jmin.resize(J);
+    e->h_jmax.resize(J);
     for (int j = 0; j < J; ++j) {
-        t.has_lim[j] = d->joints[j].has_limits;
-        t.jmin[j] = d->joints[j].min;
-        t.jmax[j] = d->joints[j].max;
+        e->h_has_lim[j] = d->joints[j].has_limits;
+        e->h_jmin[j] = d->joints[j].min;
+        e->h_jmax[j] = d->joints[j].max;
     }
-    // slots are numbered in sphere order, so each slot owns a contiguous sphere range
-    t.slot_sph.assign(e->nslots + 1, e->S);
-    for (int j = e->S - 1; j >= 0; --j) t.slot_sph[e->sphere_slot[j]] = j;
     return 0;
 }
 
@@ -505,7 +631,7 @@ int build_torque_chain(stomp_engine* e, const stomp_engine_desc* d, const HostTa
     if (torque_chain(d, path) != nullptr) return 0;
     std::vector<ChainSeg> cs(path.size());
     for (size_t i = 0; i < path.size(); ++i) {
-        cs[i].seg = tab.segs[path[i]];
+        cs[i].seg = e->h_segs[path[i]];
         // KDL::RigidBodyInertia(m, c, Ic): h = m c, I = Ic - m (c c^T - (c.c) 1)
         const stomp_inertia& in = d->inertias[path[i]];
         const double* c = in.com;
@@ -534,29 +660,12 @@ int build_torque_chain(stomp_engine* e, const stomp_engine_desc* d, const HostTa
 int build_constraints(stomp_engine* e, const stomp_engine_desc* d)
 {
     if (d->num_orientation_constraints <= 0) return 0;
-    std::vector<OcDev> oc(d->num_orientation_constraints);
-    for (int c = 0; c < d->num_orientation_constraints; ++c) {
-        const stomp_orientation_constraint& in = d->orientation_constraints[c];
-        OcDev& o = oc[c];
-        std::vector<int> path;
-        for (int sgi = in.segment; sgi >= 0; sgi = d->segments[sgi].parent) path.push_back(sgi);
-        if ((int)path.size() > kMaxChain)
-            return fail(e, STOMP_E_UNSUPPORTED, "constraint segment deeper than %d", kMaxChain);
-        std::reverse(path.begin(), path.end());
-        o.seg = in.segment; o.body_fixed = in.body_fixed ? 1 : 0; o.path_len = (int)path.size();
-        for (size_t k = 0; k < path.size(); ++k) o.path[k] = path[k];
-        oc_nominal_inverse(in.orientation, o.ninv);
-        o.tol[0] = in.absolute_roll_tolerance; o.tol[1] = in.absolute_pitch_tolerance;
-        o.tol[2] = in.absolute_yaw_tolerance; o.weight = in.weight;
-        o.rw = o.pw = o.yw = 1.0;   // constraint_evaluator.cpp:66-72
-        if (o.tol[1] >= M_PI) o.pw = 0.0;
-        if (o.tol[0] >= M_PI) o.rw = 0.0;
-        if (o.tol[2] >= M_PI) o.yw = 0.0;
-    }
-    OcDev* d_oc;
-    if (int rc = upload(e, &d_oc, oc.data(), oc.size())) return rc;
+    std::vector<OcDev> oc;
+    if (int rc = plan_constraints(e, e, d->orientation_constraints, d->num_orientation_constraints, oc)) return rc;
+    if (int rc = upload(e, &e->d_oc, oc.data(), oc.size())) return rc;
+    e->oc_cap = oc.size();
     e->terms.noc = (int)oc.size();
-    e->terms.oc = d_oc;
+    e->terms.oc = e->d_oc;
     e->terms_on = true;
     return 0;
 }
@@ -570,19 +679,9 @@ int build_terms(stomp_engine* e, const stomp_engine_desc* d, const HostTables& t
     if (int rc = build_constraints(e, d)) return rc;
     if (e->terms_on || e->torque_stats) {
         TermsModel& t = e->terms;
-        t.J = J; t.N = N;
-        const double invTime = 1.0 / e->disc, invTime2 = 1.0 / (e->disc * e->disc);   // stomp_trajectory.h:289, 301
-        for (int k = 0; k < 7; ++k) {
-            t.cv[k] = invTime * kDiffRules[0][k];
-            t.ca[k] = invTime2 * kDiffRules[1][k];
-        }
-        t.start = e->d_start; t.goal = e->d_goal;
-        t.w_con = e->w_con; t.w_tq = e->w_tq;
-        if (terms_lds_bytes(t) > 160 * 1024) {
-            if (e->terms_on)
-                return fail(e, STOMP_E_UNSUPPORTED, "state-terms kernel needs %zu B of LDS", terms_lds_bytes(t));
+        if (int rc = plan_terms(e, e, t, e->terms_on)) return rc;
+        if (terms_lds_bytes(t) > 160 * 1024)
             e->torque_stats = false;   // the chain stays in e->terms: get_best_torques says why it cannot run
-        }
         if (getenv("STOMP_DEBUG_LEAN_PRINT"))   // the launch launch_terms takes (read-only: tests and tables)
             fprintf(stderr, "stomp: terms J %d N %d nchain %d noc %d torque %d stats %d, k_terms<%d>, LDS %zu B, "
                             "opt-in %d\n", J, N, t.nchain, t.noc, t.torque, e->torque_stats ? 1 : 0, N <= 128 ? 128 : 256,
@@ -603,36 +702,44 @@ int build_terms(stomp_engine* e, const stomp_engine_desc* d, const HostTables& t
     return 0;
 }
 
+}  // namespace
+
+namespace stomp {
+
 // Stage 6: the rollout kernel's layout for this model and launch size: the sincos pre-pass, the
 // padding rows' positions in LDS or not, the LDS-lean slot-loop layouts
-int choose_layout(stomp_engine* e, const stomp_engine_desc* d, const HostTables& tab)
+// (a shared stage as those above: m is the model under construction, or on a live engine a copy of
+// its model whose compute-unit count is already known; the kernels' attributes are asked of the
+// current device, the engine's)
+int choose_layout(stomp_engine* err, const stomp_engine* e, const ModelTables& t, DevModel& m)
 {
     const int J = e->J, N = e->N;
-    DevModel& m = e->model;
-    m.J = J; m.N = N; m.Nall = e->Nall; m.S = e->S; m.nops = (int)e->ops.size(); m.nseg = e->nseg;
-    m.nslots = e->nslots;
+    const std::vector<FkOp>& ops = t.ops;
+    m.J = J; m.N = N; m.Nall = e->Nall; m.S = t.S; m.nops = (int)ops.size(); m.nseg = e->nseg;
+    m.nslots = t.nslots;
     m.sph_chunk = 1;   // the a-value buffer holds the longest sphere run
-    for (const FkOp& o : e->ops) m.sph_chunk = std::max(m.sph_chunk, o.sph_end - o.sph_begin);
+    for (const FkOp& o : ops) m.sph_chunk = std::max(m.sph_chunk, o.sph_end - o.sph_begin);
     if (m.sph_chunk * N > 65535)
-        return fail(e, STOMP_E_UNSUPPORTED, "%d spheres on one segment x %d waypoints exceed 16-bit pair ids",
+        return fail(err, STOMP_E_UNSUPPORTED, "%d spheres on one segment x %d waypoints exceed 16-bit pair ids",
                     m.sph_chunk, N);
     m.nsaves = 0;
-    for (const FkOp& o : e->ops) m.nsaves = std::max(m.nsaves, o.save + 1);
+    for (const FkOp& o : ops) m.nsaves = std::max(m.nsaves, o.save + 1);
     // the sincos pre-pass parks the cosines in the saved-frame area: only when that area
     // holds J x N doubles and the first save comes after the last joint segment
-    int last_joint = -1, first_save = (int)e->ops.size();
-    for (int i = 0; i < (int)e->ops.size(); ++i) {
-        const FkOp& o = e->ops[i];
-        if (o.seg >= 0 && tab.segs[o.seg].q_index >= 0) last_joint = i;
-        if (o.save >= 0 && first_save == (int)e->ops.size()) first_save = i;
+    int last_joint = -1, first_save = (int)ops.size();
+    for (int i = 0; i < (int)ops.size(); ++i) {
+        const FkOp& o = ops[i];
+        if (o.seg >= 0 && e->h_segs[o.seg].q_index >= 0) last_joint = i;
+        if (o.save >= 0 && first_save == (int)ops.size()) first_save = i;
     }
     m.sincos_pre = m.nsaves >= 1 && J <= 12 * m.nsaves && first_save > last_joint ? 1 : 0;
     // padding-row positions go to LDS unless that costs a workgroup per CU the launch
     // would use: one rollout launch has K_loc + 1 workgroups over the device's CUs
     const size_t stat = rollout_static_lds();
     const size_t with_pad = rollout_lds_bytes(m, 1) + stat, without = rollout_lds_bytes(m, 0) + stat;
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d->device) != hipSuccess || cus <= 0)
+    int cus = m.cus;
+    if (cus <= 0 &&
+        (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || cus <= 0))
         cus = 256;
     m.cus = cus;
     // every workgroup of the launch counts: the rollouts, the noiseless one, the pregen blocks
@@ -647,8 +754,8 @@ int choose_layout(stomp_engine* e, const stomp_engine_desc* d, const HostTables&
     m.phased_lds = (int)rollout_phased_lds_bytes(m);
     if (getenv("STOMP_DEBUG_PHASED")) fprintf(stderr, "stomp: phased rollout LDS %d B\n", m.phased_lds);
     if (lds > kRolloutLdsMax)
-        return fail(e, STOMP_E_UNSUPPORTED, "rollout kernel needs %zu B of LDS (J=%d, N=%d, S=%d, %d spheres "
-                                            "on one segment), more than %zu", lds, J, N, e->S, m.sph_chunk,
+        return fail(err, STOMP_E_UNSUPPORTED, "rollout kernel needs %zu B of LDS (J=%d, N=%d, S=%d, %d spheres "
+                                              "on one segment), more than %zu", lds, J, N, m.S, m.sph_chunk,
                     kRolloutLdsMax);
     // the LDS-lean slot-loop layout (DevModel::lean) when it puts more rollout workgroups on a
     // CU and the launch has more workgroups than the full layout's slots: cfg3's N = 199 (71.7
@@ -675,42 +782,42 @@ int choose_layout(stomp_engine* e, const stomp_engine_desc* d, const HostTables&
         fprintf(stderr, "stomp: rollout LDS full %zu / lean1 %zu / lean2 %zu B, workgroups per CU %d / %d / %d, "
                         "needed %d, layout lean %d\n", lds, rollout_lds_bytes(m, 0, 1) + stat,
                 rollout_lds_bytes(m, 0, 2) + stat, per_cu[0], per_cu[1], per_cu[2], need, m.lean);
-    if (!cost_supported(m)) return fail(e, STOMP_E_UNSUPPORTED, "FK program too large (%d ops, %d segments)",
+    if (!cost_supported(m)) return fail(err, STOMP_E_UNSUPPORTED, "FK program too large (%d ops, %d segments)",
                                         m.nops, m.nseg);
     return 0;
 }
 
-// Stage 7: the rollout kernel's LDS table image (RolloutLds from .sph on), padding positions last
-int upload_lds_image(stomp_engine* e, const HostTables& tab)
+// the lean layout's saved-frame blocks, [nsaves][12][N] per rollout workgroup of a launch, in the
+// buffer held for them (d_sv, sv_cap: the engine's fields at creation, a commit's copies of them on
+// a live engine; grown when this model needs more, as grow_buffer does)
+int place_saved_frames(stomp_engine* e, DevModel& m, double** d_sv, size_t* sv_cap, LiveAlloc* live)
 {
-    const int J = e->J, N = e->N;
+    m.sv_glob = nullptr;
+    m.sv_rows = 0;
+    if (!(m.lean && m.nsaves > 0)) return 0;
+    m.sv_rows = e->K_loc + 1;
+    if (int rc = grow_buffer(e, d_sv, sv_cap, (size_t)m.sv_rows * m.nsaves * 12 * e->N, live)) return rc;
+    m.sv_glob = *d_sv;
+    return 0;
+}
+
+}  // namespace stomp
+
+namespace {
+
+// Stage 7: the rollout kernel's LDS table image (RolloutLds from .sph on), padding positions last
+int upload_lds_image(stomp_engine* e)
+{
     DevModel& m = e->model;
-    const RolloutLds L = rollout_lds(J, N, e->S, m.sph_chunk, m.nsaves, m.nseg, m.nops, m.nslots, 1);
-    std::vector<unsigned char> img(L.total - L.sph, 0);
-    auto put = [&](size_t off, const void* src, size_t bytes) {
-        if (bytes) std::memcpy(img.data() + (off - L.sph), src, bytes);
-    };
-    std::vector<double> jlim(2 * (size_t)J);
-    for (int j = 0; j < J; ++j) { jlim[2 * j] = tab.jmin[j]; jlim[2 * j + 1] = tab.jmax[j]; }
-    put(L.sph, tab.sph.data(), sizeof(DevSphere) * e->S);
-    put(L.seg, tab.segs.data(), sizeof(DevSegment) * tab.segs.size());
-    put(L.ops, e->ops.data(), sizeof(FkOp) * e->ops.size());
-    put(L.slot, tab.slot_sph.data(), sizeof(int) * tab.slot_sph.size());
-    put(L.hl, tab.has_lim.data(), sizeof(int) * J);
-    put(L.jlim, jlim.data(), sizeof(double) * jlim.size());
-    unsigned long long* d_img;
-    if (int rc = upload(e, &d_img, (const unsigned long long*)img.data(), img.size() / 8)) return rc;
+    std::vector<unsigned char> img = build_model_image(e, e->mt, m);
+    img.resize(model_image_bytes(e, m), 0);
+    if (int rc = upload(e, &e->d_img, (const unsigned long long*)img.data(), img.size() / 8)) return rc;
+    e->img_cap = img.size() / 8;
     if (hipStreamSynchronize(e->stream) != hipSuccess)   // img is pageable and goes out of scope
         return fail(e, STOMP_E_DEVICE, "table upload failed");
-    const unsigned char* base = (const unsigned char*)d_img;
-    m.img = d_img;
-    m.img_words = (int)(((m.pad_lds ? L.total : L.pad) - L.sph) / 8);
-    m.sph = (const DevSphere*)(base + (L.sph - L.sph));
-    m.segs = (const DevSegment*)(base + (L.seg - L.sph));
-    m.ops = (const FkOp*)(base + (L.ops - L.sph));
-    m.slot_sph = (const int*)(base + (L.slot - L.sph));
-    e->d_pad_pos = (double*)(base + (L.pad - L.sph));
-    m.pad_pos = e->d_pad_pos; m.sdf = e->d_sdf;
+    point_model_into_image(e, m, e->d_img);
+    e->d_pad_pos = (double*)m.pad_pos;
+    m.sdf = e->d_sdf;
     return 0;
 }
 
@@ -775,10 +882,7 @@ int finish_model(stomp_engine* e, const stomp_engine_desc* d)
     // per rollout), and an eval batch may hold more rows than K_loc + 1
     m.split_cap = std::max(e->K_loc + 2, m.cus / 2 + 1);
     if (int rc = dev_alloc(e, &m.split_cnt, (size_t)m.split_cap)) return rc;
-    if (m.lean && m.nsaves > 0) {   // a [nsaves][12][N] block per rollout workgroup of a launch
-        m.sv_rows = e->K_loc + 1;
-        if (int rc = dev_alloc(e, &m.sv_glob, (size_t)m.sv_rows * m.nsaves * 12 * N)) return rc;
-    }
+    if (int rc = place_saved_frames(e, m, &e->d_sv, &e->sv_cap, nullptr)) return rc;
     {
         const char* env = std::getenv("STOMP_DEBUG_SPLIT_MAX");
         m.split_max = env ? std::atoi(env) : 0;
@@ -850,8 +954,8 @@ extern "C" int stomp_engine_create(const stomp_engine_desc* d, stomp_engine** ou
     if (int rc = setup_tables(e, d, tab)) return rc;
     if (int rc = alloc_buffers(e, d, tab)) return rc;
     if (int rc = build_terms(e, d, tab)) return rc;
-    if (int rc = choose_layout(e, d, tab)) return rc;
-    if (int rc = upload_lds_image(e, tab)) return rc;
+    if (int rc = choose_layout(e, e, e->mt, e->model)) return rc;
+    if (int rc = upload_lds_image(e)) return rc;
     if (int rc = place_field(e, d)) return rc;
     if (int rc = finish_model(e, d)) return rc;
     if (int rc = pad_fk(e)) return rc;

@@ -62,6 +62,12 @@ struct stomp_group {
     // no group) gets its entry refreshed before the next launch that reads the list
     unsigned char *h_rt = nullptr, *d_rt = nullptr;
     std::vector<int> pad_flags;
+    // stomp_group_retarget_requests: one call's staging, held with a capacity; the model epoch of
+    // every engine the group's lists were made from (an engine whose model was replaced on its own
+    // since then leaves them stale: check_epochs)
+    unsigned char *h_rq = nullptr, *d_rq = nullptr;
+    size_t rq_cap = 0;
+    std::vector<long long> epochs;
     std::string err;
 };
 
@@ -371,6 +377,21 @@ int sync_model_flags(stomp_group* g)
     return 0;
 }
 
+// An engine whose model stomp_engine_retarget_request replaced on its own: the group's lists
+// (d_models, d_tmodels, nterms, terms_lds) still describe the old one.  Refused before anything is
+// touched; stomp_group_retarget_requests brings the group back in step.
+int check_epochs(stomp_group* g)
+{
+    for (size_t p = 0; p < g->e.size(); ++p)
+        if (g->epochs[p] != g->e[p]->model_epoch) {
+            char buf[200];
+            snprintf(buf, sizeof buf, "engine %d of the group changed its model on its own (stomp_engine_retarget_request): "
+                                      "stomp_group_retarget_requests brings the group back in step", (int)p);
+            return gfail(g, STOMP_E_INVALID, buf);
+        }
+    return 0;
+}
+
 // what stomp_group_create_flags tells an engine the group does not take, by what the group accepts
 const char* refusal_text(bool state_terms, bool cumulative)
 {
@@ -589,8 +610,8 @@ void stomp_group_destroy(stomp_group* g)
         hipEventSynchronize(g->staged);
         hipEventDestroy(g->staged);
     }
-    free_device(g->d_models, g->d_tmodels, g->d_args, g->d_opt, g->d_mirror, g->d_track_all, g->d_rt);
-    free_pinned(g->h_args, g->h_opt, g->h_mirror, g->h_rt);
+    free_device(g->d_models, g->d_tmodels, g->d_args, g->d_opt, g->d_mirror, g->d_track_all, g->d_rt, g->d_rq);
+    free_pinned(g->h_args, g->h_opt, g->h_mirror, g->h_rt, g->h_rq);
     for (hipEvent_t ev : g->opt_ev)
         if (ev) hipEventDestroy(ev);
     delete g;
@@ -670,6 +691,7 @@ int stomp_group_create_flags(stomp_engine* const* engines, int32_t n, uint32_t a
     std::vector<DevModel> ms(n);
     for (int p = 0; p < n; ++p) ms[p] = engines[p]->model;
     for (int p = 0; p < n; ++p) g->pad_flags.push_back(engines[p]->pad_collision);
+    for (int p = 0; p < n; ++p) g->epochs.push_back(engines[p]->model_epoch);
     if (hipMalloc(&g->d_models, sizeof(DevModel) * n) != hipSuccess ||
         hipMemcpy(g->d_models, ms.data(), sizeof(DevModel) * n, hipMemcpyHostToDevice) != hipSuccess ||
         hipEventCreateWithFlags(&g->staged, hipEventDisableTiming) != hipSuccess) {
@@ -714,6 +736,7 @@ int stomp_group_retarget(stomp_group* g, const double* starts, const double* goa
     if (!g) return gfail(nullptr, STOMP_E_INVALID, "null group");
     if (!starts || !goals || !seeds) return gfail(nullptr, STOMP_E_INVALID, "retarget: null starts, goals or seeds");
     const int P = (int)g->e.size();
+    if (int rc = check_epochs(g)) return rc;
     if (int rc = retarget_validate(g->e.data(), P, starts, goals)) return gfail(g, rc, std::string(g_last_error).c_str());
     DeviceGuard dg(g->device);
     if (!g->d_rt) {
@@ -730,12 +753,70 @@ int stomp_group_retarget(stomp_group* g, const double* starts, const double* goa
     return 0;
 }
 
+int stomp_group_retarget_requests(stomp_group* g, const stomp_request* rs)
+{
+    // all of this before any engine or device is touched
+    if (!g) return gfail(nullptr, STOMP_E_INVALID, "null group");
+    if (!rs) return gfail(nullptr, STOMP_E_INVALID, "retarget: null requests");
+    const int P = (int)g->e.size();
+    for (int p = 0; p < P; ++p) {
+        if (rs[p].struct_size != (int32_t)sizeof(stomp_request))
+            return gfail(g, STOMP_E_INVALID, "retarget: struct_size is not sizeof(stomp_request)");
+        if (!rs[p].start || !rs[p].goal) return gfail(g, STOMP_E_INVALID, "retarget: null start or goal");
+    }
+    // (the plans ask the rollout kernels' attributes of the current device: the group's)
+    DeviceGuard dg(g->device);
+    std::vector<ModelPlan> plans(P);
+    for (int p = 0; p < P; ++p)
+        if (int rc = request_plan(g->e[p], &rs[p], p, plans[p])) return gfail(g, rc, std::string(g_last_error).c_str());
+    // stomp_group_create_flags' shape rule and accept rule on the planned models
+    const DevModel& m0 = plans[0].m;
+    const size_t lds0 = rollout_lds_bytes(m0, m0.pad_lds);
+    int nterms = 0;
+    size_t terms_lds = 0;
+    for (int p = 0; p < P; ++p) {
+        const DevModel& m = plans[p].m;
+        if (m.S != m0.S || rollout_lds_bytes(m, m.pad_lds) != lds0 || m.pad_lds != m0.pad_lds || m.lean != m0.lean)
+            return gfail(g, STOMP_E_INVALID,
+                         "the engines of a group have one shape (J, N, K, K_r, spheres, model, field layout)");
+        if (plans[p].terms_on && !g->state_terms)
+            return gfail(g, STOMP_E_UNSUPPORTED, refusal_text(false, g->ncum > 0));
+        if (!plans[p].terms_on) continue;
+        ++nterms;
+        terms_lds = std::max(terms_lds, terms_lds_bytes(plans[p].terms));
+    }
+    const size_t bytes = request_stage_bytes(g->e.data(), P, plans);
+    if (bytes > g->rq_cap) {
+        // (no launch reads the old staging: every call that used it waited for the stream)
+        const size_t cap = std::max(bytes, 2 * g->rq_cap);
+        free_pinned(g->h_rq);
+        free_device(g->d_rq);
+        g->rq_cap = 0;
+        if (hipHostMalloc((void**)&g->h_rq, cap) != hipSuccess || hipMalloc((void**)&g->d_rq, cap) != hipSuccess)
+            return gfail(g, STOMP_E_DEVICE, "group retarget allocation failed");
+        g->rq_cap = cap;
+        for (stomp_engine* e : g->e) e->rq_allocs += 2;
+    }
+    // one upload, one launch and one read-back for the whole group; the launch rewrites the
+    // group's own model entries, so nothing staged from the old models outlives this call
+    if (int rc = request_engines(g->e.data(), P, rs, plans, g->h_rq, g->d_rq, g->d_models, g->d_tmodels))
+        return gfail(g, rc, std::string(g_last_error).c_str());
+    g->nterms = nterms;
+    g->terms_lds = terms_lds;
+    for (int p = 0; p < P; ++p) {
+        g->pad_flags[p] = g->e[p]->pad_collision;
+        g->epochs[p] = g->e[p]->model_epoch;
+    }
+    return 0;
+}
+
 const char* stomp_group_last_error(const stomp_group* g) { return g ? g->err.c_str() : g_last_error.c_str(); }
 
 int stomp_group_run(stomp_group* g, int32_t first, int32_t count)
 {
     if (!g) return gfail(nullptr, STOMP_E_INVALID, "null group");
     if (count <= 0) return 0;
+    if (int rc = check_epochs(g)) return rc;
     DeviceGuard dg(g->device);
     const int P = (int)g->e.size();
     stomp_engine* e0 = g->e[0];
@@ -775,6 +856,7 @@ int stomp_group_run(stomp_group* g, int32_t first, int32_t count)
 int stomp_group_synchronize(stomp_group* g)
 {
     if (!g) return gfail(nullptr, STOMP_E_INVALID, "null group");
+    if (int rc = check_epochs(g)) return rc;
     DeviceGuard dg(g->device);
     const int P = (int)g->e.size();
     if (int rc = sync_model_flags(g)) return rc;
@@ -816,6 +898,7 @@ int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_i
 {
     if (!g) return gfail(nullptr, STOMP_E_INVALID, "null group");
     if (!stats) return gfail(g, STOMP_E_INVALID, "null stats");
+    if (int rc = check_epochs(g)) return rc;
     const int P = (int)g->e.size();
     stomp_engine* e0 = g->e[0];
     int maxcap = 0;

@@ -7,7 +7,9 @@
 //   engine_exchange.cpp  the in-process group, the RCCL path, the collectives, calibration
 //   engine_group.cpp     stomp_group: one launcher of a grouped step (launch_step) and one arena of
 //                        staged arguments behind run, synchronize and optimize
-//   engine_retarget.cpp  stomp_engine_retarget and the part of it stomp_group_retarget shares
+//   engine_retarget.cpp  stomp_engine_retarget and the part of it stomp_group_retarget shares;
+//                        stomp_engine_retarget_request (a request's collision points and path
+//                        constraints too) and the part stomp_group_retarget_requests shares
 //   sdf_build.cpp        the distance-field builders (does not include this header)
 //   scene.cpp            stomp_scene: the field kept in a static and a dynamic layer (uses fail and
 //                        DeviceGuard only)
@@ -17,6 +19,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -82,6 +86,16 @@ struct LocalGroup {
     }
 };
 
+// The host tables that depend on the collision points: the FK program, each sphere's published
+// frame slot, each slot's first sphere, the spheres as the kernels hold them.  Made by
+// plan_model_tables at creation and again, on a live engine, by stomp_engine_retarget_request.
+struct ModelTables {
+    int S = 0, nslots = 0;
+    std::vector<FkOp> ops;
+    std::vector<int> sphere_slot, slot_sph;
+    std::vector<DevSphere> sph;
+};
+
 }  // namespace stomp
 
 struct stomp_engine {
@@ -118,10 +132,29 @@ struct stomp_engine {
     const int* d_stop = nullptr;
     double* d_opt_costs = nullptr;    // [max_iterations] last_trajectory_cost_ per iteration
     stomp::DevTrack* h_track = nullptr;   // pinned read-back slots
-    bool tracking = false;            // inside stomp_engine_optimize: k_track after each noiseless rollout
-    std::vector<stomp::FkOp> ops;
-    std::vector<int> sphere_slot;   // published frame slot of each sphere's segment
-    int nslots = 0;
+    // inside stomp_engine_optimize: k_track after each noiseless rollout.  Atomic: the retarget
+    // calls' "inside its optimize loop" refusal may come from another host thread than the loop's
+    std::atomic<bool> tracking{false};
+    stomp::ModelTables mt;          // the FK program and the sphere tables of the current collision points
+    // what the model stages read again on a live engine (stomp_engine_retarget_request): the
+    // kinematic tree and the joint limits as the LDS image holds them
+    std::vector<stomp::DevSegment> h_segs;
+    std::vector<int> h_has_lim;
+    std::vector<double> h_jmin, h_jmax;
+    // held with a capacity, reallocated only when a request needs more than every earlier one: the
+    // LDS image (8-byte words), the path constraints' table (entries), the lean layout's saved-frame
+    // blocks (doubles), one call's staging (pinned and device, bytes)
+    unsigned long long* d_img = nullptr;
+    size_t img_cap = 0;
+    stomp::OcDev* d_oc = nullptr;
+    size_t oc_cap = 0;
+    double* d_sv = nullptr;
+    size_t sv_cap = 0;
+    unsigned char *h_rq = nullptr, *d_rq = nullptr;
+    size_t rq_cap = 0;
+    // model changes so far (a group compares it with the epoch it last saw), and the device or
+    // pinned allocations made inside retarget-request calls
+    long long model_epoch = 0, rq_allocs = 0;
     std::vector<void*> allocs;
     double *d_theta = nullptr, *d_LT = nullptr, *d_MT = nullptr, *d_QT = nullptr;
     double *d_params = nullptr, *d_noise = nullptr, *d_control = nullptr, *d_prob = nullptr, *d_state = nullptr;
@@ -253,6 +286,68 @@ int retarget_validate(stomp_engine* const* es, int P, const double* starts, cons
 int retarget_engines(stomp_engine* const* es, int P, const double* starts, const double* goals,
                      const uint64_t* seeds, unsigned char* h, unsigned char* d, DevModel* d_models);
 
+// the host side of a retarget once its launch has run: the new vectors, seed (null: kept) and
+// padding-collision flag, every piece of iteration state dropped
+void retarget_host_state(stomp_engine* e, const double* start, const double* goal, const uint64_t* seed, int flag);
+
+// A request's model for one engine, planned on the host before anything is touched: the tables
+// and the layout of the new collision points (spheres), the new path constraints (constraints),
+// the model and the terms model the engine will hold (their device pointers are set at the commit).
+// The device buffers a commit made for one engine and the ones they replace.  Until the call's
+// stream wait has succeeded the engine knows neither: a failed call frees `fresh` and the engine is
+// as it was; a finished one hands `fresh` to the engine and frees `retired` (live_alloc_*).
+struct LiveAlloc {
+    std::vector<void*> fresh, retired;
+};
+struct ModelPlan {
+    bool spheres = false, constraints = false;   // which of the two the request replaces
+    ModelTables mt;
+    DevModel m{};
+    std::vector<OcDev> oc;
+    TermsModel terms{};
+    bool terms_on = false;
+    std::vector<unsigned char> img;   // the image's tables (build_model_image)
+    // the commit's view of the buffers the engine holds with a capacity (the engine's own until one
+    // has to grow), swapped into the engine after the stream wait
+    unsigned long long* d_img = nullptr;
+    size_t img_cap = 0;
+    OcDev* d_oc = nullptr;
+    size_t oc_cap = 0;
+    double* d_sv = nullptr;
+    size_t sv_cap = 0;
+    double* d_terms_traj = nullptr;
+    LiveAlloc live;
+};
+// everything stomp_engine_retarget_request / stomp_group_retarget_requests refuse about request r
+// for engine e before an engine or a device is touched, then its plan (p: the engine's index in
+// the messages)
+int request_plan(const stomp_engine* e, const stomp_request* r, int p, ModelPlan& plan);
+// the staging of one call for these plans (bytes): [P] RequestArgs, [P][2][J] vectors, each
+// engine's image tables and constraint table, [P] flags
+size_t request_stage_bytes(stomp_engine* const* es, int P, const std::vector<ModelPlan>& plans);
+// the commit: the P engines (one shape, one stream, validated and planned) onto their requests in
+// one upload, one launch and one read-back of the P flags; h / d: staging of request_stage_bytes,
+// free for this call; d_models / d_tmodels: a group's lists, whose entries the launch also
+// rewrites, or null
+int request_engines(stomp_engine* const* es, int P, const stomp_request* rs, std::vector<ModelPlan>& plans,
+                    unsigned char* h, unsigned char* d, DevModel* d_models, TermsModel* d_tmodels);
+
+// ---- engine_create.cpp: the stages that depend on the collision points and the path
+// constraints, shared by creation and stomp_engine_retarget_request (err: where a refusal's message
+// goes -- the engine under construction, or null on a live engine, which stays as it was)
+int validate_spheres(const stomp_sphere* spheres, int n, int num_segments, double resolution);
+int validate_constraints(const stomp_orientation_constraint* oc, int n, int num_segments);
+int plan_model_tables(stomp_engine* err, const stomp_engine* e, const stomp_sphere* spheres, int S, ModelTables& t);
+int plan_constraints(stomp_engine* err, const stomp_engine* e, const stomp_orientation_constraint* ocs, int n,
+                     std::vector<OcDev>& oc);
+int plan_terms(stomp_engine* err, const stomp_engine* e, TermsModel& t, bool terms_on);
+int choose_layout(stomp_engine* err, const stomp_engine* e, const ModelTables& t, DevModel& m);
+RolloutLds model_image_layout(const stomp_engine* e, const DevModel& m);
+size_t model_image_bytes(const stomp_engine* e, const DevModel& m);
+std::vector<unsigned char> build_model_image(const stomp_engine* e, const ModelTables& t, const DevModel& m);
+void point_model_into_image(const stomp_engine* e, DevModel& m, unsigned long long* d_img);
+int place_saved_frames(stomp_engine* e, DevModel& m, double** d_sv, size_t* sv_cap, LiveAlloc* live);
+
 // ---- engine_exchange.cpp
 extern const bool kWithRccl;
 bool is_local_comm_id(const void* comm_id);
@@ -312,6 +407,56 @@ int upload(stomp_engine* e, T** p, const T* src, size_t n)
     if (rc) return rc;
     if (n) HIP_TRY(e, hipMemcpyAsync(*p, src, n * sizeof(T), hipMemcpyHostToDevice, e->stream));
     return 0;
+}
+
+// A buffer the engine holds with a capacity (in elements): reallocated only when `need` exceeds it.
+// live == null (creation): exactly `need`, the engine's own allocation (p, cap: the engine's
+// fields).  On a live engine p and cap are the commit's copies of those fields: the capacity at
+// least doubles, the new buffer goes to live->fresh and the old one -- launches already enqueued
+// may read it -- to live->retired; the engine itself is not touched.
+template <class T>
+int grow_buffer(stomp_engine* e, T** p, size_t* cap, size_t need, LiveAlloc* live)
+{
+    if (need <= *cap) return 0;
+    const size_t n = live ? std::max(need, 2 * *cap) : need;
+    T* q = nullptr;
+    if (!live) {
+        if (int rc = dev_alloc(e, &q, n)) return rc;
+    } else {
+        if (hipMalloc((void**)&q, n * sizeof(T)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(nullptr, STOMP_E_DEVICE, "hipMalloc(%zu bytes) failed", n * sizeof(T));
+        }
+        hipMemsetAsync(q, 0, n * sizeof(T), e->stream);
+        live->fresh.push_back(q);
+        if (*p) live->retired.push_back(*p);
+    }
+    *p = q;
+    *cap = n;
+    return 0;
+}
+
+// a failed call: what it allocated is given back, the engine was never told of it
+inline void live_alloc_abort(LiveAlloc& live)
+{
+    for (void* q : live.fresh) hipFree(q);
+    live.fresh.clear();
+    live.retired.clear();
+}
+
+// a finished call, after the engine's stream has passed every launch that could read the retired
+// buffers: the new ones are the engine's (counted in rq_allocs), the replaced ones are freed
+inline void live_alloc_commit(stomp_engine* e, LiveAlloc& live)
+{
+    for (void* q : live.fresh) e->allocs.push_back(q);
+    e->rq_allocs += (long long)live.fresh.size();
+    for (void* q : live.retired) {
+        auto it = std::find(e->allocs.begin(), e->allocs.end(), q);
+        if (it != e->allocs.end()) e->allocs.erase(it);
+        hipFree(q);
+    }
+    live.fresh.clear();
+    live.retired.clear();
 }
 
 inline hipEvent_t get_event(stomp_engine* e)

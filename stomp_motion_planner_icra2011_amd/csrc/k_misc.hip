@@ -46,29 +46,37 @@ const char* lds_opt_in_error()
 
 // padding-point sphere positions: iteration-0 full FK of start (rows 0..5) and goal (rows 6..11)
 // (stomp_optimizer.cpp:626-630 with JntToCartFull; padding rows of the group trajectory hold
-// start/goal, stomp_trajectory.cpp:94-107).  pad_fk_side: one side (0: start, 1: goal) of the pose
-// q; returns whether a sphere collides
-__device__ __forceinline__ bool pad_fk_side(const DevModel& m, const double* q, int side, double* pad_pos)
+// start/goal, stomp_trajectory.cpp:94-107).  pad_fk_side_tab: one side (0: start, 1: goal) of the
+// pose q, with the model's three tables given apart from the model (for a caller whose tables are
+// not yet where the model's pointers say); returns whether a sphere collides
+__device__ __forceinline__ bool pad_fk_side_tab(const DevModel& m, const FkOp* ops, const DevSegment* segs,
+                                                const DevSphere* sph, const double* q, int side, double* pad_pos)
 {
     Frame C, S0, S1;
     bool col = false;
     for (int op = 0; op < m.nops; ++op) {
-        const FkOp o = m.ops[op];
+        const FkOp o = ops[op];
         if (o.seg >= 0) {
-            const DevSegment& sg = m.segs[o.seg];
+            const DevSegment& sg = segs[o.seg];
             double st = 0.0, ct = 1.0;
             if (sg.q_index >= 0) det_sincos(q[sg.q_index], &st, &ct);
             fk_op(sg, o.base, o.save, st, ct, C, S0, S1);
         }
         for (int s = o.sph_begin; s < o.sph_end; ++s) {
             double p[3];
-            apply(C.R, C.p, m.sph[s].pos, p);
-            if ((int)sdf_d2(m, p) < m.sph[s].col_lim) col = true;   // distance <= radius
+            apply(C.R, C.p, sph[s].pos, p);
+            if ((int)sdf_d2(m, p) < sph[s].col_lim) col = true;   // distance <= radius
             for (int row = 0; row < 6; ++row)
                 for (int c = 0; c < 3; ++c) pad_pos[((size_t)(side * 6 + row) * m.S + s) * 3 + c] = p[c];
         }
     }
     return col;
+}
+
+// pad_fk_side: the same on the model's own tables
+__device__ __forceinline__ bool pad_fk_side(const DevModel& m, const double* q, int side, double* pad_pos)
+{
+    return pad_fk_side_tab(m, m.ops, m.segs, m.sph, q, side, pad_pos);
 }
 
 __global__ void k_pad_fk(DevModel m, const double* start, const double* goal, double* pad_pos, int* pad_cf)
@@ -78,30 +86,13 @@ __global__ void k_pad_fk(DevModel m, const double* start, const double* goal, do
     if (pad_fk_side(m, side ? goal : start, side, pad_pos)) atomicOr(pad_cf, 1);
 }
 
-// stomp_engine_retarget / stomp_group_retarget (RetargetArgs): grid (J + 1, engines), N <= 256
-// lanes per workgroup.  Workgroup d < J makes joint d's row of theta_0 as compute_setup does
-// (setup.cpp, setToMinControlCost): lin[c] by lane c through LDS, both sums i-ascending, then
-// theta[d][i] by lane i, k-ascending, reading Rinv[i][k] itself (RinvT[k][i]: R^-1 is not bitwise
-// symmetric).  Workgroup J is the padding FK on the new vectors in the staging buffer: the other
-// workgroups of the launch are writing start / goal meanwhile.
-__global__ __launch_bounds__(256) void k_retarget(const RetargetArgs* __restrict__ as, int J, int N)
+// joint d's row of theta_0 (also the last and the best trajectory) and its start / goal entries,
+// by the 256 lanes of one workgroup, as compute_setup does (setup.cpp, setToMinControlCost): lin[c]
+// by lane c through LDS (lin: 256 doubles), both sums i-ascending, then theta[d][i] by lane i,
+// k-ascending, reading Rinv[i][k] itself (RinvT[k][i]: R^-1 is not bitwise symmetric)
+__device__ __forceinline__ void retarget_theta_row(const RetargetArgs& a, int d, int J, int N, double* lin)
 {
-    const RetargetArgs& a = as[blockIdx.y];
-    __shared__ double lin[256];
-    __shared__ int col[2];
-    if ((int)blockIdx.x == J) {
-        const int side = threadIdx.x;
-        if (side < 2) col[side] = pad_fk_side(a.model, a.stage + (size_t)side * J, side, a.pad_pos) ? 1 : 0;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const int f = col[0] | col[1];
-            *a.pad_cf = f;
-            if (a.model_flag) *a.model_flag = f;
-            *a.flag_out = f;
-        }
-        return;
-    }
-    const int d = blockIdx.x, c = threadIdx.x;
+    const int c = threadIdx.x;
     const double sd = a.stage[d], gd = a.stage[J + d];
     if (c < N) {
         double x = 0.0;
@@ -125,9 +116,93 @@ __global__ __launch_bounds__(256) void k_retarget(const RetargetArgs* __restrict
     }
 }
 
+// the padding-collision flag of both sides, stored where the engine, a group's list and the call's
+// read-back keep it (col: the two sides' results in LDS, written before the barrier)
+__device__ __forceinline__ void retarget_store_flags(const RetargetArgs& a, const int* col)
+{
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int f = col[0] | col[1];
+        *a.pad_cf = f;
+        if (a.model_flag) *a.model_flag = f;
+        *a.flag_out = f;
+    }
+}
+
+// stomp_engine_retarget / stomp_group_retarget (RetargetArgs): grid (J + 1, engines), N <= 256
+// lanes per workgroup.  Workgroup d < J makes joint d's row of theta_0 (retarget_theta_row).
+// Workgroup J is the padding FK on the new vectors in the staging buffer: the other workgroups of
+// the launch are writing start / goal meanwhile.
+__global__ __launch_bounds__(256) void k_retarget(const RetargetArgs* __restrict__ as, int J, int N)
+{
+    const RetargetArgs& a = as[blockIdx.y];
+    __shared__ double lin[256];
+    __shared__ int col[2];
+    if ((int)blockIdx.x == J) {
+        const int side = threadIdx.x;
+        if (side < 2) col[side] = pad_fk_side(a.model, a.stage + (size_t)side * J, side, a.pad_pos) ? 1 : 0;
+        retarget_store_flags(a, col);
+        return;
+    }
+    retarget_theta_row(a, blockIdx.x, J, N, lin);
+}
+
 void launch_retarget(const RetargetArgs* as, int engines, int J, int N, hipStream_t s)
 {
     hipLaunchKernelGGL(k_retarget, dim3(J + 1, engines), dim3(256), 0, s, as, J, N);
+}
+
+// stomp_engine_retarget_request / stomp_group_retarget_requests (RequestArgs, kernels.h): grid
+// (J + 2, engines).  Nothing in this launch reads the engine's image: a CU's vector L1 and the
+// scalar cache are not refreshed by the stores workgroup J + 1 makes from another CU.
+__global__ __launch_bounds__(256) void k_retarget_model(const RequestArgs* __restrict__ as, int J, int N)
+{
+    const RequestArgs& r = as[blockIdx.y];
+    const RetargetArgs& a = r.rt;
+    __shared__ double lin[256];
+    __shared__ int col[2];
+    if ((int)blockIdx.x == J) {
+        // the new model's tables where the staging copy holds them: at the offsets they will have
+        // in the engine's image
+        const unsigned char* img = (const unsigned char*)a.model.img;
+        const unsigned char* st = (const unsigned char*)r.stage_img;
+        const FkOp* ops = (const FkOp*)(st + ((const unsigned char*)a.model.ops - img));
+        const DevSegment* segs = (const DevSegment*)(st + ((const unsigned char*)a.model.segs - img));
+        const DevSphere* sph = (const DevSphere*)(st + ((const unsigned char*)a.model.sph - img));
+        const int side = threadIdx.x;
+        if (side < 2)
+            col[side] = pad_fk_side_tab(a.model, ops, segs, sph, a.stage + (size_t)side * J, side, a.pad_pos) ? 1 : 0;
+        retarget_store_flags(a, col);
+        return;
+    }
+    if ((int)blockIdx.x == J + 1) {
+        for (int i = threadIdx.x; i < r.img_words; i += 256) r.img_out[i] = r.stage_img[i];
+        for (int i = threadIdx.x; i < r.oc_words; i += 256) r.oc_out[i] = r.stage_oc[i];
+        if (threadIdx.x == 0) *r.cs = 1;
+        if (r.model_out) {
+            const unsigned long long* src = (const unsigned long long*)&a.model;
+            unsigned long long* dst = (unsigned long long*)r.model_out;
+            const int flag_word = (int)(offsetof(DevModel, pad_collision) / 8);
+            for (int i = threadIdx.x; i < (int)(sizeof(DevModel) / 8); i += 256)
+                if (i != flag_word) dst[i] = src[i];
+        }
+        if (r.terms_out) {
+            const unsigned long long* src = (const unsigned long long*)&r.terms;
+            unsigned long long* dst = (unsigned long long*)r.terms_out;
+            for (int i = threadIdx.x; i < (int)(sizeof(TermsModel) / 8); i += 256) dst[i] = src[i];
+        }
+        return;
+    }
+    retarget_theta_row(a, blockIdx.x, J, N, lin);
+}
+
+static_assert(sizeof(DevModel) % 8 == 0 && sizeof(TermsModel) % 8 == 0 && offsetof(DevModel, pad_collision) % 8 == 0 &&
+                  offsetof(DevModel, QT) == offsetof(DevModel, pad_collision) + 8,
+              "k_retarget_model copies the model entries by 8-byte words and skips pad_collision's");
+
+void launch_retarget_model(const RequestArgs* as, int engines, int J, int N, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_retarget_model, dim3(J + 2, engines), dim3(256), 0, s, as, J, N);
 }
 
 __global__ void k_gather_max(const double* g, int world, int n, double* out)

@@ -491,6 +491,30 @@ struct RetargetArgs {
     int* flag_out;              // the call's read-back slot of this engine
 };
 void launch_retarget(const RetargetArgs* as, int engines, int J, int N, hipStream_t s);
+// A live engine put onto a request that also replaces its collision points and / or its path
+// constraints (stomp_engine_retarget_request / stomp_group_retarget_requests).  Grid (J + 2,
+// engines): workgroups d < J make theta_0 as k_retarget's; workgroup J runs the padding FK of the
+// NEW model, reading its segment / sphere / FK-program tables from the call's staging copy of the
+// image (stage_img) -- never from the engine's image, which workgroup J + 1 is writing meanwhile --
+// and writes the padding positions (rt.pad_pos, in the engine's image) and the flags; workgroup
+// J + 1 copies the staged image tables [0, img_words) and the staged constraint table into the
+// engine's buffers, raises the constraints-satisfied flag of the noiseless rollout to creation's 1
+// and, for a group, rewrites the engine's entries of the group's model lists (every word but
+// DevModel::pad_collision's, which is workgroup J's).
+struct RequestArgs {
+    RetargetArgs rt;            // rt.model: the new model (its table pointers into the engine's image)
+    const unsigned long long* stage_img;   // the image's tables in the call's staging buffer
+    unsigned long long* img_out;           // the engine's image
+    int img_words;              // 8-byte words of the tables (everything before the padding positions)
+    int oc_words;               // 8-byte words of the constraint table (0: none)
+    const unsigned long long* stage_oc;
+    unsigned long long* oc_out; // the engine's constraint table (TermsModel::oc)
+    uint8_t* cs;                // the noiseless rollout's constraints-satisfied flag
+    TermsModel terms;           // the new terms model
+    DevModel* model_out;        // the engine's entry of a group's DevModel list, or null
+    TermsModel* terms_out;      // of its TermsModel list, or null
+};
+void launch_retarget_model(const RequestArgs* as, int engines, int J, int N, hipStream_t s);
 // src_*: the previous iteration's rows (ranked, copied from); params / noise / state: this
 // iteration's rows K_gen.. (written).  The two row sets must be distinct buffers (the copy has no
 // staging pass); returns -1 without launching when they alias, -2 when one candidate's cost rows

@@ -312,6 +312,49 @@ static void mesh_box_sphere(const double* V, int nv, double* centre, double* rad
 
 namespace stomp {
 
+// btMatrix3x3::setRotation (bodies::Body::setPose) of the quaternion (x, y, z, w)
+void body_basis(const double* q, double* B)
+{
+    const double qx = q[0], qy = q[1], qz = q[2], qw = q[3];
+    const double dq = qx * qx + qy * qy + qz * qz + qw * qw;
+    const double sc = 2.0 / dq;
+    const double xs = qx * sc, ys = qy * sc, zs = qz * sc;
+    const double wx = qw * xs, wy = qw * ys, wz = qw * zs;
+    const double xx = qx * xs, xy = qx * ys, xz = qx * zs;
+    const double yy = qy * ys, yz = qy * zs, zz = qz * zs;
+    const double M[9] = {1.0 - (yy + zz), xy - wz, xz + wy, xy + wz, 1.0 - (xx + zz), yz - wx,
+                         xz - wy, yz + wx, 1.0 - (xx + yy)};
+    std::memcpy(B, M, sizeof M);
+}
+
+// bodies::*::computeBoundingSphere of a STOMP_BODY_* shape posed with basis B at its position
+// (padding folded into dims; a mesh's: the sphere around its vertices' bounding-box centre, grown
+// by the padding).  Returns false for any other type, or a mesh without its vertices.
+bool body_bounding_sphere(const stomp_shape& sh, const double* B, double* centre, double* radius)
+{
+    const double* d = sh.dims;
+    for (int a = 0; a < 3; ++a) centre[a] = sh.position[a];
+    if (sh.type == STOMP_BODY_SPHERE) {
+        *radius = d[0];
+    } else if (sh.type == STOMP_BODY_BOX) {
+        const double a = d[0] / 2.0, b = d[1] / 2.0, c = d[2] / 2.0;
+        *radius = std::sqrt(a * a + b * b + c * c);
+    } else if (sh.type == STOMP_BODY_CYLINDER) {
+        const double h = d[1] / 2.0;
+        *radius = std::sqrt(d[0] * d[0] + h * h);
+    } else if (sh.type == STOMP_BODY_MESH) {
+        if (!sh.vertices || sh.num_vertices < 1) return false;
+        double bc[3], rb;
+        mesh_box_sphere(sh.vertices, sh.num_vertices, bc, &rb);
+        for (int a = 0; a < 3; ++a)
+            centre[a] = B[3 * a] * bc[0] + B[3 * a + 1] * bc[1] + B[3 * a + 2] * bc[2] + sh.position[a];
+        *radius = rb + d[0];
+    } else {
+        return false;
+    }
+    return true;
+}
+
 // StompCollisionSpace::setStartState's per-object lattices (stomp_collision_space.cpp:199-297,
 // 564-650): the environment objects' coordinate lists by the reference's own running-sum loops,
 // the robot bodies' and meshes' bounding-sphere lattices, the meshes' hull planes
@@ -358,28 +401,10 @@ int lattice_setup(const stomp_shape* shapes, int n_shapes, double res, LatticeSe
             }
             if (npts > kMaxLattice) return fail(nullptr, STOMP_E_INVALID, "object %d: lattice too large", s);
         } else if (sh.type >= STOMP_BODY_SPHERE && sh.type <= STOMP_BODY_MESH) {
-            // btMatrix3x3::setRotation (bodies::Body::setPose)
-            const double dq = qx * qx + qy * qy + qz * qz + qw * qw;
-            const double sc = 2.0 / dq;
-            const double xs = qx * sc, ys = qy * sc, zs = qz * sc;
-            const double wx = qw * xs, wy = qw * ys, wz = qw * zs;
-            const double xx = qx * xs, xy = qx * ys, xz = qx * zs;
-            const double yy = qy * ys, yz = qy * zs, zz = qz * zs;
-            const double B[9] = {1.0 - (yy + zz), xy - wz, xz + wy, xy + wz, 1.0 - (xx + zz), yz - wx,
-                                 xz - wy, yz + wx, 1.0 - (xx + yy)};
+            double B[9];
+            body_basis(sh.orientation, B);
             std::memcpy(j.R, B, sizeof B);
-            const double* d = sh.dims;
-            double r;   // bodies::*::computeBoundingSphere
-            double centre[3] = {sh.position[0], sh.position[1], sh.position[2]};
-            if (sh.type == STOMP_BODY_SPHERE) {
-                r = d[0];
-            } else if (sh.type == STOMP_BODY_BOX) {
-                const double a = d[0] / 2.0, b = d[1] / 2.0, c = d[2] / 2.0;
-                r = std::sqrt(a * a + b * b + c * c);
-            } else if (sh.type == STOMP_BODY_CYLINDER) {
-                const double h = d[1] / 2.0;
-                r = std::sqrt(d[0] * d[0] + h * h);
-            } else {
+            if (sh.type == STOMP_BODY_MESH) {
                 // bodies::ConvexMesh: the convex hull of the vertices as planes, the lattice around
                 // the bounding sphere of the vertices' bounding-box centre
                 if (!sh.vertices || sh.num_vertices < 4)
@@ -389,15 +414,14 @@ int lattice_setup(const stomp_shape* shapes, int n_shapes, double res, LatticeSe
                 if (np < 0) return fail(nullptr, STOMP_E_INVALID, "mesh %d: the vertices span no volume", s);
                 j.nplanes = np;
                 j.off[0] = first;   // plane offset, resolved to a device pointer below
-                double bc[3], rb;
-                mesh_box_sphere(sh.vertices, sh.num_vertices, bc, &rb);
+            }
+            double r, centre[3];   // bodies::*::computeBoundingSphere
+            body_bounding_sphere(sh, B, centre, &r);
+            if (sh.type == STOMP_BODY_MESH)
                 for (int a = 0; a < 3; ++a) {
                     j.org[a] = sh.position[a];
-                    centre[a] = B[3 * a] * bc[0] + B[3 * a + 1] * bc[1] + B[3 * a + 2] * bc[2] + sh.position[a];
                     j.pos[a] = centre[a];
                 }
-                r = rb + d[0];
-            }
             long long npts = 1;
             for (int a = 0; a < 3; ++a) {
                 const double c = centre[a];
@@ -430,6 +454,48 @@ void resolve_mesh_planes(std::vector<SdfLatticeJob>& jobs, const double* d_plane
 }  // namespace stomp
 
 extern "C" {
+
+int stomp_attached_collision_points(const stomp_sphere* base, int32_t n_base, const stomp_attached_body* bodies,
+                                    int32_t n_bodies, double clearance, stomp_sphere* out, int32_t capacity,
+                                    int32_t* n_out)
+{
+    if (!out || !n_out || n_base < 0 || n_bodies < 0 || capacity < 0 || (n_base > 0 && !base) || (n_bodies > 0 && !bodies))
+        return fail(nullptr, STOMP_E_INVALID, "attached collision points: null array or negative count");
+    if (!(clearance > 0.0) || !std::isfinite(clearance))
+        return fail(nullptr, STOMP_E_INVALID, "attached collision points: clearance not finite and positive");
+    std::vector<stomp_sphere> added(n_bodies);
+    for (int i = 0; i < n_bodies; ++i) {
+        const stomp_shape& sh = bodies[i].shape;
+        if (sh.type == STOMP_BODY_MESH && (!sh.vertices || sh.num_vertices < 4))
+            return fail(nullptr, STOMP_E_INVALID, "mesh %d: needs at least 4 vertices", i);
+        double B[9];
+        body_basis(sh.orientation, B);
+        stomp_sphere& sp = added[i];
+        sp.segment = bodies[i].segment;
+        sp.clearance = clearance;
+        if (!body_bounding_sphere(sh, B, sp.pos, &sp.radius))
+            return fail(nullptr, STOMP_E_INVALID, "attached body %d: type %d is no robot body shape", i, sh.type);
+    }
+    const int n = n_base + n_bodies;
+    *n_out = n;
+    if (capacity < n)
+        return fail(nullptr, STOMP_E_INVALID, "attached collision points: %d entries needed, capacity %d", n, capacity);
+    // each new sphere after the last sphere of its segment (the bodies of one segment in input
+    // order); a segment the list has no sphere of: before the first sphere of a later segment
+    std::vector<stomp_sphere> list(base, base + n_base);
+    for (const stomp_sphere& sp : added) {
+        size_t at = list.size();
+        bool found = false;
+        for (size_t k = list.size(); k-- > 0;)
+            if (list[k].segment == sp.segment) { at = k + 1; found = true; break; }
+        if (!found)
+            for (size_t k = 0; k < list.size(); ++k)
+                if (list[k].segment > sp.segment) { at = k; break; }
+        list.insert(list.begin() + at, sp);
+    }
+    if (n) std::memcpy(out, list.data(), sizeof(stomp_sphere) * n);
+    return 0;
+}
 
 int stomp_sdf_build(int32_t nx, int32_t ny, int32_t nz, const double* origin, double res, double max_expansion,
                     const double* boxes, int32_t n_boxes, const double* cyl, int32_t n_cyl, uint16_t* out, void* stream)

@@ -22,6 +22,13 @@ struct LatticeSetup {
 // unknown type, a degenerate mesh, a lattice too large).  Touches no device.
 int lattice_setup(const stomp_shape* shapes, int n_shapes, double res, LatticeSetup& out);
 
+// The bounding-sphere rule lattice_setup and stomp_attached_collision_points share: B, the basis
+// bodies::Body::setPose makes of the quaternion (x, y, z, w); the centre and radius
+// bodies::*::computeBoundingSphere gives a STOMP_BODY_* shape posed with it (false: another type,
+// or a mesh without vertices).
+void body_basis(const double* q, double* B);
+bool body_bounding_sphere(const stomp_shape& sh, const double* B, double* centre, double* radius);
+
 // every mesh job's planes pointed into the device copy of mesh_planes
 void resolve_mesh_planes(std::vector<SdfLatticeJob>& jobs, const double* d_planes);
 

@@ -51,6 +51,17 @@ class stomp_orientation_constraint(C.Structure):
                 ("absolute_yaw_tolerance", C.c_double), ("weight", C.c_double)]
 
 
+class stomp_request(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("start", C.POINTER(C.c_double)), ("goal", C.POINTER(C.c_double)),
+                ("seed", C.c_uint64), ("num_spheres", C.c_int32), ("spheres", C.POINTER(stomp_sphere)),
+                ("num_orientation_constraints", C.c_int32),
+                ("orientation_constraints", C.POINTER(stomp_orientation_constraint))]
+
+
+class stomp_attached_body(C.Structure):
+    _fields_ = [("segment", C.c_int32), ("shape", stomp_shape)]
+
+
 class stomp_engine_desc(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("num_joints", C.c_int32), ("num_time_steps", C.c_int32),
                 ("num_rollouts", C.c_int32), ("num_reused_rollouts", C.c_int32), ("num_segments", C.c_int32),
@@ -107,7 +118,8 @@ EXPORTED = ["stomp_engine_create", "stomp_engine_destroy", "stomp_engine_last_er
             "stomp_engine_shard_info", "stomp_shard_decide", "stomp_engine_source_hash",
             "stomp_engine_refresh_field", "stomp_device_selftest_trig", "stomp_engine_retarget",
             "stomp_group_retarget", "stomp_scene_create", "stomp_scene_set_static", "stomp_scene_set_dynamic",
-            "stomp_scene_window", "stomp_scene_info", "stomp_scene_destroy"]
+            "stomp_scene_window", "stomp_scene_info", "stomp_scene_destroy", "stomp_engine_retarget_request",
+            "stomp_engine_model_info", "stomp_group_retarget_requests", "stomp_attached_collision_points"]
 
 _lib = None
 
@@ -145,6 +157,13 @@ def load_library(path: Optional[str] = None):
     if hasattr(l, "stomp_engine_retarget"):   # (a variant library named by STOMP_ENGINE_LIB may predate them)
         l.stomp_engine_retarget.argtypes = [P, dp, dp, C.c_uint64]
         l.stomp_group_retarget.argtypes = [C.c_void_p, dp, dp, C.POINTER(C.c_uint64)]
+    if hasattr(l, "stomp_engine_retarget_request"):
+        l.stomp_engine_retarget_request.argtypes = [P, C.POINTER(stomp_request)]
+        l.stomp_group_retarget_requests.argtypes = [C.c_void_p, C.POINTER(stomp_request)]
+        l.stomp_engine_model_info.argtypes = [P, C.POINTER(C.c_int64)]
+        l.stomp_attached_collision_points.argtypes = [C.POINTER(stomp_sphere), C.c_int32,
+                                                      C.POINTER(stomp_attached_body), C.c_int32, C.c_double,
+                                                      C.POINTER(stomp_sphere), C.c_int32, C.POINTER(C.c_int32)]
     l.stomp_engine_set_theta.argtypes = [P, dp]
     l.stomp_engine_iterate.argtypes = [P, C.c_int32, C.POINTER(stomp_iter_out)]
     l.stomp_engine_run.argtypes = [P, C.c_int32, C.c_int32]
@@ -342,6 +361,43 @@ class Scene:
         self.close()
 
 
+def sphere_array(spheres):
+    """problem.Sphere list -> stomp_sphere[] (ctypes array; length >= 1)."""
+    return (stomp_sphere * max(len(spheres), 1))(*[
+        stomp_sphere(s.segment, s.radius, s.clearance, (C.c_double * 3)(*s.pos)) for s in spheres])
+
+
+def constraint_array(robot, constraints):
+    """problem.OrientationConstraint list -> stomp_orientation_constraint[] (length >= 1)."""
+    return (stomp_orientation_constraint * max(len(constraints), 1))(*[
+        stomp_orientation_constraint(robot.index(c.link_name), (C.c_double * 4)(*c.orientation),
+                                     0 if c.header_frame else 1, c.absolute_roll_tolerance,
+                                     c.absolute_pitch_tolerance, c.absolute_yaw_tolerance, c.weight)
+        for c in constraints])
+
+
+def attached_collision_points(spheres, bodies, clearance: float):
+    """stomp_attached_collision_points (host only): the collision points of a robot holding attached
+    bodies.  spheres: the robot's own list (problem.Sphere); bodies: (segment, problem.SceneObject)
+    pairs, each a STOMP_BODY_* shape posed in its owner segment's frame.  Every body becomes one
+    sphere at its bounding sphere's centre with that radius and `clearance`, placed after the last
+    sphere of its segment.  Returns the new problem.Sphere list."""
+    from .problem import Sphere
+    l = load_library()
+    base = sphere_array(spheres)
+    shapes = shape_array([o for _, o in bodies])
+    att = (stomp_attached_body * max(len(bodies), 1))()
+    for i, (seg, _) in enumerate(bodies):
+        att[i].segment = int(seg)
+        att[i].shape = shapes[i]
+    cap = len(spheres) + len(bodies)
+    out = (stomp_sphere * max(cap, 1))()
+    n = C.c_int32(0)
+    _check(l.stomp_attached_collision_points(base, len(spheres), att, len(bodies), float(clearance), out, cap,
+                                             C.byref(n)))
+    return [Sphere(out[i].segment, out[i].radius, out[i].clearance, tuple(out[i].pos)) for i in range(n.value)]
+
+
 class Engine:
     """One planning problem on one device: the StompOptimizer / PolicyImprovementLoop pair."""
 
@@ -355,8 +411,7 @@ class Engine:
         self._segs = (stomp_segment * len(p.robot.segments))(*[
             stomp_segment(s.parent, s.q_index, (C.c_double * 9)(*s.rot), (C.c_double * 3)(*s.trans),
                           (C.c_double * 3)(*s.axis)) for s in p.robot.segments])
-        self._sph = (stomp_sphere * max(self.S, 1))(*[
-            stomp_sphere(s.segment, s.radius, s.clearance, (C.c_double * 3)(*s.pos)) for s in p.spheres])
+        self._sph = sphere_array(p.spheres)
         self._joints = (stomp_joint * self.J)(*[
             stomp_joint(int(j.has_limits), j.min, j.max, j.joint_cost) for j in p.robot.joints])
         pr = p.params
@@ -419,11 +474,7 @@ class Engine:
         d.torque_root, d.torque_tip = p.torque_segments()
         d.gravity = (C.c_double * 3)(*p.gravity)
         oc = p.orientation_constraints
-        self._oc = (stomp_orientation_constraint * max(len(oc), 1))(*[
-            stomp_orientation_constraint(p.robot.index(c.link_name), (C.c_double * 4)(*c.orientation),
-                                         0 if c.header_frame else 1, c.absolute_roll_tolerance,
-                                         c.absolute_pitch_tolerance, c.absolute_yaw_tolerance, c.weight)
-            for c in oc])
+        self._oc = constraint_array(p.robot, oc)
         d.num_orientation_constraints = len(oc)
         d.orientation_constraints = self._oc
         self._desc = d
@@ -478,25 +529,65 @@ class Engine:
         """stomp_engine_refresh_field: the caller rebuilt its device field in place."""
         _check(load_library().stomp_engine_refresh_field(self.h), self.h)
 
-    def retarget(self, start, goal, seed: Optional[int] = None):
+    def retarget(self, start, goal, seed: Optional[int] = None, spheres=None, orientation_constraints=None):
         """stomp_engine_retarget: the live engine onto a new start, goal and seed (None keeps the
         engine's seed).  Afterwards it is the engine Engine(problem') would be for problem' =
         dataclasses.replace(problem, start=..., goal=..., seed=...), which self.problem becomes; the
-        iteration state it held is dropped.  A refused call raises and changes nothing."""
+        iteration state it held is dropped.  A refused call raises and changes nothing.
+        spheres (problem.Sphere list) / orientation_constraints (problem.OrientationConstraint list):
+        the request's collision points and path constraints too (stomp_engine_retarget_request);
+        None keeps the engine's, an empty list means none.  problem' then has them replaced as well,
+        and S, pad_positions() and model_info() follow."""
         s = np.ascontiguousarray(start, np.float64).reshape(-1)
         g = np.ascontiguousarray(goal, np.float64).reshape(-1)
         if s.shape != (self.J,) or g.shape != (self.J,):
             raise ValueError(f"start and goal must hold {self.J} values")
         seed = int(self.problem.seed if seed is None else seed)
-        _check(load_library().stomp_engine_retarget(self.h, _dp(s), _dp(g), C.c_uint64(seed)), self.h)
-        self._follow(s, g, seed)
+        if spheres is None and orientation_constraints is None:
+            _check(load_library().stomp_engine_retarget(self.h, _dp(s), _dp(g), C.c_uint64(seed)), self.h)
+            self._follow(s, g, seed)
+            return
+        req, keep = self._request(s, g, seed, spheres, orientation_constraints)
+        # (a refusal writes nothing of the engine, not even its message: the thread's last error has it)
+        _check(load_library().stomp_engine_retarget_request(self.h, C.byref(req)))
+        self._follow(s, g, seed, spheres, orientation_constraints, keep)
 
-    def _follow(self, start, goal, seed):
-        """the Python side of a retarget: the problem attribute and the vectors the descriptor names"""
+    def _request(self, s, g, seed, spheres, constraints):
+        """a stomp_request and the ctypes arrays it points to (kept by the caller until the call
+        returns, and by _follow afterwards: the descriptor copy names them)"""
+        sph = None if spheres is None else sphere_array(spheres)
+        oc = None if constraints is None else constraint_array(self.problem.robot, constraints)
+        req = stomp_request(C.sizeof(stomp_request), _dp(s), _dp(g), seed,
+                            -1 if spheres is None else len(spheres), sph,
+                            -1 if constraints is None else len(constraints), oc)
+        return req, (sph, oc)
+
+    def _follow(self, start, goal, seed, spheres=None, constraints=None, arrays=(None, None)):
+        """the Python side of a retarget: the problem attribute and the arrays the descriptor names"""
         # fresh arrays: the old ones may be the caller's problem's own
         self._start, self._goal = np.array(start, np.float64), np.array(goal, np.float64)
         self._desc.start, self._desc.goal, self._desc.seed = _dp(self._start), _dp(self._goal), seed
-        self.problem = dataclasses.replace(self.problem, start=self._start.copy(), goal=self._goal.copy(), seed=seed)
+        changes = dict(start=self._start.copy(), goal=self._goal.copy(), seed=seed)
+        if spheres is not None:
+            self._sph, self.S = arrays[0], len(spheres)
+            self._desc.num_spheres, self._desc.spheres = self.S, self._sph
+            changes["spheres"] = list(spheres)
+        if constraints is not None:
+            self._oc = arrays[1]
+            self._desc.num_orientation_constraints, self._desc.orientation_constraints = len(constraints), self._oc
+            changes["orientation_constraints"] = list(constraints)
+        self.problem = dataclasses.replace(self.problem, **changes)
+
+    MODEL_INFO = ("S", "nops", "nslots", "nsaves", "sph_chunk", "pad_lds", "lean", "sincos_pre",
+                  "orientation_constraints", "terms_on", "model_changes", "request_allocations")
+
+    def model_info(self) -> dict:
+        """stomp_engine_model_info: the engine's current model (spheres, FK program steps, frame
+        slots, saved frames, longest sphere run, the rollout layout's choices, constraints, terms),
+        the model changes so far and the allocations made inside retarget-request calls."""
+        v = (C.c_int64 * 12)()
+        _check(load_library().stomp_engine_model_info(self.h, v), self.h)
+        return dict(zip(self.MODEL_INFO, [int(x) for x in v]))
 
     def execute(self, params, iteration_member: int = 1):
         prm = np.ascontiguousarray(params, np.float64)
@@ -688,11 +779,14 @@ class EngineGroup:
         self._check(load_library().stomp_group_optimize(self._h, st, _dp(costs), costs_stride))
         return [(st[i], costs[i, : st[i].iterations].copy()) for i in range(n)]
 
-    def retarget(self, starts, goals, seeds=None):
+    def retarget(self, starts, goals, seeds=None, spheres=None, orientation_constraints=None):
         """stomp_group_retarget: every engine onto its new start, goal and seed (rows of starts /
         goals, P x J; seeds None keeps every engine's seed) in one launch.  Each engine is then the
         freshly created engine of its new problem, so engines that left optimize() at different
-        iterations run in lockstep again; every engine's problem attribute follows."""
+        iterations run in lockstep again; every engine's problem attribute follows.
+        spheres / orientation_constraints: per-engine lists of lists (an entry None keeps that
+        engine's): stomp_group_retarget_requests, every engine's collision points and path
+        constraints replaced in the same launch.  The planned engines must again be of one shape."""
         n = len(self.engines)
         J = self.engines[0].J
         s = np.ascontiguousarray(starts, np.float64).reshape(-1)
@@ -704,10 +798,24 @@ class EngineGroup:
         sd = np.array([int(v) for v in seeds], np.uint64)
         if sd.shape != (n,):
             raise ValueError(f"seeds must hold {n} values")
-        self._check(load_library().stomp_group_retarget(self._h, _dp(s), _dp(g),
-                                                        sd.ctypes.data_as(C.POINTER(C.c_uint64))))
+        if spheres is None and orientation_constraints is None:
+            self._check(load_library().stomp_group_retarget(self._h, _dp(s), _dp(g),
+                                                            sd.ctypes.data_as(C.POINTER(C.c_uint64))))
+            for p, e in enumerate(self.engines):
+                e._follow(s[p * J:(p + 1) * J], g[p * J:(p + 1) * J], int(sd[p]))
+            return
+        sph = list(spheres) if spheres is not None else [None] * n
+        ocs = list(orientation_constraints) if orientation_constraints is not None else [None] * n
+        if len(sph) != n or len(ocs) != n:
+            raise ValueError(f"spheres and orientation_constraints must hold {n} lists")
+        rows = [(s[p * J:(p + 1) * J].copy(), g[p * J:(p + 1) * J].copy()) for p in range(n)]
+        reqs, keep = (stomp_request * n)(), []
         for p, e in enumerate(self.engines):
-            e._follow(s[p * J:(p + 1) * J], g[p * J:(p + 1) * J], int(sd[p]))
+            reqs[p], k = e._request(rows[p][0], rows[p][1], int(sd[p]), sph[p], ocs[p])
+            keep.append(k)
+        self._check(load_library().stomp_group_retarget_requests(self._h, reqs))
+        for p, e in enumerate(self.engines):
+            e._follow(rows[p][0], rows[p][1], int(sd[p]), sph[p], ocs[p], keep[p])
 
     def close(self):
         if self._h is not None and self._h.value:

@@ -294,6 +294,101 @@ bool StompOptimizer::retargetBatch(const std::vector<StompOptimizer*>& optimizer
     return true;
 }
 
+// the optimizer's own copies of the collision points and the constraints (createSibling reads
+// them through desc_) after a retarget that replaced them
+void StompOptimizer::followModel(const std::vector<stomp_sphere>* collision_points, const Constraints* constraints)
+{
+    if (collision_points) {
+        spheres_ = *collision_points;
+        desc_.num_spheres = (int32_t)spheres_.size();
+        desc_.spheres = spheres_.data();
+    }
+    if (constraints) {
+        constraints_ = *constraints;
+        desc_.num_orientation_constraints = (int32_t)constraints_.orientation_constraints.size();
+        desc_.orientation_constraints = constraints_.orientation_constraints.data();
+    }
+    if (collision_points || constraints) ++model_epoch_;
+}
+
+stomp_request StompOptimizer::request(const std::vector<double>& start, const std::vector<double>& goal, uint64_t seed,
+                                      const std::vector<stomp_sphere>* collision_points,
+                                      const Constraints* constraints) const
+{
+    stomp_request r{};
+    r.struct_size = (int32_t)sizeof(stomp_request);
+    r.start = start.data();
+    r.goal = goal.data();
+    r.seed = seed;
+    r.num_spheres = collision_points ? (int32_t)collision_points->size() : -1;
+    r.spheres = collision_points ? collision_points->data() : nullptr;
+    r.num_orientation_constraints = constraints ? (int32_t)constraints->orientation_constraints.size() : -1;
+    r.orientation_constraints = constraints ? constraints->orientation_constraints.data() : nullptr;
+    return r;
+}
+
+bool StompOptimizer::retarget(const std::vector<double>& start, const std::vector<double>& goal, uint64_t seed,
+                              const std::vector<stomp_sphere>* collision_points, const Constraints* constraints)
+{
+    if (!engine_) return false;
+    if ((int)start.size() != J_ || (int)goal.size() != J_) {
+        error_ = "retarget: start and goal must have num_joints entries";
+        return false;
+    }
+    const stomp_request r = request(start, goal, seed, collision_points, constraints);
+    if (!check(stomp_engine_retarget_request(engine_, &r))) return false;
+    followRetarget(start, goal, seed);
+    followModel(collision_points, constraints);
+    return true;
+}
+
+bool StompOptimizer::retargetBatch(const std::vector<StompOptimizer*>& optimizers,
+                                   const std::vector<std::vector<double>>& starts,
+                                   const std::vector<std::vector<double>>& goals, const std::vector<uint64_t>& seeds,
+                                   const std::vector<const std::vector<stomp_sphere>*>& collision_points,
+                                   const std::vector<const Constraints*>& constraints)
+{
+    if (optimizers.empty()) return true;
+    StompOptimizer* first = optimizers[0];
+    if (!first) return false;
+    const size_t P = optimizers.size();
+    if (starts.size() != P || goals.size() != P || seeds.size() != P || collision_points.size() != P ||
+        constraints.size() != P) {
+        first->error_ = "retargetBatch: one start, goal, seed, collision point list and constraints per optimizer";
+        return false;
+    }
+    std::vector<stomp_engine*> engines;
+    std::vector<stomp_request> rs;
+    for (size_t p = 0; p < P; ++p) {
+        StompOptimizer* o = optimizers[p];
+        if (!o || !o->engine_) {
+            first->error_ = "retargetBatch: an optimizer without an engine";
+            return false;
+        }
+        if ((int)starts[p].size() != o->J_ || (int)goals[p].size() != o->J_) {
+            first->error_ = "retargetBatch: start and goal must have num_joints entries";
+            return false;
+        }
+        engines.push_back(o->engine_);
+        rs.push_back(o->request(starts[p], goals[p], seeds[p], collision_points[p], constraints[p]));
+    }
+    stomp_group* grp = nullptr;
+    if (stomp_group_create_flags(engines.data(), (int32_t)P, STOMP_GROUP_ACCEPT_STATE_TERMS | STOMP_GROUP_ACCEPT_CUMULATIVE,
+                                 -1, &grp) != 0) {
+        first->error_ = stomp_last_error();
+        return false;
+    }
+    const int rc = stomp_group_retarget_requests(grp, rs.data());
+    if (rc != 0) first->error_ = stomp_group_last_error(grp);
+    stomp_group_destroy(grp);
+    if (rc != 0) return false;
+    for (size_t p = 0; p < P; ++p) {
+        optimizers[p]->followRetarget(starts[p], goals[p], seeds[p]);
+        optimizers[p]->followModel(collision_points[p], constraints[p]);
+    }
+    return true;
+}
+
 bool StompOptimizer::initialize(int num_time_steps)
 {
     if (!engine_) return false;
@@ -713,6 +808,7 @@ bool PolicyImprovement::setNumRollouts(const int num_rollouts, const int num_reu
             own_ = nullptr;
         }
         K_ = num_rollouts;
+        Kr_ = num_reused_rollouts;
         if (num_rollouts == owner_->parameters_->num_rollouts &&
             num_reused_rollouts == owner_->parameters_->num_reused_rollouts &&
             use_cumulative_ == owner_->parameters_->use_cumulative_costs) {
@@ -722,6 +818,7 @@ bool PolicyImprovement::setNumRollouts(const int num_rollouts, const int num_reu
         std::string err;
         own_ = owner_->createSibling(num_rollouts, num_reused_rollouts, use_cumulative_, err);
         engine_ = own_;
+        own_epoch_ = owner_->model_epoch_;
         if (!own_) {
             error_ = "setNumRollouts: " + err;
             return false;
@@ -748,6 +845,19 @@ bool PolicyImprovement::getRollouts(std::vector<std::vector<VectorXd>>& rollouts
     if (!initialized_) { error_ = "getRollouts: not initialized"; return false; }
     if ((int)noise_stddev.size() != J_) { error_ = "getRollouts: one noise_stddev per dimension"; return false; }
     if (!host_) {
+        if (engine_ == own_ && own_ && own_epoch_ != owner_->model_epoch_) {
+            // the optimizer was retargeted onto other collision points or constraints: the engine
+            // of our own is dropped and made again from the optimizer's new model
+            stomp_engine_destroy(own_);
+            std::string err;
+            own_ = owner_->createSibling(K_, Kr_, use_cumulative_, err);
+            engine_ = own_;
+            own_epoch_ = owner_->model_epoch_;
+            if (!own_) {
+                error_ = "getRollouts: " + err;
+                return false;
+            }
+        }
         if (engine_ == own_) {
             // generateRollouts perturbs the policy's current parameters: the optimizer's theta
             std::vector<double> th((size_t)J_ * N_);
