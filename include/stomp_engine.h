@@ -297,7 +297,8 @@ int stomp_engine_retarget_request(stomp_engine* e, const stomp_request* r);
  * [5] padding positions in LDS, [6] the LDS-lean layout (0, 1, 2), [7] the sincos pre-pass,
  * [8] orientation constraints, [9] state-cost terms on, [10] model changes so far (retarget-request
  * calls that replaced the collision points or the constraints), [11] device or pinned allocations
- * made inside retarget-request calls so far.  Host only. */
+ * made inside retarget calls of either kind so far (a call's staging included; a repeated call
+ * allocates nothing).  Host only. */
 int stomp_engine_model_info(stomp_engine* e, int64_t info[12]);
 
 int stomp_engine_get_theta(stomp_engine* e, double* theta);

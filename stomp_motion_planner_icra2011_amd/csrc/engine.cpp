@@ -39,7 +39,6 @@ void release(stomp_engine* e)
     if (e->h_cf) hipHostFree(e->h_cf);
     if (e->h_track) hipHostFree(e->h_track);
     if (e->h_stall) hipHostFree(e->h_stall);
-    if (e->h_rt) hipHostFree(e->h_rt);
     if (e->h_rq) hipHostFree(e->h_rq);
     if (e->d_rq) hipFree(e->d_rq);
     for (auto& r : e->coll_ring)

@@ -19,9 +19,10 @@
 //     that writes)
 //   cumulative costs (stomp_group_create_flags): k_cumulative_group before the weights launch, in
 //     its timed scope (an engine without has no workgroup that writes)
-// stomp_group_retarget puts every engine of the group onto a new start, goal and seed in one launch
-// and one read-back (engine_retarget.cpp); the launch also writes the padding-collision flags of
-// the group's own DevModel list, which the grouped launches of a run and a synchronize read.
+// stomp_group_retarget and stomp_group_retarget_requests put every engine of the group onto its next
+// request in one launch and one read-back (group_retarget, over engine_retarget.cpp); the launch
+// also writes the padding-collision flags of the group's own DevModel list, which the grouped
+// launches of a run and a synchronize read, and rewrites the entries of a replaced model.
 #include "engine_internal.h"
 
 #include <algorithm>
@@ -57,16 +58,14 @@ struct stomp_group {
     int* h_mirror = nullptr;              // [2][P][2]
     TrackArgs* d_track_all = nullptr;     // [P]
     hipEvent_t opt_ev[2] = {nullptr, nullptr};
-    // stomp_group_retarget: one call's staging (pinned and device); the padding-collision flag each
-    // entry of d_models holds, so that an engine retargeted on its own (stomp_engine_retarget knows
-    // no group) gets its entry refreshed before the next launch that reads the list
-    unsigned char *h_rt = nullptr, *d_rt = nullptr;
-    std::vector<int> pad_flags;
-    // stomp_group_retarget_requests: one call's staging, held with a capacity; the model epoch of
-    // every engine the group's lists were made from (an engine whose model was replaced on its own
-    // since then leaves them stale: check_epochs)
+    // the retarget calls: one call's staging (pinned and device), held with a capacity; the
+    // padding-collision flag each entry of d_models holds, so that an engine retargeted on its own
+    // (stomp_engine_retarget knows no group) gets its entry refreshed before the next launch that
+    // reads the list; the model epoch of every engine the group's lists were made from (an engine
+    // whose model was replaced on its own since then leaves them stale: check_epochs)
     unsigned char *h_rq = nullptr, *d_rq = nullptr;
     size_t rq_cap = 0;
+    std::vector<int> pad_flags;
     std::vector<long long> epochs;
     std::string err;
 };
@@ -401,6 +400,56 @@ const char* refusal_text(bool state_terms, bool cumulative)
     return "groups run single-device engines of at most 16 joints without state-cost terms or cumulative costs";
 }
 
+// What both group retarget calls do once their arguments are checked: every engine onto its
+// request (none with a null start or goal) in one upload, one launch and one read-back; every engine
+// leaves in the freshly created iteration state, whichever iteration its optimize loop stopped at.
+int group_retarget(stomp_group* g, const stomp_request* rs)
+{
+    const int P = (int)g->e.size();
+    // host only: before any engine or device is touched
+    for (int p = 0; p < P; ++p)
+        if (int rc = request_validate(g->e[p], &rs[p], p)) return gfail(g, rc, std::string(g_last_error).c_str());
+    // (the plans ask the rollout kernels' attributes of the current device: the group's)
+    DeviceGuard dg(g->device);
+    std::vector<ModelPlan> plans(P);
+    for (int p = 0; p < P; ++p)
+        if (int rc = request_plan(g->e[p], &rs[p], plans[p])) return gfail(g, rc, std::string(g_last_error).c_str());
+    // stomp_group_create_flags' shape rule and accept rule on the planned models
+    const DevModel& m0 = plans[0].m;
+    const size_t lds0 = rollout_lds_bytes(m0, m0.pad_lds);
+    int nterms = 0;
+    size_t terms_lds = 0;
+    bool behind = false;   // an engine's model was replaced on its own: the lists are rewritten whatever the requests keep
+    for (int p = 0; p < P; ++p) {
+        const DevModel& m = plans[p].m;
+        if (m.S != m0.S || rollout_lds_bytes(m, m.pad_lds) != lds0 || m.pad_lds != m0.pad_lds || m.lean != m0.lean)
+            return gfail(g, STOMP_E_INVALID,
+                         "the engines of a group have one shape (J, N, K, K_r, spheres, model, field layout)");
+        if (plans[p].terms_on && !g->state_terms)
+            return gfail(g, STOMP_E_UNSUPPORTED, refusal_text(false, g->ncum > 0));
+        behind = behind || g->epochs[p] != g->e[p]->model_epoch;
+        if (!plans[p].terms_on) continue;
+        ++nterms;
+        terms_lds = std::max(terms_lds, terms_lds_bytes(plans[p].terms));
+    }
+    const size_t cap = g->rq_cap;
+    if (!reserve_stage(&g->h_rq, &g->d_rq, &g->rq_cap, request_stage_bytes(g->e.data(), P, plans)))
+        return gfail(g, STOMP_E_DEVICE, "group retarget allocation failed");
+    if (g->rq_cap != cap)
+        for (stomp_engine* e : g->e) e->rq_allocs += 2;
+    // the launch rewrites the group's own entries of a replaced model, so nothing staged from the
+    // old models outlives this call
+    if (int rc = request_engines(g->e.data(), P, rs, plans, g->h_rq, g->d_rq, g->d_models, g->d_tmodels, behind))
+        return gfail(g, rc, std::string(g_last_error).c_str());
+    g->nterms = nterms;
+    g->terms_lds = terms_lds;
+    for (int p = 0; p < P; ++p) {
+        g->pad_flags[p] = g->e[p]->pad_collision;
+        g->epochs[p] = g->e[p]->model_epoch;
+    }
+    return 0;
+}
+
 TrackArgs track_args(const stomp_group* g, int p)
 {
     const stomp_engine* e = g->e[p];
@@ -610,8 +659,8 @@ void stomp_group_destroy(stomp_group* g)
         hipEventSynchronize(g->staged);
         hipEventDestroy(g->staged);
     }
-    free_device(g->d_models, g->d_tmodels, g->d_args, g->d_opt, g->d_mirror, g->d_track_all, g->d_rt, g->d_rq);
-    free_pinned(g->h_args, g->h_opt, g->h_mirror, g->h_rt, g->h_rq);
+    free_device(g->d_models, g->d_tmodels, g->d_args, g->d_opt, g->d_mirror, g->d_track_all, g->d_rq);
+    free_pinned(g->h_args, g->h_opt, g->h_mirror, g->h_rq);
     for (hipEvent_t ev : g->opt_ev)
         if (ev) hipEventDestroy(ev);
     delete g;
@@ -735,22 +784,11 @@ int stomp_group_retarget(stomp_group* g, const double* starts, const double* goa
     // all of this before any engine or device is touched
     if (!g) return gfail(nullptr, STOMP_E_INVALID, "null group");
     if (!starts || !goals || !seeds) return gfail(nullptr, STOMP_E_INVALID, "retarget: null starts, goals or seeds");
-    const int P = (int)g->e.size();
     if (int rc = check_epochs(g)) return rc;
-    if (int rc = retarget_validate(g->e.data(), P, starts, goals)) return gfail(g, rc, std::string(g_last_error).c_str());
-    DeviceGuard dg(g->device);
-    if (!g->d_rt) {
-        const size_t bytes = retarget_stage_bytes(P, g->e[0]->J);
-        if ((!g->h_rt && hipHostMalloc((void**)&g->h_rt, bytes) != hipSuccess) ||
-            hipMalloc((void**)&g->d_rt, bytes) != hipSuccess)
-            return gfail(g, STOMP_E_DEVICE, "group retarget allocation failed");
-    }
-    // one launch and one read-back for the whole group; every engine leaves in the freshly created
-    // iteration state, whichever iteration its optimize loop stopped at
-    if (int rc = retarget_engines(g->e.data(), P, starts, goals, seeds, g->h_rt, g->d_rt, g->d_models))
-        return gfail(g, rc, std::string(g_last_error).c_str());
-    for (int p = 0; p < P; ++p) g->pad_flags[p] = g->e[p]->pad_collision;
-    return 0;
+    const size_t P = g->e.size(), J = (size_t)g->e[0]->J;
+    std::vector<stomp_request> rs(P);
+    for (size_t p = 0; p < P; ++p) rs[p] = kept_request(starts + p * J, goals + p * J, seeds[p]);
+    return group_retarget(g, rs.data());
 }
 
 int stomp_group_retarget_requests(stomp_group* g, const stomp_request* rs)
@@ -758,56 +796,12 @@ int stomp_group_retarget_requests(stomp_group* g, const stomp_request* rs)
     // all of this before any engine or device is touched
     if (!g) return gfail(nullptr, STOMP_E_INVALID, "null group");
     if (!rs) return gfail(nullptr, STOMP_E_INVALID, "retarget: null requests");
-    const int P = (int)g->e.size();
-    for (int p = 0; p < P; ++p) {
+    for (size_t p = 0; p < g->e.size(); ++p) {
         if (rs[p].struct_size != (int32_t)sizeof(stomp_request))
             return gfail(g, STOMP_E_INVALID, "retarget: struct_size is not sizeof(stomp_request)");
         if (!rs[p].start || !rs[p].goal) return gfail(g, STOMP_E_INVALID, "retarget: null start or goal");
     }
-    // (the plans ask the rollout kernels' attributes of the current device: the group's)
-    DeviceGuard dg(g->device);
-    std::vector<ModelPlan> plans(P);
-    for (int p = 0; p < P; ++p)
-        if (int rc = request_plan(g->e[p], &rs[p], p, plans[p])) return gfail(g, rc, std::string(g_last_error).c_str());
-    // stomp_group_create_flags' shape rule and accept rule on the planned models
-    const DevModel& m0 = plans[0].m;
-    const size_t lds0 = rollout_lds_bytes(m0, m0.pad_lds);
-    int nterms = 0;
-    size_t terms_lds = 0;
-    for (int p = 0; p < P; ++p) {
-        const DevModel& m = plans[p].m;
-        if (m.S != m0.S || rollout_lds_bytes(m, m.pad_lds) != lds0 || m.pad_lds != m0.pad_lds || m.lean != m0.lean)
-            return gfail(g, STOMP_E_INVALID,
-                         "the engines of a group have one shape (J, N, K, K_r, spheres, model, field layout)");
-        if (plans[p].terms_on && !g->state_terms)
-            return gfail(g, STOMP_E_UNSUPPORTED, refusal_text(false, g->ncum > 0));
-        if (!plans[p].terms_on) continue;
-        ++nterms;
-        terms_lds = std::max(terms_lds, terms_lds_bytes(plans[p].terms));
-    }
-    const size_t bytes = request_stage_bytes(g->e.data(), P, plans);
-    if (bytes > g->rq_cap) {
-        // (no launch reads the old staging: every call that used it waited for the stream)
-        const size_t cap = std::max(bytes, 2 * g->rq_cap);
-        free_pinned(g->h_rq);
-        free_device(g->d_rq);
-        g->rq_cap = 0;
-        if (hipHostMalloc((void**)&g->h_rq, cap) != hipSuccess || hipMalloc((void**)&g->d_rq, cap) != hipSuccess)
-            return gfail(g, STOMP_E_DEVICE, "group retarget allocation failed");
-        g->rq_cap = cap;
-        for (stomp_engine* e : g->e) e->rq_allocs += 2;
-    }
-    // one upload, one launch and one read-back for the whole group; the launch rewrites the
-    // group's own model entries, so nothing staged from the old models outlives this call
-    if (int rc = request_engines(g->e.data(), P, rs, plans, g->h_rq, g->d_rq, g->d_models, g->d_tmodels))
-        return gfail(g, rc, std::string(g_last_error).c_str());
-    g->nterms = nterms;
-    g->terms_lds = terms_lds;
-    for (int p = 0; p < P; ++p) {
-        g->pad_flags[p] = g->e[p]->pad_collision;
-        g->epochs[p] = g->e[p]->model_epoch;
-    }
-    return 0;
+    return group_retarget(g, rs);
 }
 
 const char* stomp_group_last_error(const stomp_group* g) { return g ? g->err.c_str() : g_last_error.c_str(); }

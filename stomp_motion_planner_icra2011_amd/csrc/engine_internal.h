@@ -7,9 +7,8 @@
 //   engine_exchange.cpp  the in-process group, the RCCL path, the collectives, calibration
 //   engine_group.cpp     stomp_group: one launcher of a grouped step (launch_step) and one arena of
 //                        staged arguments behind run, synchronize and optimize
-//   engine_retarget.cpp  stomp_engine_retarget and the part of it stomp_group_retarget shares;
-//                        stomp_engine_retarget_request (a request's collision points and path
-//                        constraints too) and the part stomp_group_retarget_requests shares
+//   engine_retarget.cpp  the one retarget path (validate, plan, stage, launch, commit) behind
+//                        stomp_engine_retarget, stomp_engine_retarget_request and the two group calls
 //   sdf_build.cpp        the distance-field builders (does not include this header)
 //   scene.cpp            stomp_scene: the field kept in a static and a dynamic layer (uses fail and
 //                        DeviceGuard only)
@@ -143,7 +142,8 @@ struct stomp_engine {
     std::vector<double> h_jmin, h_jmax;
     // held with a capacity, reallocated only when a request needs more than every earlier one: the
     // LDS image (8-byte words), the path constraints' table (entries), the lean layout's saved-frame
-    // blocks (doubles), one call's staging (pinned and device, bytes)
+    // blocks (doubles), one retarget call's staging (pinned and device, bytes; allocated by the
+    // engine's first call -- a group stages its engines in buffers of its own)
     unsigned long long* d_img = nullptr;
     size_t img_cap = 0;
     stomp::OcDev* d_oc = nullptr;
@@ -153,7 +153,7 @@ struct stomp_engine {
     unsigned char *h_rq = nullptr, *d_rq = nullptr;
     size_t rq_cap = 0;
     // model changes so far (a group compares it with the epoch it last saw), and the device or
-    // pinned allocations made inside retarget-request calls
+    // pinned allocations made inside retarget calls of either kind (the staging's included)
     long long model_epoch = 0, rq_allocs = 0;
     std::vector<void*> allocs;
     double *d_theta = nullptr, *d_LT = nullptr, *d_MT = nullptr, *d_QT = nullptr;
@@ -185,11 +185,9 @@ struct stomp_engine {
     int grid_n[3] = {0, 0, 0};
     int* d_pad_cf = nullptr;
     int pad_collision = 0;
-    // stomp_engine_retarget: the boundary rows of R cut to the free columns [12][N] and R^-1
-    // transposed [N][N] (uploaded at creation), the engine's own staging of one call (pinned and
-    // device, allocated by its first call; a group stages its engines in buffers of its own)
+    // a retarget's theta_0: the boundary rows of R cut to the free columns [12][N] and R^-1
+    // transposed [N][N] (uploaded at creation)
     double *d_Rb = nullptr, *d_RinvT = nullptr;
-    unsigned char *h_rt = nullptr, *d_rt = nullptr;
     bool reused_next = false, extra_added = false;
     // the extra rollout's params are not the current theta (stomp_engine_set_theta after its
     // noiseless rollout, stomp_pi_add_extra_rollouts with rows of the caller's): the next reuse step
@@ -275,17 +273,12 @@ void launch_noiseless(stomp_engine* e, int member);
 int run_reuse(stomp_engine* e);
 
 // ---- engine_retarget.cpp
-// One call's staging for P engines of J joints: [P] RetargetArgs, [P][2][J] vectors, [P] flags.
-size_t retarget_stage_bytes(int P, int J);
-// everything stomp_engine_retarget / stomp_group_retarget refuse before an engine or a device is
-// touched (es: the P engines, none null; seeds may be null: every engine keeps its own)
-int retarget_validate(stomp_engine* const* es, int P, const double* starts, const double* goals);
-// the P engines (one shape, one stream, validated) onto their new problems in one launch and one
-// read-back of the P padding-collision flags; h / d: staging of retarget_stage_bytes(P, J), free
-// for this call; d_models: the group's DevModel list whose flags the launch also writes, or null
-int retarget_engines(stomp_engine* const* es, int P, const double* starts, const double* goals,
-                     const uint64_t* seeds, unsigned char* h, unsigned char* d, DevModel* d_models);
-
+// the request stomp_engine_retarget / stomp_group_retarget make of their arguments: it keeps the
+// engine's collision points and path constraints
+inline stomp_request kept_request(const double* start, const double* goal, uint64_t seed)
+{
+    return stomp_request{(int32_t)sizeof(stomp_request), start, goal, seed, -1, nullptr, -1, nullptr};
+}
 // the host side of a retarget once its launch has run: the new vectors, seed (null: kept) and
 // padding-collision flag, every piece of iteration state dropped
 void retarget_host_state(stomp_engine* e, const double* start, const double* goal, const uint64_t* seed, int flag);
@@ -318,19 +311,25 @@ struct ModelPlan {
     double* d_terms_traj = nullptr;
     LiveAlloc live;
 };
-// everything stomp_engine_retarget_request / stomp_group_retarget_requests refuse about request r
-// for engine e before an engine or a device is touched, then its plan (p: the engine's index in
-// the messages)
-int request_plan(const stomp_engine* e, const stomp_request* r, int p, ModelPlan& plan);
+// everything the retarget calls refuse about request r (start and goal not null) for engine e
+// on the host alone, before an engine or a device is touched (p: the engine's index in the messages)
+int request_validate(const stomp_engine* e, const stomp_request* r, int p);
+// the plan of a validated request, with the engine's device current; for a request that keeps both
+// lists a copy of the engine's model and terms model
+int request_plan(const stomp_engine* e, const stomp_request* r, ModelPlan& plan);
 // the staging of one call for these plans (bytes): [P] RequestArgs, [P][2][J] vectors, each
 // engine's image tables and constraint table, [P] flags
 size_t request_stage_bytes(stomp_engine* const* es, int P, const std::vector<ModelPlan>& plans);
+// one retarget call's staging of at least `bytes`, pinned (*h) and on the device (*d), held with a
+// capacity (*cap) that at least doubles when it grows; false: an allocation failed, nothing is held
+bool reserve_stage(unsigned char** h, unsigned char** d, size_t* cap, size_t bytes);
 // the commit: the P engines (one shape, one stream, validated and planned) onto their requests in
 // one upload, one launch and one read-back of the P flags; h / d: staging of request_stage_bytes,
-// free for this call; d_models / d_tmodels: a group's lists, whose entries the launch also
-// rewrites, or null
+// free for this call; d_models / d_tmodels: a group's lists, whose flags the launch also writes and
+// whose entries it rewrites when a request replaces something or the lists are behind an engine's
+// model (lists_behind), or null
 int request_engines(stomp_engine* const* es, int P, const stomp_request* rs, std::vector<ModelPlan>& plans,
-                    unsigned char* h, unsigned char* d, DevModel* d_models, TermsModel* d_tmodels);
+                    unsigned char* h, unsigned char* d, DevModel* d_models, TermsModel* d_tmodels, bool lists_behind);
 
 // ---- engine_create.cpp: the stages that depend on the collision points and the path
 // constraints, shared by creation and stomp_engine_retarget_request (err: where a refusal's message

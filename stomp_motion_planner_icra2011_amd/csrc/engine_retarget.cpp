@@ -1,75 +1,19 @@
-// engine_retarget.cpp -- stomp_engine_retarget, and the part of it stomp_group_retarget shares:
-// a live engine put onto a new start, goal and seed.  Only four things in an engine depend on the
-// request: the start / goal vectors, theta_0, the padding rows' sphere positions with their
-// collision flag, and the noise seed.  One launch (k_retarget) remakes the device side of all P
-// engines of a call, one read-back fetches the P flags, and the host drops every piece of
-// iteration state that was made with the old problem, so that the engine is the one
-// stomp_engine_create would return for the new one.
+// engine_retarget.cpp -- the one path behind the four retarget entry points: live engines put onto
+// their next requests.  A request is a new start, goal and seed and, where it replaces them, the
+// collision points and the path constraints; stomp_engine_retarget and stomp_group_retarget make
+// requests that keep both.  Only four things in an engine depend on the start and goal: the two
+// vectors, theta_0, the padding rows' sphere positions with their collision flag, and the noise
+// seed.  Every request is validated and its model planned on the host (request_validate,
+// request_plan); then one upload, one launch (k_retarget) and one read-back of the P flags remake
+// the device side of all P engines of a call (request_engines), and the host drops every piece of
+// iteration state that was made with the old problem (retarget_host_state), so that the engine is
+// the one stomp_engine_create would return for the new one.  For a kept model the plan is a copy of
+// the engine's fields: nothing is allocated but the call's staging, and that once.
 #include "engine_internal.h"
 
 using namespace stomp;
 
 namespace stomp {
-
-size_t retarget_stage_bytes(int P, int J)
-{
-    return align256(sizeof(RetargetArgs) * P) + align256(sizeof(double) * 2 * J * P) + align256(sizeof(int) * P);
-}
-
-int retarget_validate(stomp_engine* const* es, int P, const double* starts, const double* goals)
-{
-    if (!starts || !goals) return fail(nullptr, STOMP_E_INVALID, "retarget: null start or goal");
-    for (int p = 0; p < P; ++p) {
-        const int J = es[p]->J;
-        for (int d = 0; d < J; ++d)
-            if (!std::isfinite(starts[(size_t)p * J + d]) || !std::isfinite(goals[(size_t)p * J + d]))
-                return fail(nullptr, STOMP_E_INVALID, "retarget: start / goal of engine %d, joint %d is not finite", p, d);
-    }
-    for (int p = 0; p < P; ++p)
-        if (es[p]->world > 1 || es[p]->gather)
-            // its ranks would have to retarget in lockstep (as the PolicyImprovement API on ranks)
-            return fail(nullptr, STOMP_E_UNSUPPORTED, "retargeting is single-rank (a sharded engine's ranks would "
-                                                      "have to retarget in lockstep)");
-    for (int p = 0; p < P; ++p)
-        if (es[p]->tracking) return fail(nullptr, STOMP_E_INVALID, "retarget: an engine is inside its optimize loop");
-    return 0;
-}
-
-int retarget_engines(stomp_engine* const* es, int P, const double* starts, const double* goals,
-                     const uint64_t* seeds, unsigned char* h, unsigned char* d, DevModel* d_models)
-{
-    stomp_engine* e0 = es[0];
-    const int J = e0->J, N = e0->N;
-    hipStream_t s = e0->stream;
-    const size_t o_vec = align256(sizeof(RetargetArgs) * P), o_flag = o_vec + align256(sizeof(double) * 2 * J * P);
-    RetargetArgs* as = (RetargetArgs*)h;
-    double* vec = (double*)(h + o_vec);
-    int* flags = (int*)(h + o_flag);
-    for (int p = 0; p < P; ++p) {
-        stomp_engine* e = es[p];
-        RetargetArgs& a = as[p];
-        a.model = e->model;
-        a.stage = (const double*)(d + o_vec) + (size_t)p * 2 * J;
-        a.Rb = e->d_Rb; a.RinvT = e->d_RinvT;
-        a.theta = e->d_theta; a.last_traj = e->d_last_traj; a.best_traj = e->d_best_traj;
-        a.start = e->d_start; a.goal = e->d_goal;
-        a.pad_pos = e->d_pad_pos; a.pad_cf = e->d_pad_cf;
-        a.model_flag = d_models ? &d_models[p].pad_collision : nullptr;
-        a.flag_out = (int*)(d + o_flag) + p;
-        std::memcpy(vec + (size_t)p * 2 * J, starts + (size_t)p * J, sizeof(double) * J);
-        std::memcpy(vec + (size_t)p * 2 * J + J, goals + (size_t)p * J, sizeof(double) * J);
-    }
-    // ordered on the stream after everything enqueued before: iterations still in flight, and a
-    // stomp_engine_refresh_field whose bricks the padding FK reads
-    HIP_TRY(e0, hipMemcpyAsync(d, h, o_flag, hipMemcpyHostToDevice, s));
-    launch_retarget((const RetargetArgs*)d, P, J, N, s);
-    HIP_TRY(e0, hipGetLastError());
-    HIP_TRY(e0, hipMemcpyAsync(flags, d + o_flag, sizeof(int) * P, hipMemcpyDeviceToHost, s));
-    HIP_TRY(e0, hipStreamSynchronize(s));
-    for (int p = 0; p < P; ++p)
-        retarget_host_state(es[p], starts + (size_t)p * J, goals + (size_t)p * J, seeds ? &seeds[p] : nullptr, flags[p]);
-    return 0;
-}
 
 // the host side of a retarget, once the launch has run: the new vectors, seed and flag, and every
 // piece of iteration state dropped
@@ -95,7 +39,6 @@ void retarget_host_state(stomp_engine* e, const double* start, const double* goa
     e->cur_it = -1;
 }
 
-// ---------------------------------------------------------------- requests with a model
 namespace {
 
 bool all_finite(const double* v, int n)
@@ -129,9 +72,9 @@ struct StageMap {
 
 int request_validate(const stomp_engine* e, const stomp_request* r, int p)
 {
-    const int J = e->J;
-    if (!all_finite(r->start, J) || !all_finite(r->goal, J))
-        return fail(nullptr, STOMP_E_INVALID, "retarget: start / goal of engine %d is not finite", p);
+    for (int d = 0; d < e->J; ++d)
+        if (!std::isfinite(r->start[d]) || !std::isfinite(r->goal[d]))
+            return fail(nullptr, STOMP_E_INVALID, "retarget: start / goal of engine %d, joint %d is not finite", p, d);
     if (r->num_spheres < -1 || (r->num_spheres > 0 && !r->spheres))
         return fail(nullptr, STOMP_E_INVALID, "retarget: request %d has %d spheres and no sphere array", p, r->num_spheres);
     if (r->num_orientation_constraints < -1)
@@ -158,9 +101,8 @@ int request_validate(const stomp_engine* e, const stomp_request* r, int p)
     return 0;
 }
 
-int request_plan(const stomp_engine* e, const stomp_request* r, int p, ModelPlan& plan)
+int request_plan(const stomp_engine* e, const stomp_request* r, ModelPlan& plan)
 {
-    if (int rc = request_validate(e, r, p)) return rc;
     plan.spheres = r->num_spheres >= 0;
     plan.constraints = r->num_orientation_constraints >= 0;
     plan.m = e->model;
@@ -221,7 +163,8 @@ int request_buffers(stomp_engine* const* es, int P, std::vector<ModelPlan>& plan
 }
 
 int request_launch(stomp_engine* const* es, int P, const stomp_request* rs, const std::vector<ModelPlan>& plans,
-                   unsigned char* h, unsigned char* d, DevModel* d_models, TermsModel* d_tmodels, const int** flags_out)
+                   unsigned char* h, unsigned char* d, DevModel* d_models, TermsModel* d_tmodels, bool replaces,
+                   const int** flags_out)
 {
     stomp_engine* e0 = es[0];
     const int J = e0->J, N = e0->N;
@@ -233,17 +176,17 @@ int request_launch(stomp_engine* const* es, int P, const stomp_request* rs, cons
     for (int p = 0; p < P; ++p) {
         stomp_engine* e = es[p];
         const ModelPlan& pl = plans[p];
+        replaces = replaces || pl.spheres || pl.constraints;
         RequestArgs& r = as[p];
         std::memset(&r, 0, sizeof r);
-        RetargetArgs& a = r.rt;
-        a.model = pl.m;
-        a.stage = (const double*)(d + at.vec) + (size_t)p * 2 * J;
-        a.Rb = e->d_Rb; a.RinvT = e->d_RinvT;
-        a.theta = e->d_theta; a.last_traj = e->d_last_traj; a.best_traj = e->d_best_traj;
-        a.start = e->d_start; a.goal = e->d_goal;
-        a.pad_pos = (double*)pl.m.pad_pos; a.pad_cf = e->d_pad_cf;
-        a.model_flag = d_models ? &d_models[p].pad_collision : nullptr;
-        a.flag_out = (int*)(d + at.flag) + p;
+        r.model = pl.m;
+        r.stage = (const double*)(d + at.vec) + (size_t)p * 2 * J;
+        r.Rb = e->d_Rb; r.RinvT = e->d_RinvT;
+        r.theta = e->d_theta; r.last_traj = e->d_last_traj; r.best_traj = e->d_best_traj;
+        r.start = e->d_start; r.goal = e->d_goal;
+        r.pad_pos = (double*)pl.m.pad_pos; r.pad_cf = e->d_pad_cf;
+        r.model_flag = d_models ? &d_models[p].pad_collision : nullptr;
+        r.flag_out = (int*)(d + at.flag) + p;
         // collision points kept: the tables are the engine's own, which no workgroup writes
         r.stage_img = pl.spheres ? (const unsigned long long*)(d + at.img[p]) : pl.m.img;
         r.img_out = pl.d_img;
@@ -265,9 +208,10 @@ int request_launch(stomp_engine* const* es, int P, const stomp_request* rs, cons
         if (pl.constraints && !pl.oc.empty()) std::memcpy(h + at.oc[p], pl.oc.data(), sizeof(OcDev) * pl.oc.size());
     }
     // ordered on the stream after everything enqueued before: iterations still in flight read the
-    // old image, the old constraint table and the group's old model entries
+    // old image, the old constraint table and the group's old model entries, and a
+    // stomp_engine_refresh_field's bricks are the ones the padding FK reads
     HIP_TRY(nullptr, hipMemcpyAsync(d, h, at.flag, hipMemcpyHostToDevice, s));
-    launch_retarget_model((const RequestArgs*)d, P, J, N, s);
+    launch_retarget((const RequestArgs*)d, P, J, N, replaces, s);
     HIP_TRY(nullptr, hipGetLastError());
     HIP_TRY(nullptr, hipMemcpyAsync(flags, d + at.flag, sizeof(int) * P, hipMemcpyDeviceToHost, s));
     HIP_TRY(nullptr, hipStreamSynchronize(s));
@@ -278,11 +222,11 @@ int request_launch(stomp_engine* const* es, int P, const stomp_request* rs, cons
 }  // namespace
 
 int request_engines(stomp_engine* const* es, int P, const stomp_request* rs, std::vector<ModelPlan>& plans,
-                    unsigned char* h, unsigned char* d, DevModel* d_models, TermsModel* d_tmodels)
+                    unsigned char* h, unsigned char* d, DevModel* d_models, TermsModel* d_tmodels, bool lists_behind)
 {
     const int* flags = nullptr;
     int rc = request_buffers(es, P, plans);
-    if (!rc) rc = request_launch(es, P, rs, plans, h, d, d_models, d_tmodels, &flags);
+    if (!rc) rc = request_launch(es, P, rs, plans, h, d, d_models, d_tmodels, lists_behind, &flags);
     if (rc) {
         // nothing was handed to an engine yet: what the call allocated is given back (the stream is
         // waited for first, a launch of this call may still write the new buffers)
@@ -314,25 +258,40 @@ int request_engines(stomp_engine* const* es, int P, const stomp_request* rs, std
     return 0;
 }
 
+bool reserve_stage(unsigned char** h, unsigned char** d, size_t* cap, size_t bytes)
+{
+    if (bytes <= *cap) return true;
+    const size_t grown = std::max(bytes, 2 * *cap);
+    // (no launch reads the old staging: every call that used it waited for the stream)
+    if (*h) hipHostFree(*h);
+    if (*d) hipFree(*d);
+    *h = *d = nullptr;
+    *cap = 0;
+    if (hipHostMalloc((void**)h, grown) != hipSuccess || hipMalloc((void**)d, grown) != hipSuccess) return false;
+    *cap = grown;
+    return true;
+}
+
 }  // namespace stomp
 
 namespace {
 
-// one call's staging of `bytes`, pinned and on the device, held with a capacity
-int reserve_request_stage(stomp_engine* e, size_t bytes)
+// What both engine entry points do once their arguments are checked: e onto request r.  A refusal
+// writes nothing of the engine, not even its message (stomp_last_error has it), so the "inside its
+// optimize loop" refusal may be made from another host thread than the loop's (stomp_engine_retarget
+// copies the message into the engine afterwards, as its callers expect).
+int retarget_engine(stomp_engine* e, const stomp_request* r)
 {
-    if (bytes <= e->rq_cap) return 0;
-    const size_t cap = std::max(bytes, 2 * e->rq_cap);
-    // (no launch reads the old staging: every call that used it waited for the stream)
-    if (e->h_rq) hipHostFree(e->h_rq);
-    if (e->d_rq) hipFree(e->d_rq);
-    e->h_rq = e->d_rq = nullptr;
-    e->rq_cap = 0;
-    if (hipHostMalloc((void**)&e->h_rq, cap) != hipSuccess || hipMalloc((void**)&e->d_rq, cap) != hipSuccess)
+    if (int rc = request_validate(e, r, 0)) return rc;   // host only: no device is touched yet
+    // the plan asks the rollout kernels' attributes of the current device: the engine's
+    DeviceGuard dg(e->device);
+    std::vector<ModelPlan> plans(1);
+    if (int rc = request_plan(e, r, plans[0])) return rc;
+    const size_t cap = e->rq_cap;
+    if (!reserve_stage(&e->h_rq, &e->d_rq, &e->rq_cap, request_stage_bytes(&e, 1, plans)))
         return fail(e, STOMP_E_DEVICE, "retarget staging allocation failed");
-    e->rq_cap = cap;
-    e->rq_allocs += 2;
-    return 0;
+    if (e->rq_cap != cap) e->rq_allocs += 2;
+    return request_engines(&e, 1, r, plans, e->h_rq, e->d_rq, nullptr, nullptr, false);
 }
 
 }  // namespace
@@ -345,16 +304,7 @@ extern "C" int stomp_engine_retarget_request(stomp_engine* e, const stomp_reques
     if (r->struct_size != (int32_t)sizeof(stomp_request))
         return fail(nullptr, STOMP_E_INVALID, "retarget: struct_size is not sizeof(stomp_request)");
     if (!r->start || !r->goal) return fail(nullptr, STOMP_E_INVALID, "retarget: null start or goal");
-    if (r->num_spheres == -1 && r->num_orientation_constraints == -1)   // the model kept: retarget's own launch
-        return stomp_engine_retarget(e, r->start, r->goal, r->seed);
-    // the plan asks the rollout kernels' attributes of the current device: the engine's.  A refusal
-    // writes nothing of the engine, not even its message (stomp_last_error has it), so the "inside
-    // its optimize loop" refusal may be made from another host thread than the loop's
-    DeviceGuard dg(e->device);
-    std::vector<ModelPlan> plans(1);
-    if (int rc = request_plan(e, r, 0, plans[0])) return rc;
-    if (int rc = reserve_request_stage(e, request_stage_bytes(&e, 1, plans))) return rc;
-    return request_engines(&e, 1, r, plans, e->h_rq, e->d_rq, nullptr, nullptr);
+    return retarget_engine(e, r);
 }
 
 extern "C" int stomp_engine_model_info(stomp_engine* e, int64_t info[12])
@@ -371,16 +321,8 @@ extern "C" int stomp_engine_retarget(stomp_engine* e, const double* start, const
 {
     if (!e) return fail(nullptr, STOMP_E_INVALID, "null engine");
     if (!start || !goal) return fail(nullptr, STOMP_E_INVALID, "retarget: null start or goal");   // (e not touched)
-    if (int rc = retarget_validate(&e, 1, start, goal)) {
-        e->err = g_last_error;
-        return rc;
-    }
-    DeviceGuard dg(e->device);
-    if (!e->d_rt) {
-        const size_t bytes = retarget_stage_bytes(1, e->J);
-        if (!e->h_rt && hipHostMalloc((void**)&e->h_rt, bytes) != hipSuccess)
-            return fail(e, STOMP_E_DEVICE, "hipHostMalloc failed");
-        if (int rc = dev_alloc(e, &e->d_rt, bytes)) return rc;
-    }
-    return retarget_engines(&e, 1, start, goal, &seed, e->h_rt, e->d_rt, nullptr);
+    const stomp_request r = kept_request(start, goal, seed);
+    const int rc = retarget_engine(e, &r);
+    if (rc) e->err = g_last_error;
+    return rc;
 }

@@ -90,7 +90,7 @@ __global__ void k_pad_fk(DevModel m, const double* start, const double* goal, do
 // by the 256 lanes of one workgroup, as compute_setup does (setup.cpp, setToMinControlCost): lin[c]
 // by lane c through LDS (lin: 256 doubles), both sums i-ascending, then theta[d][i] by lane i,
 // k-ascending, reading Rinv[i][k] itself (RinvT[k][i]: R^-1 is not bitwise symmetric)
-__device__ __forceinline__ void retarget_theta_row(const RetargetArgs& a, int d, int J, int N, double* lin)
+__device__ __forceinline__ void retarget_theta_row(const RequestArgs& a, int d, int J, int N, double* lin)
 {
     const int c = threadIdx.x;
     const double sd = a.stage[d], gd = a.stage[J + d];
@@ -118,7 +118,7 @@ __device__ __forceinline__ void retarget_theta_row(const RetargetArgs& a, int d,
 
 // the padding-collision flag of both sides, stored where the engine, a group's list and the call's
 // read-back keep it (col: the two sides' results in LDS, written before the barrier)
-__device__ __forceinline__ void retarget_store_flags(const RetargetArgs& a, const int* col)
+__device__ __forceinline__ void retarget_store_flags(const RequestArgs& a, const int* col)
 {
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -129,50 +129,29 @@ __device__ __forceinline__ void retarget_store_flags(const RetargetArgs& a, cons
     }
 }
 
-// stomp_engine_retarget / stomp_group_retarget (RetargetArgs): grid (J + 1, engines), N <= 256
-// lanes per workgroup.  Workgroup d < J makes joint d's row of theta_0 (retarget_theta_row).
-// Workgroup J is the padding FK on the new vectors in the staging buffer: the other workgroups of
-// the launch are writing start / goal meanwhile.
-__global__ __launch_bounds__(256) void k_retarget(const RetargetArgs* __restrict__ as, int J, int N)
-{
-    const RetargetArgs& a = as[blockIdx.y];
-    __shared__ double lin[256];
-    __shared__ int col[2];
-    if ((int)blockIdx.x == J) {
-        const int side = threadIdx.x;
-        if (side < 2) col[side] = pad_fk_side(a.model, a.stage + (size_t)side * J, side, a.pad_pos) ? 1 : 0;
-        retarget_store_flags(a, col);
-        return;
-    }
-    retarget_theta_row(a, blockIdx.x, J, N, lin);
-}
-
-void launch_retarget(const RetargetArgs* as, int engines, int J, int N, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_retarget, dim3(J + 1, engines), dim3(256), 0, s, as, J, N);
-}
-
-// stomp_engine_retarget_request / stomp_group_retarget_requests (RequestArgs, kernels.h): grid
-// (J + 2, engines).  Nothing in this launch reads the engine's image: a CU's vector L1 and the
-// scalar cache are not refreshed by the stores workgroup J + 1 makes from another CU.
-__global__ __launch_bounds__(256) void k_retarget_model(const RequestArgs* __restrict__ as, int J, int N)
+// The four retarget entry points (RequestArgs, kernels.h): grid (J + 1, engines) or (J + 2,
+// engines), N <= 256 lanes per workgroup.  Workgroup d < J makes joint d's row of theta_0
+// (retarget_theta_row).  Workgroup J is the padding FK on the new vectors in the staging buffer: the
+// other workgroups of the launch are writing start / goal meanwhile.  Nothing in this launch reads
+// an image that workgroup J + 1 writes: a CU's vector L1 and the scalar cache are not refreshed by
+// the stores it makes from another CU.
+__global__ __launch_bounds__(256) void k_retarget(const RequestArgs* __restrict__ as, int J, int N)
 {
     const RequestArgs& r = as[blockIdx.y];
-    const RetargetArgs& a = r.rt;
     __shared__ double lin[256];
     __shared__ int col[2];
     if ((int)blockIdx.x == J) {
-        // the new model's tables where the staging copy holds them: at the offsets they will have
-        // in the engine's image
-        const unsigned char* img = (const unsigned char*)a.model.img;
+        // the model's tables where stage_img holds them: at the offsets they have, or will have, in
+        // the engine's image
+        const unsigned char* img = (const unsigned char*)r.model.img;
         const unsigned char* st = (const unsigned char*)r.stage_img;
-        const FkOp* ops = (const FkOp*)(st + ((const unsigned char*)a.model.ops - img));
-        const DevSegment* segs = (const DevSegment*)(st + ((const unsigned char*)a.model.segs - img));
-        const DevSphere* sph = (const DevSphere*)(st + ((const unsigned char*)a.model.sph - img));
+        const FkOp* ops = (const FkOp*)(st + ((const unsigned char*)r.model.ops - img));
+        const DevSegment* segs = (const DevSegment*)(st + ((const unsigned char*)r.model.segs - img));
+        const DevSphere* sph = (const DevSphere*)(st + ((const unsigned char*)r.model.sph - img));
         const int side = threadIdx.x;
         if (side < 2)
-            col[side] = pad_fk_side_tab(a.model, ops, segs, sph, a.stage + (size_t)side * J, side, a.pad_pos) ? 1 : 0;
-        retarget_store_flags(a, col);
+            col[side] = pad_fk_side_tab(r.model, ops, segs, sph, r.stage + (size_t)side * J, side, r.pad_pos) ? 1 : 0;
+        retarget_store_flags(r, col);
         return;
     }
     if ((int)blockIdx.x == J + 1) {
@@ -180,7 +159,7 @@ __global__ __launch_bounds__(256) void k_retarget_model(const RequestArgs* __res
         for (int i = threadIdx.x; i < r.oc_words; i += 256) r.oc_out[i] = r.stage_oc[i];
         if (threadIdx.x == 0) *r.cs = 1;
         if (r.model_out) {
-            const unsigned long long* src = (const unsigned long long*)&a.model;
+            const unsigned long long* src = (const unsigned long long*)&r.model;
             unsigned long long* dst = (unsigned long long*)r.model_out;
             const int flag_word = (int)(offsetof(DevModel, pad_collision) / 8);
             for (int i = threadIdx.x; i < (int)(sizeof(DevModel) / 8); i += 256)
@@ -193,16 +172,23 @@ __global__ __launch_bounds__(256) void k_retarget_model(const RequestArgs* __res
         }
         return;
     }
-    retarget_theta_row(a, blockIdx.x, J, N, lin);
+    retarget_theta_row(r, blockIdx.x, J, N, lin);
 }
 
 static_assert(sizeof(DevModel) % 8 == 0 && sizeof(TermsModel) % 8 == 0 && offsetof(DevModel, pad_collision) % 8 == 0 &&
                   offsetof(DevModel, QT) == offsetof(DevModel, pad_collision) + 8,
-              "k_retarget_model copies the model entries by 8-byte words and skips pad_collision's");
+              "k_retarget copies the model entries by 8-byte words and skips pad_collision's");
 
-void launch_retarget_model(const RequestArgs* as, int engines, int J, int N, hipStream_t s)
+void launch_retarget(const RequestArgs* as, int engines, int J, int N, bool replaces, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_retarget_model, dim3(J + 2, engines), dim3(256), 0, s, as, J, N);
+    // The copy workgroup J + 1 is launched only when a request of the call replaces collision points
+    // or constraints (or a group's lists are behind its engines' models): for an engine that keeps
+    // both it copies no words and rewrites the group's entries with what they hold.  Without it
+    // `*cs = 1` is skipped too, which nothing can observe: d_cs is read only after a noiseless
+    // rollout (stomp_engine_iterate, k_track); with terms on k_terms writes it first, and with terms
+    // off it is 1 -- creation sets it, and the only way from on to off is a request that replaces the
+    // constraints, which launches the copy workgroup.
+    hipLaunchKernelGGL(k_retarget, dim3(J + (replaces ? 2 : 1), engines), dim3(256), 0, s, as, J, N);
 }
 
 __global__ void k_gather_max(const double* g, int world, int n, double* out)

@@ -469,13 +469,22 @@ void launch_update_group(int J, int N, const UpdateArgs* as, int engines, hipStr
 void launch_gather_max(const double* gathered, int world, int n, double* out, hipStream_t s);
 void launch_pad_fk(const DevModel& m, const double* start, const double* goal, double* pad_pos, int* pad_cf,
                    hipStream_t s);
-// A live engine put onto a new problem (stomp_engine_retarget / stomp_group_retarget): what
-// creation derives from the start and goal vectors, remade on the device.  One entry per engine in
-// device memory; engine p of the launch gets J workgroups for theta_0 (compute_setup's
-// setToMinControlCost, the same operations in the same order) and one for the padding rows' FK
-// (k_pad_fk's body on the engine's own model).
-struct RetargetArgs {
-    DevModel model;             // the engine's model (its tables and field; pad_collision not read)
+// A live engine put onto its next request (the four retarget entry points): what creation derives
+// from the start and goal vectors, remade on the device, and with a request that replaces its
+// collision points and / or its path constraints the new model too.  One entry per engine in device
+// memory.  Grid (J + 1, engines), or (J + 2, engines) when a request of the call replaces
+// something.  Workgroups d < J make theta_0 (compute_setup's setToMinControlCost, the same
+// operations in the same order).  Workgroup J runs the padding FK (k_pad_fk's body) of `model`,
+// reading its segment / sphere / FK-program tables through stage_img -- for a new model the call's
+// staging copy of the image, never the engine's image, which workgroup J + 1 is writing meanwhile;
+// for a kept one the engine's own image, which then no workgroup writes -- and writes the padding
+// positions and the flags.  Workgroup J + 1 copies the staged image tables [0, img_words) and the
+// staged constraint table into the engine's buffers, raises the constraints-satisfied flag of the
+// noiseless rollout to creation's 1 and, for a group, rewrites the engine's entries of the group's
+// model lists (every word but DevModel::pad_collision's, which is workgroup J's).
+struct RequestArgs {
+    DevModel model;             // the model the engine will hold (its table pointers into the engine's
+                                // image; pad_collision not read)
     const double* stage;        // [2][J] the new start, then the new goal (the call's staging buffer:
                                 // the padding FK reads them here, never start / goal below)
     const double* Rb;           // [12][N] rows 0..5 and N + 6..N + 11 of R, cut to the free columns
@@ -489,32 +498,20 @@ struct RetargetArgs {
     int* pad_cf;                // the engine's padding-collision flag (stored, not or-ed)
     int* model_flag;            // pad_collision of the engine's DevModel in a group's list, or null
     int* flag_out;              // the call's read-back slot of this engine
-};
-void launch_retarget(const RetargetArgs* as, int engines, int J, int N, hipStream_t s);
-// A live engine put onto a request that also replaces its collision points and / or its path
-// constraints (stomp_engine_retarget_request / stomp_group_retarget_requests).  Grid (J + 2,
-// engines): workgroups d < J make theta_0 as k_retarget's; workgroup J runs the padding FK of the
-// NEW model, reading its segment / sphere / FK-program tables from the call's staging copy of the
-// image (stage_img) -- never from the engine's image, which workgroup J + 1 is writing meanwhile --
-// and writes the padding positions (rt.pad_pos, in the engine's image) and the flags; workgroup
-// J + 1 copies the staged image tables [0, img_words) and the staged constraint table into the
-// engine's buffers, raises the constraints-satisfied flag of the noiseless rollout to creation's 1
-// and, for a group, rewrites the engine's entries of the group's model lists (every word but
-// DevModel::pad_collision's, which is workgroup J's).
-struct RequestArgs {
-    RetargetArgs rt;            // rt.model: the new model (its table pointers into the engine's image)
-    const unsigned long long* stage_img;   // the image's tables in the call's staging buffer
+    const unsigned long long* stage_img;   // the image's tables: the call's staging buffer, or the engine's image
     unsigned long long* img_out;           // the engine's image
-    int img_words;              // 8-byte words of the tables (everything before the padding positions)
-    int oc_words;               // 8-byte words of the constraint table (0: none)
+    int img_words;              // 8-byte words of the tables (everything before the padding positions; 0: kept)
+    int oc_words;               // 8-byte words of the constraint table (0: none, or kept)
     const unsigned long long* stage_oc;
     unsigned long long* oc_out; // the engine's constraint table (TermsModel::oc)
     uint8_t* cs;                // the noiseless rollout's constraints-satisfied flag
-    TermsModel terms;           // the new terms model
+    TermsModel terms;           // the terms model the engine will hold
     DevModel* model_out;        // the engine's entry of a group's DevModel list, or null
     TermsModel* terms_out;      // of its TermsModel list, or null
 };
-void launch_retarget_model(const RequestArgs* as, int engines, int J, int N, hipStream_t s);
+// replaces: a request of the call replaces collision points or constraints, or a group's lists are
+// behind its engines' models (the grid has workgroup J + 1)
+void launch_retarget(const RequestArgs* as, int engines, int J, int N, bool replaces, hipStream_t s);
 // src_*: the previous iteration's rows (ranked, copied from); params / noise / state: this
 // iteration's rows K_gen.. (written).  The two row sets must be distinct buffers (the copy has no
 // staging pass); returns -1 without launching when they alias, -2 when one candidate's cost rows

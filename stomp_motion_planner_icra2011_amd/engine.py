@@ -584,7 +584,8 @@ class Engine:
     def model_info(self) -> dict:
         """stomp_engine_model_info: the engine's current model (spheres, FK program steps, frame
         slots, saved frames, longest sphere run, the rollout layout's choices, constraints, terms),
-        the model changes so far and the allocations made inside retarget-request calls."""
+        the model changes so far and the allocations made inside retarget calls of either kind (the
+        call staging of the first one included; a repeated call allocates nothing)."""
         v = (C.c_int64 * 12)()
         _check(load_library().stomp_engine_model_info(self.h, v), self.h)
         return dict(zip(self.MODEL_INFO, [int(x) for x in v]))
@@ -798,22 +799,19 @@ class EngineGroup:
         sd = np.array([int(v) for v in seeds], np.uint64)
         if sd.shape != (n,):
             raise ValueError(f"seeds must hold {n} values")
-        if spheres is None and orientation_constraints is None:
-            self._check(load_library().stomp_group_retarget(self._h, _dp(s), _dp(g),
-                                                            sd.ctypes.data_as(C.POINTER(C.c_uint64))))
-            for p, e in enumerate(self.engines):
-                e._follow(s[p * J:(p + 1) * J], g[p * J:(p + 1) * J], int(sd[p]))
-            return
         sph = list(spheres) if spheres is not None else [None] * n
         ocs = list(orientation_constraints) if orientation_constraints is not None else [None] * n
         if len(sph) != n or len(ocs) != n:
             raise ValueError(f"spheres and orientation_constraints must hold {n} lists")
-        rows = [(s[p * J:(p + 1) * J].copy(), g[p * J:(p + 1) * J].copy()) for p in range(n)]
-        reqs, keep = (stomp_request * n)(), []
-        for p, e in enumerate(self.engines):
-            reqs[p], k = e._request(rows[p][0], rows[p][1], int(sd[p]), sph[p], ocs[p])
-            keep.append(k)
-        self._check(load_library().stomp_group_retarget_requests(self._h, reqs))
+        rows = [(s[p * J:(p + 1) * J], g[p * J:(p + 1) * J]) for p in range(n)]   # (views: s and g outlive the call)
+        reqs, keep = (stomp_request * n)(), [(None, None)] * n
+        if spheres is None and orientation_constraints is None:
+            self._check(load_library().stomp_group_retarget(self._h, _dp(s), _dp(g),
+                                                            sd.ctypes.data_as(C.POINTER(C.c_uint64))))
+        else:
+            for p, e in enumerate(self.engines):
+                reqs[p], keep[p] = e._request(rows[p][0], rows[p][1], int(sd[p]), sph[p], ocs[p])
+            self._check(load_library().stomp_group_retarget_requests(self._h, reqs))
         for p, e in enumerate(self.engines):
             e._follow(rows[p][0], rows[p][1], int(sd[p]), sph[p], ocs[p], keep[p])
 

@@ -240,13 +240,60 @@ void StompOptimizer::followRetarget(const std::vector<double>& start, const std:
     last_cs_ = true;
 }
 
-bool StompOptimizer::retarget(const std::vector<double>& start, const std::vector<double>& goal, uint64_t seed)
+namespace {
+
+// the size rule of every retarget: false with the reason, in `who`'s name, in `error`
+bool retargetSizes(const char* who, const std::vector<double>& start, const std::vector<double>& goal, int J,
+                   std::string& error)
 {
-    if (!engine_) return false;
-    if ((int)start.size() != J_ || (int)goal.size() != J_) {
-        error_ = "retarget: start and goal must have num_joints entries";
+    if ((int)start.size() == J && (int)goal.size() == J) return true;
+    error = std::string(who) + ": start and goal must have num_joints entries";
+    return false;
+}
+
+// What the two retargetBatch overloads share: the size checks (one_each: the overload's own count
+// rule, with its text), the optimizers' engines as the group optimizeBatch makes, `call` on that
+// group, the failure's reason into `error` (the first optimizer's) and, after a call that
+// succeeded, follow(p) for every optimizer.
+template <class Call, class Follow>
+bool retargetGroup(const std::vector<StompOptimizer*>& optimizers, const std::vector<std::vector<double>>& starts,
+                   const std::vector<std::vector<double>>& goals, bool one_each, const char* one_each_text,
+                   std::string& error, Call call, Follow follow)
+{
+    if (!one_each) {
+        error = one_each_text;
         return false;
     }
+    const size_t P = optimizers.size();
+    std::vector<stomp_engine*> engines;
+    for (size_t p = 0; p < P; ++p) {
+        StompOptimizer* o = optimizers[p];
+        if (!o || !o->engine()) {
+            error = "retargetBatch: an optimizer without an engine";
+            return false;
+        }
+        if (!retargetSizes("retargetBatch", starts[p], goals[p], o->numJoints(), error)) return false;
+        engines.push_back(o->engine());
+    }
+    stomp_group* grp = nullptr;
+    if (stomp_group_create_flags(engines.data(), (int32_t)P, STOMP_GROUP_ACCEPT_STATE_TERMS | STOMP_GROUP_ACCEPT_CUMULATIVE,
+                                 -1, &grp) != 0) {
+        error = stomp_last_error();
+        return false;
+    }
+    const int rc = call(grp);
+    if (rc != 0) error = stomp_group_last_error(grp);
+    stomp_group_destroy(grp);
+    if (rc != 0) return false;
+    for (size_t p = 0; p < P; ++p) follow(p);
+    return true;
+}
+
+}  // namespace
+
+bool StompOptimizer::retarget(const std::vector<double>& start, const std::vector<double>& goal, uint64_t seed)
+{
+    if (!engine_ || !retargetSizes("retarget", start, goal, J_, error_)) return false;
     if (!check(stomp_engine_retarget(engine_, start.data(), goal.data(), seed))) return false;
     followRetarget(start, goal, seed);
     return true;
@@ -260,38 +307,18 @@ bool StompOptimizer::retargetBatch(const std::vector<StompOptimizer*>& optimizer
     StompOptimizer* first = optimizers[0];
     if (!first) return false;
     const size_t P = optimizers.size();
-    if (starts.size() != P || goals.size() != P || seeds.size() != P) {
-        first->error_ = "retargetBatch: one start, goal and seed per optimizer";
-        return false;
-    }
-    std::vector<stomp_engine*> engines;
-    std::vector<double> s, g;
-    for (size_t p = 0; p < P; ++p) {
-        StompOptimizer* o = optimizers[p];
-        if (!o || !o->engine_) {
-            first->error_ = "retargetBatch: an optimizer without an engine";
-            return false;
-        }
-        if ((int)starts[p].size() != o->J_ || (int)goals[p].size() != o->J_) {
-            first->error_ = "retargetBatch: start and goal must have num_joints entries";
-            return false;
-        }
-        engines.push_back(o->engine_);
-        s.insert(s.end(), starts[p].begin(), starts[p].end());
-        g.insert(g.end(), goals[p].begin(), goals[p].end());
-    }
-    stomp_group* grp = nullptr;
-    if (stomp_group_create_flags(engines.data(), (int32_t)P, STOMP_GROUP_ACCEPT_STATE_TERMS | STOMP_GROUP_ACCEPT_CUMULATIVE,
-                                 -1, &grp) != 0) {
-        first->error_ = stomp_last_error();
-        return false;
-    }
-    const int rc = stomp_group_retarget(grp, s.data(), g.data(), seeds.data());
-    if (rc != 0) first->error_ = stomp_group_last_error(grp);
-    stomp_group_destroy(grp);
-    if (rc != 0) return false;
-    for (size_t p = 0; p < P; ++p) optimizers[p]->followRetarget(starts[p], goals[p], seeds[p]);
-    return true;
+    return retargetGroup(
+        optimizers, starts, goals, starts.size() == P && goals.size() == P && seeds.size() == P,
+        "retargetBatch: one start, goal and seed per optimizer", first->error_,
+        [&](stomp_group* grp) {
+            std::vector<double> s, g;
+            for (size_t p = 0; p < P; ++p) {
+                s.insert(s.end(), starts[p].begin(), starts[p].end());
+                g.insert(g.end(), goals[p].begin(), goals[p].end());
+            }
+            return stomp_group_retarget(grp, s.data(), g.data(), seeds.data());
+        },
+        [&](size_t p) { optimizers[p]->followRetarget(starts[p], goals[p], seeds[p]); });
 }
 
 // the optimizer's own copies of the collision points and the constraints (createSibling reads
@@ -330,11 +357,7 @@ stomp_request StompOptimizer::request(const std::vector<double>& start, const st
 bool StompOptimizer::retarget(const std::vector<double>& start, const std::vector<double>& goal, uint64_t seed,
                               const std::vector<stomp_sphere>* collision_points, const Constraints* constraints)
 {
-    if (!engine_) return false;
-    if ((int)start.size() != J_ || (int)goal.size() != J_) {
-        error_ = "retarget: start and goal must have num_joints entries";
-        return false;
-    }
+    if (!engine_ || !retargetSizes("retarget", start, goal, J_, error_)) return false;
     const stomp_request r = request(start, goal, seed, collision_points, constraints);
     if (!check(stomp_engine_retarget_request(engine_, &r))) return false;
     followRetarget(start, goal, seed);
@@ -352,41 +375,21 @@ bool StompOptimizer::retargetBatch(const std::vector<StompOptimizer*>& optimizer
     StompOptimizer* first = optimizers[0];
     if (!first) return false;
     const size_t P = optimizers.size();
-    if (starts.size() != P || goals.size() != P || seeds.size() != P || collision_points.size() != P ||
-        constraints.size() != P) {
-        first->error_ = "retargetBatch: one start, goal, seed, collision point list and constraints per optimizer";
-        return false;
-    }
-    std::vector<stomp_engine*> engines;
-    std::vector<stomp_request> rs;
-    for (size_t p = 0; p < P; ++p) {
-        StompOptimizer* o = optimizers[p];
-        if (!o || !o->engine_) {
-            first->error_ = "retargetBatch: an optimizer without an engine";
-            return false;
-        }
-        if ((int)starts[p].size() != o->J_ || (int)goals[p].size() != o->J_) {
-            first->error_ = "retargetBatch: start and goal must have num_joints entries";
-            return false;
-        }
-        engines.push_back(o->engine_);
-        rs.push_back(o->request(starts[p], goals[p], seeds[p], collision_points[p], constraints[p]));
-    }
-    stomp_group* grp = nullptr;
-    if (stomp_group_create_flags(engines.data(), (int32_t)P, STOMP_GROUP_ACCEPT_STATE_TERMS | STOMP_GROUP_ACCEPT_CUMULATIVE,
-                                 -1, &grp) != 0) {
-        first->error_ = stomp_last_error();
-        return false;
-    }
-    const int rc = stomp_group_retarget_requests(grp, rs.data());
-    if (rc != 0) first->error_ = stomp_group_last_error(grp);
-    stomp_group_destroy(grp);
-    if (rc != 0) return false;
-    for (size_t p = 0; p < P; ++p) {
-        optimizers[p]->followRetarget(starts[p], goals[p], seeds[p]);
-        optimizers[p]->followModel(collision_points[p], constraints[p]);
-    }
-    return true;
+    return retargetGroup(
+        optimizers, starts, goals,
+        starts.size() == P && goals.size() == P && seeds.size() == P && collision_points.size() == P &&
+            constraints.size() == P,
+        "retargetBatch: one start, goal, seed, collision point list and constraints per optimizer", first->error_,
+        [&](stomp_group* grp) {
+            std::vector<stomp_request> rs;
+            for (size_t p = 0; p < P; ++p)
+                rs.push_back(optimizers[p]->request(starts[p], goals[p], seeds[p], collision_points[p], constraints[p]));
+            return stomp_group_retarget_requests(grp, rs.data());
+        },
+        [&](size_t p) {
+            optimizers[p]->followRetarget(starts[p], goals[p], seeds[p]);
+            optimizers[p]->followModel(collision_points[p], constraints[p]);
+        });
 }
 
 bool StompOptimizer::initialize(int num_time_steps)

@@ -15,7 +15,7 @@ from oracle import pyoracle as po
 from tests import model_zoo as mz
 from tests.group_util import CHUNKS, INT_STATS, Group, assert_same
 from tests.test_gpu_retarget import SHORT, created, moved, rows
-from tests.test_gpu_request_model import assert_edit_matters, attach, model, snapshot
+from tests.test_gpu_request_model import assert_edit_matters, attach, model, small, small_constraint, snapshot
 
 pytestmark = pytest.mark.gpu
 
@@ -179,4 +179,43 @@ def test_an_engine_remodelled_on_its_own_makes_the_group_stale():
         o.iterate(1)
         o.iterate(2)
         assert_same(rows(e, True), rows(o, True), f"engine {i}")
+    g.close()
+
+
+def test_plain_mixed_and_all_kept_calls_in_turn():
+    # one path behind both group calls: plain; a requests call in which engine 1 alone replaces its
+    # path constraints (the spheres stay: one shape) and engines 0 and 2 keep everything; plain; a
+    # requests call in which every request keeps both lists, through stomp_group_retarget_requests
+    # itself; the same once more after engine 0 took a constraint on its own, which leaves the
+    # group's lists behind it (that call alone rewrites them).  After each: every engine is its fresh
+    # twin, and two grouped iterations are each engine's own two.
+    base = small()
+    ps = [moved(base, 90 + i) for i in range(P)]
+    g = Group(ps, state_terms=True)
+    c = [small_constraint()]
+    all_kept = dict(spheres=[None] * P)
+    # (what is done, the engine re-modelled on its own first, the group call's lists, the constraints held after, model_changes)
+    steps = [("plain", None, {}, [[], [], []], [0, 0, 0]),
+             ("engine 1 replaces its constraints", None, dict(orientation_constraints=[None, c, None]), [[], c, []], [0, 1, 0]),
+             ("plain again", None, {}, [[], c, []], [0, 1, 0]),
+             ("every request keeps both lists", None, all_kept, [[], c, []], [0, 1, 0]),
+             ("every request keeps both lists, the group behind engine 0", 0, all_kept, [c, c, []], [1, 1, 0])]
+    for k, (tag, own, lists, held, changes) in enumerate(steps):
+        qs = [dataclasses.replace(moved(base, 100 + 10 * k + i), orientation_constraints=list(held[i])) for i in range(P)]
+        if own is not None:
+            g.engines[own].retarget(ps[own].start, ps[own].goal, orientation_constraints=held[own])
+        g.group.retarget([q.start for q in qs], [q.goal for q in qs], [q.seed for q in qs], **lists)
+        twins = [eng.Engine(q) for q in qs]
+        for i, (e, t, q) in enumerate(zip(g.engines, twins, qs)):
+            assert e.problem.seed == q.seed and len(e.problem.orientation_constraints) == len(held[i])
+            assert model(e) == model(t), (tag, i)
+            assert_same(created(e), created(t), f"{tag}: engine {i} created")
+        assert [e.model_info()["model_changes"] for e in g.engines] == changes, tag
+        g.group.run(1, 2)
+        g.group.synchronize()
+        for i, (e, t) in enumerate(zip(g.engines, twins)):
+            t.run(1, 2)
+            t.synchronize()
+            assert_same(rows(e, True), rows(t, True), f"{tag}: engine {i} after two iterations")
+            t.close()
     g.close()

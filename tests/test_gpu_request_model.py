@@ -10,6 +10,7 @@ Every sphere-edit case first asserts, on the oracle alone, that the edit changes
 iteration 1: a call that silently kept the old spheres cannot pass.
 
 Without the feature Engine.retarget takes no spheres and Engine has no model_info: every case fails."""
+import ctypes as C
 import dataclasses
 import functools
 
@@ -439,3 +440,150 @@ def test_a_repeated_request_allocates_nothing():
     e.retarget(p.start, p.goal, p.seed)
     assert e.model_info()["model_changes"] == 3
     e.close()
+
+
+# ------------------------------------------------------------------------------------------------
+# 7. one staging behind every retarget, in any order
+
+def small(Kr=3, **kw):
+    """the zoo's smallest robot at K = 8, N = 20, on a 32^3 field"""
+    return mz.stick1(K=8, Kr=Kr, waypoints=21, shape=(32, 32, 32), **kw)
+
+
+def small_constraint():
+    return mz.random_constraint(np.random.default_rng(1101), "wand_tip", False, (0.5, 0.4, 0.3))
+
+
+def counts(e):
+    info = e.model_info()
+    return info["model_changes"], info["request_allocations"]
+
+
+def test_one_staging_in_any_order():
+    # the first retarget ever is a plain one: the staging is sized for a kept model, so the request
+    # after it has to grow the staging and the model buffers; then plain and the request again
+    p = small()
+    e = eng.Engine(p)
+    assert p.N == 20 and counts(e) == (0, 0)
+    q1 = moved(p, 81)
+    e.retarget(q1.start, q1.goal, q1.seed)
+    assert_created(e, q1, "plain, the first call")
+    changes, allocs = counts(e)
+    assert changes == 0 and allocs >= 1          # (the staging)
+    q2 = edited(p, 82, attach(p), [small_constraint()])
+    assert_edit_matters(q2, p.spheres)
+    request_to(e, q2)
+    assert_created(e, q2, "request")
+    grown = counts(e)
+    assert grown[0] == 1 and grown[1] > allocs, (grown, allocs)
+    q3 = moved(q2, 83)                   # plain: the attached sphere and the constraint are kept
+    e.retarget(q3.start, q3.goal, q3.seed)
+    assert_created(e, q3, "plain, after the request")
+    assert counts(e) == grown
+    request_to(e, q2)
+    assert_created(e, q2, "the request again")
+    assert counts(e) == (2, grown[1])
+    e.close()
+
+
+# ------------------------------------------------------------------------------------------------
+# 8. one validator behind both engine entry points: the refusals of 5. and of
+# tests/test_gpu_retarget.py, each through stomp_engine_retarget and through
+# stomp_engine_retarget_request with both lists kept -- the same code and text, the engine untouched,
+# and each entry point's own error sink (the engine's last error after stomp_engine_retarget; the
+# calling thread's alone after stomp_engine_retarget_request)
+
+ENTRIES = ["stomp_engine_retarget", "stomp_engine_retarget_request"]
+
+
+def engine_error(e):
+    return eng.load_library().stomp_engine_last_error(e.h).decode()
+
+
+def call_entry(e, entry, start, goal, seed):
+    """(code, the calling thread's last error) of one call of the C entry point itself"""
+    lib = eng.load_library()
+    s, g = np.ascontiguousarray(start, np.float64), np.ascontiguousarray(goal, np.float64)
+    if entry == "stomp_engine_retarget":
+        rc = lib.stomp_engine_retarget(e.h, eng._dp(s), eng._dp(g), C.c_uint64(seed))
+    else:
+        req, _ = e._request(s, g, seed, None, None)
+        assert req.num_spheres == -1 and req.num_orientation_constraints == -1
+        rc = lib.stomp_engine_retarget_request(e.h, C.byref(req))
+    return rc, lib.stomp_last_error().decode()
+
+
+def assert_refusal(e, entry, result, code, text, error_before):
+    rc, thread_error = result
+    assert rc == code and text in thread_error, (entry, rc, thread_error)
+    if entry == "stomp_engine_retarget":
+        assert engine_error(e) == thread_error
+    else:
+        assert engine_error(e) == error_before and text not in error_before
+
+
+def goal_not_finite(entry):
+    p = small()
+    e, o = eng.Engine(p), po.Oracle(p)
+    e.iterate(1)
+    o.iterate(1)
+    before, error_before = snapshot(e), engine_error(e)
+    goal = p.goal.copy()
+    goal[0] = np.nan
+    result = call_entry(e, entry, p.start, goal, p.seed)
+    assert_refusal(e, entry, result, -1, "not finite", error_before)
+    assert "engine 0, joint 0" in result[1], result[1]      # the one message names both
+    assert_same(snapshot(e), before, "after the refusal")
+    assert e.iterate(2) == o.iterate(2)            # its iteration state is untouched too
+    assert_same(rows(e, True), rows(o, True), "iteration 2 after the refusal")
+    e.close()
+
+
+def inside_optimize(entry):
+    # A second host thread calls while stomp_engine_optimize runs.  A request that keeps both lists
+    # is accepted outside the loop, so the thread first probes with a request that is refused
+    # wherever it lands (its sphere list is not ordered by segment: -3 outside the loop, -1 inside)
+    # and writes nothing; after the first probe that met the loop it makes the call under test,
+    # once -- within the loop's first few of 1500 iterations.
+    import threading
+    p = small(Kr=0, max_iterations=1500, max_iterations_after_collision_free=1500)
+    bad = attach(p)[::-1]
+    e, twin = eng.Engine(p), eng.Engine(p)
+    error_before = engine_error(e)
+    seen, result, stop = [], [], threading.Event()
+
+    def caller():
+        while not stop.is_set():
+            try:
+                e.retarget(p.start, p.goal, p.seed, spheres=bad)
+                seen.append("accepted")
+            except RuntimeError as err:
+                seen.append("inside" if "error -1" in str(err) and "inside its optimize loop" in str(err) else
+                            "outside" if "error -3" in str(err) and "ordered by segment" in str(err) else str(err))
+            if seen[-1] != "outside":
+                break
+        if seen[-1] == "inside":
+            result.append(call_entry(e, entry, p.start, p.goal, p.seed))
+
+    t = threading.Thread(target=caller)
+    t.start()
+    try:
+        while not seen:             # the caller is up and probing before the loop starts
+            pass
+        assert seen[0] == "outside"
+        snap = optimize_snapshot(e)
+    finally:
+        stop.set()
+        t.join()
+    assert set(seen) == {"inside", "outside"} and len(result) == 1, sorted(set(seen))
+    assert_refusal(e, entry, result[0], -1, "inside its optimize loop", error_before)
+    assert snap["stats"][0] == 1500 and e.problem is p and e.model_info()["model_changes"] == 0
+    assert_same(snap, optimize_snapshot(twin), "the loop the refused call ran beside")
+    twin.close()
+    e.close()
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+@pytest.mark.parametrize("case", [goal_not_finite, inside_optimize])
+def test_one_validator(case, entry):
+    case(entry)
