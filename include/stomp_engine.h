@@ -637,6 +637,55 @@ int stomp_group_retarget(stomp_group* g, const double* starts, const double* goa
  * STOMP_E_INVALID naming the engine and touches nothing, until stomp_group_retarget_requests has
  * brought the group back in step. */
 int stomp_group_retarget_requests(stomp_group* g, const stomp_request* requests /* P */);
+/* A queue of requests served by the group's P engines as slots: a slot whose request has stopped
+ * takes the next waiting request instead of idling until the slowest problem of a batch ends.
+ * A request is a plain retarget: a start, a goal and a seed (row r of starts / goals, seeds[r]).
+ * The model, the field and every parameter are the slot's own as they stand.  A request that
+ * replaces collision points or constraints, or a scene update between requests, stays with
+ * stomp_group_retarget_requests + stomp_group_optimize.
+ * Assignment: requests are handed out in index order.  Requests 0 .. min(P, n) - 1 go to slots
+ * 0, 1, .. in one retarget launch and run their iteration 1 in group step 1.  The host reads the
+ * slots' stop flags once per chunk of STOMP_GROUP_OPTIMIZE_CHUNK steps, one chunk behind the one it
+ * enqueues (as stomp_group_optimize does); each time it learns that slots have stopped, the free
+ * slots take the next waiting requests in ascending slot order, and the requests' iteration 1 runs
+ * in the first step of the next chunk staged.  While requests wait every chunk has
+ * STOMP_GROUP_OPTIMIZE_CHUNK steps (a step in which no slot has work launches nothing).  These
+ * decisions depend on P, the chunk size and the requests' iteration counts alone, never on
+ * timing: stomp_serve_schedule is the same decision procedure as a host-only function and returns,
+ * for given iteration counts, the slots and start steps the loop produces (total_steps: the step in
+ * which the last request stops, start_step + iterations at most).  With n < P the slots >= n are
+ * neither retargeted nor launched.
+ * Results, for request r planned by slot s: results[r].stats but for the two durations (which
+ * count from the slot's own start stamp), best_trajectories[r] and
+ * costs_per_iteration[r][0 .. iterations) are bit for bit what stomp_engine_retarget(e_s, start_r,
+ * goal_r, seed_r) followed by stomp_engine_optimize(e_s, ..) gives.  Afterwards every used engine is
+ * where the retarget to the last request it planned followed by its own stomp_engine_optimize
+ * leaves it (stomp_group_optimize's post-conditions).  Per-request torque statistics are not
+ * available: the engine's best-trajectory buffer has moved on when a later request runs.
+ * Refused before any engine or device is touched: a NULL group, starts, goals, seeds, results or
+ * best_trajectories, num_requests <= 0, a value that is not finite (the message names the
+ * request), a costs_stride below the largest max_iterations when costs_per_iteration is given, an
+ * engine inside its own optimize loop, an engine without iterations to run (max_iterations <= 0),
+ * a stale model epoch (STOMP_E_INVALID each); sharded engines (STOMP_E_UNSUPPORTED).
+ * stomp_group_serve_info, about the last call: [0] group steps run (up to the one in which the last
+ * request stopped), [1] the requests' iterations summed (occupied slot-steps), [2] turnovers
+ * (requests that did not start in step 1), [3] steps in which two live slots ran different
+ * iteration numbers, [4] the largest idle gap in steps between a slot's stop and its next
+ * request's iteration 1, [5] kernel launches enqueued, [6] device bytes held for results,
+ * [7] allocations made by the call. */
+typedef struct stomp_serve_result {
+    int32_t slot;        /* index in the group of the engine that planned the request */
+    int32_t start_step;  /* 1-based group step whose rollout launch ran the request's iteration 1 */
+    stomp_stats stats;   /* durations from the slot's own start stamp, device wall clock */
+} stomp_serve_result;
+int stomp_group_serve(stomp_group* g, const double* starts /* [n][J] */, const double* goals /* [n][J] */,
+                      const uint64_t* seeds /* [n] */, int32_t num_requests,
+                      stomp_serve_result* results /* [n] */, double* best_trajectories /* [n][J][N] */,
+                      double* costs_per_iteration /* NULL or [n][costs_stride] */, int32_t costs_stride);
+int stomp_group_serve_info(stomp_group* g, int64_t info[8]);
+/* iterations: [n], each >= 1; slot, start_step: [n] out; total_steps: out or NULL */
+int stomp_serve_schedule(int32_t num_slots, int32_t num_requests, const int32_t* iterations /* [n] */,
+                         int32_t* slot /* [n] */, int32_t* start_step /* [n] */, int32_t* total_steps);
 const char* stomp_group_last_error(const stomp_group* g);
 void stomp_group_destroy(stomp_group* g);
 

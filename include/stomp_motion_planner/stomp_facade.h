@@ -462,6 +462,30 @@ public:
                               const std::vector<std::vector<double>>& goals, const std::vector<uint64_t>& seeds,
                               const std::vector<const std::vector<stomp_sphere>*>& collision_points,
                               const std::vector<const Constraints*>& constraints);
+    // A queue of planning requests (starts[r], goals[r], seeds[r]) served by the optimizers as
+    // slots (stomp_group_serve; the group obtained as optimizeBatch obtains it): requests are handed
+    // out in index order, and an optimizer whose request has stopped takes the next waiting one
+    // instead of idling until the slowest problem of a batch ends.  A request is a plain retarget:
+    // the collision points, the path constraints and every parameter are the planning optimizer's
+    // own (a request that replaces them stays with retargetBatch + optimizeBatch).  results[r]: the
+    // slot (index into optimizers) that planned request r, the group step of its first iteration,
+    // its statistics and its best trajectory (free waypoints, per joint), each what retarget(request
+    // r) + optimize() of that optimizer gives -- without the torques: the engine's best-trajectory
+    // buffer has moved on when a later request runs, so per-request torque statistics are out of
+    // scope (results[r].stats.torques is empty).  Afterwards every optimizer that planned a request
+    // is as after retarget(the last request it planned) + optimize(), torques included; with fewer
+    // requests than optimizers the others are untouched.  On failure returns false with the reason
+    // in the first optimizer's lastError(), and nothing is changed.
+    struct ServeResult {
+        int slot = -1;
+        int start_step = 0;
+        STOMPStatistics stats;
+        std::vector<VectorXd> best_trajectory;   // [num_joints] of num_time_steps
+    };
+    static bool serveBatch(const std::vector<StompOptimizer*>& optimizers,
+                           const std::vector<std::vector<double>>& starts,
+                           const std::vector<std::vector<double>>& goals, const std::vector<uint64_t>& seeds,
+                           std::vector<ServeResult>& results);
     const STOMPStatistics& getStatistics() const { return stats_; }
 
     // Task (stomp_optimizer.cpp:1063-1165, 1167-1182)

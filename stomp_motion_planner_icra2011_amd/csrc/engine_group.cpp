@@ -23,54 +23,18 @@
 // request in one launch and one read-back (group_retarget, over engine_retarget.cpp); the launch
 // also writes the padding-collision flags of the group's own DevModel list, which the grouped
 // launches of a run and a synchronize read, and rewrites the entries of a replaced model.
-#include "engine_internal.h"
+// The engines of a step need not be at one iteration: stage_step takes the iteration per engine, a
+// StepLaunch carries the largest counts and the kernels take an engine's own from its arguments.
+// stomp_group_run and stomp_group_optimize stage equal iterations; stomp_group_serve
+// (engine_serve.cpp) runs the optimize loop's stages (engine_group.h) with every slot at its own.
+#include "engine_group.h"
 
 #include <algorithm>
 #include <optional>
 
 using namespace stomp;
 
-struct stomp_group {
-    std::vector<stomp_engine*> e;
-    std::vector<int> all;                 // 0 .. P - 1: the engines of a run's step and of a synchronize's flush
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int nt = 0;                           // weights tiles per engine
-    NoiseArgs shape{};                    // J, N, Nall of the reuse launches
-    DevModel* d_models = nullptr;         // [P]
-    bool state_terms = false;             // engines with terms accepted (stomp_group_create_with)
-    TermsModel* d_tmodels = nullptr;      // [P] every engine's terms model (state_terms)
-    int nterms = 0;                       // engines with terms
-    int ncum = 0;                         // engines with cumulative costs (stomp_group_create_flags)
-    size_t terms_lds = 0;                 // the largest terms_lds_bytes among them: k_terms_group's dynamic LDS
-    // stomp_group_run / stomp_group_synchronize: one run's arguments, a take_step per iteration
-    unsigned char* d_args = nullptr;
-    size_t d_cap = 0;
-    unsigned char* h_args = nullptr;      // pinned staging of one run's arguments
-    size_t h_cap = 0;
-    hipEvent_t staged = nullptr;          // the last upload from h_args is done
-    // stomp_group_optimize: two slots of one chunk's arguments each (pinned and device), the
-    // engines' (stop, iterations) mirror with a pinned read-back per slot, all P track arguments
-    bool compact = false;                 // stopped engines leave the launches (STOMP_DEBUG_GROUP_COMPACT=1 / 0)
-    unsigned char *h_opt = nullptr, *d_opt = nullptr;
-    size_t opt_slot = 0;                  // bytes per slot
-    int* d_mirror = nullptr;              // [P][2]
-    int* h_mirror = nullptr;              // [2][P][2]
-    TrackArgs* d_track_all = nullptr;     // [P]
-    hipEvent_t opt_ev[2] = {nullptr, nullptr};
-    // the retarget calls: one call's staging (pinned and device), held with a capacity; the
-    // padding-collision flag each entry of d_models holds, so that an engine retargeted on its own
-    // (stomp_engine_retarget knows no group) gets its entry refreshed before the next launch that
-    // reads the list; the model epoch of every engine the group's lists were made from (an engine
-    // whose model was replaced on its own since then leaves them stale: check_epochs)
-    unsigned char *h_rq = nullptr, *d_rq = nullptr;
-    size_t rq_cap = 0;
-    std::vector<int> pad_flags;
-    std::vector<long long> epochs;
-    std::string err;
-};
-
-namespace {
+namespace stomp {
 int gfail(stomp_group* g, int code, const char* msg)
 {
     g_last_error = msg;
@@ -78,109 +42,82 @@ int gfail(stomp_group* g, int code, const char* msg)
     return code;
 }
 
+namespace {
 // the group's buffers are made with hipMalloc / hipHostMalloc and freed here, pointer reset
 template <class... T>
 void free_device(T*&... p) { ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...); }
 template <class... T>
 void free_pinned(T*&... p) { ((p ? (void)hipHostFree(p) : (void)0, p = nullptr), ...); }
-
-// A bump allocator over a staging buffer, `cap` bytes pinned at `h` and on the device at `d`:
-// take(n, dev) hands out the next array of n T at a 256-byte aligned offset of both, the host side
-// returned, the device side in `dev`.  The caller checks overflowed() before it fills.  With no
-// buffers it only measures: used() after the takes is the capacity they need.
-struct Arena {
-    unsigned char *h = nullptr, *d = nullptr;
-    size_t cap = ~(size_t)0, off = 0;
-    template <class T>
-    T* take(size_t n, const T*& dev)
-    {
-        const size_t o = off;
-        off += align256(sizeof(T) * n);
-        dev = d ? (const T*)(d + o) : nullptr;
-        return h ? (T*)(h + o) : nullptr;
-    }
-    size_t used() const { return off; }
-    bool overflowed() const { return off > cap; }
-};
-
-// the DevModel and TermsModel lists of a launch: the group's own over all P engines, or staged ones
-struct ModelLists {
-    const DevModel* models = nullptr;
-    const TermsModel* tmodels = nullptr;
-    int nx = 0;   // engines with terms among the launch's (0: no terms launch)
-};
-
-// One grouped step: what launch_step needs and nothing else, device pointers and counts.
-struct StepLaunch {
-    // the engines that run the iteration: rollouts, weights, update
-    const CostArgs* cas = nullptr; const WeightArgs* was = nullptr; const UpdateArgs* uas = nullptr;
-    const ReuseRowArgs* ras = nullptr; const TermsArgs* xas = nullptr;
-    ModelLists lists;
-    int nm = 0, nro = 0, ntot = 0;   // engines; rollout workgroups and totals blocks of each
-    bool reuse = false;
-    // the flush cohort: engines whose pending noiseless rollout alone is evaluated
-    const CostArgs* ccs = nullptr; const TermsArgs* cxas = nullptr;
-    ModelLists clists;
-    int nc = 0;
-    bool time_flush = true;          // the cohort's rollout launch is recorded on T_NOISELESS
-    // k_track_group over both sets ([nm + nc]); track_it < 0: no launch
-    const TrackArgs* tas = nullptr;
-    int track_it = -1;
-};
+}  // namespace
 
 // The launches of one grouped step, in the order everything depends on.  With timing on for the
 // group's first engine, its timers hold the group's launches.
-void launch_step(stomp_group* g, const StepLaunch& L)
+int launch_step(stomp_group* g, const StepLaunch& L)
 {
     stomp_engine* e0 = g->e[0];
     hipStream_t s = g->stream;
     const int J = e0->J, N = e0->N, K = e0->K_loc;
     const DevModel& shape = e0->model;   // the engines of a group have one shape and one field layout
+    int n = 0;
     if (L.nc > 0) {
         // every cohort engine's pending noiseless rollout in one launch (one workgroup per engine)
         std::optional<Timed> tm;
         if (L.time_flush) tm.emplace(e0, T_NOISELESS, s);
         launch_cost_group(shape, L.clists.models, L.ccs, L.nc, 1, 0, s);
+        ++n;
     }
     if (L.nc > 0 && L.clists.nx > 0) {
         Timed tm(e0, T_TERMS, s);
         launch_terms_group(L.clists.tmodels, L.cxas, L.nc, 1, N, g->terms_lds, s);
+        ++n;
     }
     if (L.nm > 0) {
+        // (the grid by the step's largest counts; an engine's block roles are its own CostArgs')
         Timed tm(e0, T_COST, s);
         launch_cost_group(shape, L.lists.models, L.cas, L.nm, L.nro, K + L.ntot, s);
+        ++n;
     }
     if (L.nm > 0 && L.lists.nx > 0) {
         // the state-cost terms of both rollout launches before the bookkeeping reads the noiseless
         // rollouts' totals and constraints-satisfied flags, the reuse ranking and the weights the rows
         Timed tm(e0, T_TERMS, s);
         launch_terms_group(L.lists.tmodels, L.xas, L.nm, L.nro, N, g->terms_lds, s);
+        ++n;
     }
     // before this step's weights / update: a break decided on the previous iteration's noiseless
     // rollout leaves theta where the reference leaves it
-    if (L.track_it >= 0) launch_track_group(L.tas, L.nm + L.nc, L.track_it, J * N, s);
-    if (L.nm <= 0) return;
+    if (L.ntrack > 0) {
+        launch_track_group(L.tas, L.ntrack, -1, J * N, s);
+        ++n;
+    }
+    if (L.nm <= 0) return n;
     if (L.reuse) {
         // every engine's reuse step (an engine on its own records its reused rows' launch on this
         // timer too); after the bookkeeping, as the engine's own loop: a stopped engine's reused
-        // rows stay the ones of the iteration it stopped at
+        // rows stay the ones of the iteration it stopped at.  An engine of the step that does not
+        // reuse (a serve loop's fresh slot) has an empty entry: no workgroup of it writes
         Timed tm(e0, T_NOISE, s);
         launch_reuse_rows_group(g->shape, L.ras, L.nm, e0->K, e0->Kr, s);
+        ++n;
     }
     {
         // the cumulative rows of the engines that use them, on the control costs the reuse launch
         // re-priced, in the weights' scope as an engine's own launch_cumulative (the step's own
         // list: compacted, or a stopped engine a no-op at its flag)
         Timed tm(e0, T_WEIGHTS, s);
-        if (g->ncum > 0) launch_cumulative_group(L.was, L.nm, J, N, K, s);
+        if (g->ncum > 0) launch_cumulative_group(L.was, L.nm, J, N, K, s), ++n;
         launch_weights_group(L.was, L.nm, J, N, K, s);
+        ++n;
     }
     {
         Timed tm(e0, T_UPDATE, s);
         launch_update_group(J, N, L.uas, L.nm, s);
+        ++n;
     }
+    return n;
 }
 
+namespace {
 // one step's staged arrays over nm engines that run the iteration and nc of the flush cohort (the
 // arrays a group has no use for are empty): the host side; L gets the device side and the counts
 struct StepHost {
@@ -194,7 +131,7 @@ StepHost take_step(Arena& a, const stomp_group* g, int nm, int nc, bool track, S
     L.nm = nm; L.nc = nc;
     return StepHost{a.take(nm, L.cas), a.take(nm, L.was), a.take(nm, L.uas), a.take(reuse * nm, L.ras),
                     a.take(terms * nm, L.xas), a.take(nc, L.ccs), a.take(terms * nc, L.cxas),
-                    a.take(track ? nm + nc : 0, L.tas)};
+                    a.take(track ? nm + nc : 0, L.tas)};   // (stage_step fills L.ntrack of them)
 }
 
 // the model lists of a launch over the n engines `of`, staged (of == nullptr: measured only)
@@ -211,6 +148,7 @@ ModelLists take_models(Arena& a, const stomp_group* g, const int* of, int n)
     }
     return l;
 }
+}  // namespace
 
 // the capacity one staged step needs, with `lists` its two launches' model lists too
 size_t step_bytes(const stomp_group* g, int nm, int nc, bool track, bool lists)
@@ -221,6 +159,8 @@ size_t step_bytes(const stomp_group* g, int nm, int nc, bool track, bool lists)
     if (lists) take_models(measure, g, nullptr, nm), take_models(measure, g, nullptr, nc);
     return measure.used();
 }
+
+namespace {
 
 // h_args / d_args of at least `bytes` and h_args free again: the last upload has left it; a device
 // buffer is freed once the stream's launches have read it
@@ -317,6 +257,10 @@ StagedIteration stage_iteration(stomp_engine* e, int it, bool keep_in_pre, CostA
         ra.state = e->d_state;
         rr->nz = na;
         rr->ra = ra;
+    } else if (rr) {
+        // no reuse in this iteration (the generate-all one): with neighbours that reuse in the same
+        // step the engine's entry of the grouped reuse launch is empty (ra.K == 0: no workgroup writes)
+        *rr = ReuseRowArgs{};
     }
     WeightArgs wa = weight_args(e, e->K_loc, rows_pre ? na.pre_eps : e->d_noise);
     wa.mode = W_FUSED;
@@ -379,6 +323,7 @@ int sync_model_flags(stomp_group* g)
 // An engine whose model stomp_engine_retarget_request replaced on its own: the group's lists
 // (d_models, d_tmodels, nterms, terms_lds) still describe the old one.  Refused before anything is
 // touched; stomp_group_retarget_requests brings the group back in step.
+}  // namespace
 int check_epochs(stomp_group* g)
 {
     for (size_t p = 0; p < g->e.size(); ++p)
@@ -390,6 +335,7 @@ int check_epochs(stomp_group* g)
         }
     return 0;
 }
+namespace {
 
 // what stomp_group_create_flags tells an engine the group does not take, by what the group accepts
 const char* refusal_text(bool state_terms, bool cumulative)
@@ -450,55 +396,51 @@ int group_retarget(stomp_group* g, const stomp_request* rs)
     return 0;
 }
 
-TrackArgs track_args(const stomp_group* g, int p)
+}  // namespace
+
+// engine p's bookkeeping arguments; it: the iteration index of a launch's entry (negative: the
+// launch's own, as the start and clear launches leave it)
+TrackArgs track_args(const stomp_group* g, int p, int it)
 {
     const stomp_engine* e = g->e[p];
     return TrackArgs{e->d_track, e->d_total, e->d_cf, e->d_cs, e->d_opt_costs, e->d_last_traj, e->d_best_traj,
-                     e->max_it_cf, e->max_it, g->d_mirror + 2 * p};
+                     e->max_it_cf, e->max_it, g->d_mirror + 2 * p, it};
 }
 
-// One step's arguments into the arena, host only: iteration `it` of the engines `main`
-// (stage_iteration and their terms arguments; they must agree on the step's counts), the flush of
-// the engines `cohort`, and with `track` the bookkeeping arguments of both sets.
-int stage_step(stomp_group* g, Arena& a, const std::vector<int>& main, const std::vector<int>& cohort, int it,
-               bool keep_in_pre, bool track, StepLaunch& L)
+namespace {
+// One step's arguments into the arena, host only: engine main[k] at its iteration its[k]
+// (stage_iteration and its terms arguments; the step's counts are the largest of the engines'),
+// the flush of the engines `cohort`, and with `track` the bookkeeping arguments: iteration index
+// its[k] - 2 of a main engine past its first iteration, max_iterations - 1 of a cohort engine (the
+// table above stomp_group_optimize, per engine).
+int stage_step(stomp_group* g, Arena& a, const std::vector<int>& main, const std::vector<int>& its,
+               const std::vector<int>& cohort, bool keep_in_pre, bool track, StepLaunch& L)
 {
     const int nm = (int)main.size(), nc = (int)cohort.size();
     const StepHost h = take_step(a, g, nm, nc, track, L);
     if (a.overflowed()) return gfail(g, STOMP_E_INVALID, "group optimize staging overflow");
+    L.nro = L.ntot = L.ntrack = 0;
+    L.reuse = false;
     for (int k = 0; k < nm; ++k) {
         stomp_engine* e = g->e[main[k]];
-        const StagedIteration si = stage_iteration(e, it, keep_in_pre, h.cas[k], h.was[k], h.uas[k], h.ras + k);
+        const StagedIteration si = stage_iteration(e, its[k], keep_in_pre, h.cas[k], h.was[k], h.uas[k],
+                                                   e->Kr > 0 ? h.ras + k : nullptr);
         if (g->nterms > 0) h.xas[k] = terms_args(e, h.cas[k]);
-        if (k == 0) { L.nro = si.nro; L.ntot = si.ntot; L.reuse = si.reuse; }
-        else if (si.nro != L.nro || si.ntot != L.ntot || si.reuse != L.reuse)
-            return gfail(g, STOMP_E_INVALID, "group engines out of step");
-        if (track) h.tas[k] = track_args(g, main[k]);
+        L.nro = std::max(L.nro, si.nro);
+        L.ntot = std::max(L.ntot, si.ntot);
+        L.reuse = L.reuse || si.reuse;
+        if (track && its[k] >= 2) h.tas[L.ntrack++] = track_args(g, main[k], its[k] - 2);
     }
     for (int k = 0; k < nc; ++k) {
         stomp_engine* e = g->e[cohort[k]];
         h.ccs[k] = noiseless_args(e);   // with K_r > 0 the extra rollout's rows too
         if (g->nterms > 0) h.cxas[k] = terms_args(e, h.ccs[k]);
-        if (track) h.tas[nm + k] = track_args(g, cohort[k]);
+        if (track) h.tas[L.ntrack++] = track_args(g, cohort[k], e->max_it - 1);
     }
     return 0;
 }
 
-// ---- stomp_group_optimize's stages
-
-// what the stages of one stomp_group_optimize call share
-struct OptimizeLoop {
-    struct HostState { bool reused_next, extra_added; int row_set; };   // generateRollouts' on the host
-    stomp_group* g = nullptr;
-    std::vector<int> live;     // the engines staged from here on (all, or with g->compact the ones not seen stopped)
-    int next = 1;              // the first step not staged yet
-    int last_step = 0;         // the flush of the engines that ran the largest max_iterations
-    // after[p][it - 1]: engine p's state after iteration it, to restore for every engine the one
-    // of the iteration the device stopped it at (stomp_engine_optimize's)
-    std::vector<std::vector<HostState>> after;
-    std::vector<int> main, cohort;    // the step being staged
-    std::vector<StepLaunch> steps;    // the chunk being staged
-};
+// ---- stomp_group_optimize's stages (OptimizeLoop: engine_group.h)
 
 // The model lists of the rollout launch within a chunk: staged once, again where an engine's
 // max_iterations takes it out of the set (the upload of a chunk carries them once, not per step).
@@ -515,13 +457,17 @@ struct MainLists {
     }
 };
 
+}  // namespace
+
 // first-call allocations and the track arguments' upload
 int optimize_prepare(stomp_group* g)
 {
     if (g->d_mirror) return 0;
     const int P = (int)g->e.size();
-    // one chunk of steps with every engine in both sets at most, and both launches' model lists
-    const size_t slot_bytes = step_bytes(g, P, P, true, true) * (size_t)STOMP_GROUP_OPTIMIZE_CHUNK;
+    // one chunk of steps with every engine in both sets at most, and both launches' model lists;
+    // a serve loop's chunk also carries a turnover's arguments
+    const size_t slot_bytes = step_bytes(g, P, P, true, true) * (size_t)STOMP_GROUP_OPTIMIZE_CHUNK +
+                              serve_chunk_bytes(P, g->e[0]->J);
     if (hipMalloc((void**)&g->d_mirror, sizeof(int) * 2 * P) != hipSuccess ||
         hipHostMalloc((void**)&g->h_mirror, sizeof(int) * 4 * P) != hipSuccess ||
         hipMalloc((void**)&g->d_track_all, sizeof(TrackArgs) * P) != hipSuccess ||
@@ -539,6 +485,7 @@ int optimize_prepare(stomp_group* g)
     return 0;
 }
 
+namespace {
 // The engines enter in any state: rows out of the pregen buffers, pending noiseless rollouts
 // evaluated, the pregen rows of iteration 1 made where another iteration's are held.
 void optimize_enter(stomp_group* g)
@@ -554,50 +501,76 @@ void optimize_enter(stomp_group* g)
     launch_track_start_group(g->d_track_all, (int)g->e.size(), false, g->stream);   // stomp_optimizer.cpp:251 start_time
 }
 
-// The next chunk of steps into the arena and onto o.steps, host only.  In step `it` the engines
-// of o.main run the iteration and the ones of o.cohort, which ended with it - 1, get their flush
-// (the table above stomp_group_optimize).
+// the staged entries of engines whose padding-collision flag the host does not know (a serve
+// loop's turned slots): listed for launch_serve_flags
+void note_flag_copies(OptimizeLoop& o, const ModelLists& l, const std::vector<int>& of)
+{
+    if (!o.flag_unknown || !l.models) return;
+    for (size_t k = 0; k < of.size(); ++k)
+        if ((*o.flag_unknown)[of[k]])
+            o.flag_copies.push_back({o.g->e[of[k]]->d_pad_cf, (int*)((const unsigned char*)(l.models + k) +
+                                                                      offsetof(DevModel, pad_collision))});
+}
+
+// The next chunk of steps into the arena and onto o.steps, host only.  In step `step` engine p is
+// at its iteration it = step - o.start[p] + 1: the engines of o.main run theirs, the ones of
+// o.cohort, which ended with it - 1, get their flush (the table above stomp_group_optimize).
 int optimize_stage_chunk(OptimizeLoop& o, Arena& a)
 {
     stomp_group* g = o.g;
     MainLists lists;
     o.steps.clear();
+    o.flag_copies.clear();
     const int end = std::min(o.next + STOMP_GROUP_OPTIMIZE_CHUNK, o.last_step + 1);
-    for (int it = o.next; it < end; ++it) {
+    for (int step = o.next; step < end; ++step) {
         o.main.clear();
+        o.main_it.clear();
         o.cohort.clear();
         for (int p : o.live) {
-            if (g->e[p]->max_it >= it) o.main.push_back(p);
-            else if (g->e[p]->max_it == it - 1 && it >= 2) o.cohort.push_back(p);
+            const int it = step - o.start[p] + 1;
+            if (it >= 1 && g->e[p]->max_it >= it) {
+                o.main.push_back(p);
+                o.main_it.push_back(it);
+            } else if (g->e[p]->max_it == it - 1 && it >= 2) {
+                o.cohort.push_back(p);
+            }
         }
         // inside the optimize loop the noise / params rows are copied out of the pregen buffer
         // (pregen blocks enqueued past a stop overwrite the ping-pong buffers), the weights read
         // d_noise
-        for (int p : o.main)
-            if (g->e[p]->pre_it != it) return gfail(g, STOMP_E_INVALID, "group pregen rows out of step");
+        for (size_t k = 0; k < o.main.size(); ++k)
+            if (g->e[o.main[k]]->pre_it != o.main_it[k]) return gfail(g, STOMP_E_INVALID, "group pregen rows out of step");
         StepLaunch L;
-        if (int rc = stage_step(g, a, o.main, o.cohort, it, false, true, L)) return rc;
+        if (int rc = stage_step(g, a, o.main, o.main_it, o.cohort, false, true, L)) return rc;
         L.clists = take_models(a, g, o.cohort.data(), (int)o.cohort.size());
+        const DevModel* held = lists.lists.models;
         L.lists = lists.get(a, g, o.main);
         if (a.overflowed()) return gfail(g, STOMP_E_INVALID, "group optimize staging overflow");
-        L.track_it = it >= 2 ? it - 2 : -1;
-        for (int p : o.main)
-            if (g->e[p]->Kr > 0) o.after[p][it - 1] = {g->e[p]->reused_next, g->e[p]->extra_added, g->e[p]->row_set};
+        note_flag_copies(o, L.clists, o.cohort);
+        if (L.lists.models != held) note_flag_copies(o, L.lists, o.main);
+        for (size_t k = 0; k < o.main.size(); ++k) {
+            const stomp_engine* e = g->e[o.main[k]];
+            if (e->Kr > 0) o.after[o.main[k]][o.main_it[k] - 1] = {e->reused_next, e->extra_added, e->row_set};
+        }
         o.steps.push_back(L);
     }
     o.next = end;
     return 0;
 }
+}  // namespace
 
 // one chunk of steps staged into `slot`, uploaded and enqueued, then the mirror's read-back
-int optimize_enqueue_chunk(OptimizeLoop& o, int slot)
+int optimize_enqueue_chunk(OptimizeLoop& o, int slot, const ChunkExtra* extra)
 {
     stomp_group* g = o.g;
     const int P = (int)g->e.size();
     Arena a{g->h_opt + (size_t)slot * g->opt_slot, g->d_opt + (size_t)slot * g->opt_slot, g->opt_slot};
     if (int rc = optimize_stage_chunk(o, a)) return rc;
+    if (extra)
+        if (int rc = extra->stage(a)) return rc;
     if (int rc = upload(g, a, nullptr)) return rc;
-    for (const StepLaunch& L : o.steps) launch_step(g, L);
+    if (extra) extra->launch();
+    for (const StepLaunch& L : o.steps) o.launches += launch_step(g, L);
     if (hipMemcpyAsync(g->h_mirror + (size_t)slot * 2 * P, g->d_mirror, sizeof(int) * 2 * P, hipMemcpyDeviceToHost,
                        g->stream) != hipSuccess ||
         hipEventRecord(g->opt_ev[slot], g->stream) != hipSuccess)
@@ -605,6 +578,17 @@ int optimize_enqueue_chunk(OptimizeLoop& o, int slot)
     return 0;
 }
 
+void optimize_restore(OptimizeLoop& o, int p, int iterations)
+{
+    stomp_engine* e = o.g->e[p];
+    if (e->Kr <= 0 || iterations <= 0) return;
+    const OptimizeLoop::HostState& h = o.after[p][iterations - 1];
+    e->reused_next = h.reused_next;
+    e->extra_added = h.extra_added;
+    if (e->row_set != h.row_set) swap_row_sets(e);
+}
+
+namespace {
 // The loop is over (rc: how): pipeline state reset, every engine's DevTrack read back, its
 // generateRollouts state put back to the iteration it stopped at, cost histories and stats out.
 int optimize_finish(OptimizeLoop& o, int rc, stomp_stats* stats, double* costs_per_iteration, int32_t costs_stride)
@@ -632,13 +616,7 @@ int optimize_finish(OptimizeLoop& o, int rc, stomp_stats* stats, double* costs_p
     for (int p = 0; p < P; ++p) {
         stomp_engine* e = g->e[p];
         const DevTrack& t = e->h_track[2];
-        if (e->Kr > 0 && t.iterations > 0) {
-            // the steps staged past the engine's stop were no-ops on the device
-            const OptimizeLoop::HostState& h = o.after[p][t.iterations - 1];
-            e->reused_next = h.reused_next;
-            e->extra_added = h.extra_added;
-            if (e->row_set != h.row_set) swap_row_sets(e);
-        }
+        optimize_restore(o, p, t.iterations);
         if (costs_per_iteration && t.iterations > 0 &&
             hipMemcpy(costs_per_iteration + (size_t)p * costs_stride, e->d_opt_costs, sizeof(double) * t.iterations,
                       hipMemcpyDeviceToHost) != hipSuccess)
@@ -648,6 +626,7 @@ int optimize_finish(OptimizeLoop& o, int rc, stomp_stats* stats, double* costs_p
     return 0;
 }
 }  // namespace
+}  // namespace stomp
 
 extern "C" {
 
@@ -659,7 +638,7 @@ void stomp_group_destroy(stomp_group* g)
         hipEventSynchronize(g->staged);
         hipEventDestroy(g->staged);
     }
-    free_device(g->d_models, g->d_tmodels, g->d_args, g->d_opt, g->d_mirror, g->d_track_all, g->d_rq);
+    free_device(g->d_models, g->d_tmodels, g->d_args, g->d_opt, g->d_mirror, g->d_track_all, g->d_rq, g->d_slab);
     free_pinned(g->h_args, g->h_opt, g->h_mirror, g->h_rq);
     for (hipEvent_t ev : g->opt_ev)
         if (ev) hipEventDestroy(ev);
@@ -828,14 +807,16 @@ int stomp_group_run(stomp_group* g, int32_t first, int32_t count)
     Arena a{g->h_args, g->d_args, bytes};
     std::vector<StepLaunch> steps(count);
     std::vector<char> pregen_first(P, 0);
+    std::vector<int> its(P);
     for (int i = 0; i < count; ++i) {
         const int it = first + i;
+        std::fill(its.begin(), its.end(), it);   // a run's engines are in lockstep
         for (int p = 0; p < P; ++p) {
             if (g->e[p]->pre_it == it) continue;
             if (i > 0) return gfail(g, STOMP_E_INVALID, "group pregen rows out of step");
             pregen_first[p] = 1;
         }
-        if (int rc = stage_step(g, a, g->all, {}, it, true, false, steps[i])) return rc;
+        if (int rc = stage_step(g, a, g->all, its, {}, true, false, steps[i])) return rc;
         steps[i].lists = {g->d_models, g->d_tmodels, g->nterms};
     }
     for (int p = 0; p < P; ++p)
@@ -865,7 +846,7 @@ int stomp_group_synchronize(stomp_group* g)
             return gfail(g, STOMP_E_DEVICE, "group staging wait failed");
         Arena a{g->h_args, g->d_args, cap};
         StepLaunch L;
-        if (int rc = stage_step(g, a, {}, g->all, 0, false, false, L)) return rc;
+        if (int rc = stage_step(g, a, {}, {}, g->all, false, false, L)) return rc;
         L.clists = {g->d_models, g->d_tmodels, g->nterms};
         L.time_flush = false;
         if (int rc = upload(g, a, g->staged)) return rc;
@@ -912,6 +893,7 @@ int stomp_group_optimize(stomp_group* g, stomp_stats* stats, double* costs_per_i
     OptimizeLoop o;
     o.g = g;
     o.after.resize(P);
+    o.start.assign(P, 1);   // lockstep: every engine's iteration 1 in step 1
     if (e0->Kr > 0)
         for (int p = 0; p < P; ++p) o.after[p].resize((size_t)std::max(g->e[p]->max_it, 0));
     for (int p = 0; p < P; ++p)

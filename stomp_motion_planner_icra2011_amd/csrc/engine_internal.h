@@ -6,7 +6,10 @@
 //   engine_create.cpp    descriptor validation and stomp_engine_create's stages
 //   engine_exchange.cpp  the in-process group, the RCCL path, the collectives, calibration
 //   engine_group.cpp     stomp_group: one launcher of a grouped step (launch_step) and one arena of
-//                        staged arguments behind run, synchronize and optimize
+//                        staged arguments behind run, synchronize and optimize (engine_group.h: what
+//                        it shares with engine_serve.cpp)
+//   engine_serve.cpp     stomp_group_serve: the optimize loop over a queue, a slot that stops taking
+//                        the next request; stomp_serve_schedule, its decisions as a host-only function
 //   engine_retarget.cpp  the one retarget path (validate, plan, stage, launch, commit) behind
 //                        stomp_engine_retarget, stomp_engine_retarget_request and the two group calls
 //   sdf_build.cpp        the distance-field builders (does not include this header)
@@ -282,6 +285,10 @@ inline stomp_request kept_request(const double* start, const double* goal, uint6
 // the host side of a retarget once its launch has run: the new vectors, seed (null: kept) and
 // padding-collision flag, every piece of iteration state dropped
 void retarget_host_state(stomp_engine* e, const double* start, const double* goal, const uint64_t* seed, int flag);
+// k_retarget's arguments for an engine that keeps its model: d_vec [2][J] the new start and goal
+// on the device, d_flag_out the read-back slot, list_entry the engine's entry of a group's DevModel
+// list or null
+RequestArgs kept_request_args(const stomp_engine* e, const double* d_vec, int* d_flag_out, DevModel* list_entry);
 
 // A request's model for one engine, planned on the host before anything is touched: the tables
 // and the layout of the new collision points (spheres), the new path constraints (constraints),

@@ -39,6 +39,28 @@ void retarget_host_state(stomp_engine* e, const double* start, const double* goa
     e->cur_it = -1;
 }
 
+// k_retarget's arguments for an engine that keeps its model, outside a retarget call (a serve
+// loop's turnover): request_launch's entry of a request that replaces nothing
+RequestArgs kept_request_args(const stomp_engine* e, const double* d_vec, int* d_flag_out, DevModel* list_entry)
+{
+    RequestArgs r;
+    std::memset(&r, 0, sizeof r);
+    r.model = e->model;
+    r.stage = d_vec;
+    r.Rb = e->d_Rb; r.RinvT = e->d_RinvT;
+    r.theta = e->d_theta; r.last_traj = e->d_last_traj; r.best_traj = e->d_best_traj;
+    r.start = e->d_start; r.goal = e->d_goal;
+    r.pad_pos = (double*)e->model.pad_pos; r.pad_cf = e->d_pad_cf;
+    r.model_flag = list_entry ? &list_entry->pad_collision : nullptr;
+    r.flag_out = d_flag_out;
+    r.stage_img = e->model.img;   // the tables are the engine's own, which no workgroup writes
+    r.img_out = e->d_img;
+    r.oc_out = (unsigned long long*)e->d_oc;
+    r.cs = e->d_cs;
+    r.terms = e->terms;
+    return r;
+}
+
 namespace {
 
 bool all_finite(const double* v, int n)

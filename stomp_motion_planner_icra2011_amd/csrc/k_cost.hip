@@ -925,28 +925,38 @@ __global__ __launch_bounds__(kWideBlock, kWideBlock > 512 ? 4 : 2) void k_rollou
 }
 
 // one launch for the rollouts of a group of engines of one shape (stomp_group_run): every
-// engine's rollout workgroups first (engine p's nro of them at p nro), then every engine's
-// pregen blocks and, on a reusing iteration, its reuse candidates' totals blocks after them (npre
-// = pre_rows + tot_rows each, at the default priority behind the rollouts of all); models and
-// arguments live in device memory, one entry per engine
+// engine's rollout workgroups first (engine p's at p nro), then every engine's pregen blocks and,
+// on a reusing iteration, its reuse candidates' totals blocks after them (engine p's at p npre, at
+// the default priority behind the rollouts of all); models and arguments live in device memory,
+// one entry per engine.  nro / npre: the most rollout workgroups and the most pregen + totals
+// blocks any engine of the launch has.  An engine's own counts are its CostArgs' (the engines of a
+// serve loop are each at their own iteration: a fresh one generates every row and has no noiseless
+// rollout pending while its neighbours reuse); a block past them returns before it touches LDS or
+// memory, and the blocks behind the rollouts are numbered from the engine's own rollout count, as
+// rollout_body reads them.
 template <int BLOCK, bool BRICK>
 __global__ __launch_bounds__(BLOCK, rollout_min_waves<BLOCK>()) void k_rollout_group(const DevModel* ms, const CostArgs* as,
                                                                            int engines, int nro, int npre)
 {
+    // the per-engine models and arguments read through the constant address space: wave-uniform
+    // scalar loads the compiler may repeat, as it does for a kernel argument
+    using CModel = const __attribute__((address_space(4))) DevModel;
+    using CArgs = const __attribute__((address_space(4))) CostArgs;
     const int b = blockIdx.x;
     int p, bid;
     if (b < engines * nro) {
         p = b / nro;
         bid = b - p * nro;
+        const CostArgs& a = *(const CostArgs*)((CArgs*)as + p);
+        if (bid >= a.num_noisy + (a.x_params ? 1 : 0)) return;
     } else {
         const int j = b - engines * nro;
         p = j / npre;
-        bid = nro + (j - p * npre);
+        const int r = j - p * npre;
+        const CostArgs& a = *(const CostArgs*)((CArgs*)as + p);
+        if (r >= a.pre_rows + a.tot_rows) return;
+        bid = a.num_noisy + (a.x_params ? 1 : 0) + r;
     }
-    // the per-engine models and arguments read through the constant address space: wave-uniform
-    // scalar loads the compiler may repeat, as it does for a kernel argument
-    using CModel = const __attribute__((address_space(4))) DevModel;
-    using CArgs = const __attribute__((address_space(4))) CostArgs;
     // the FK advance overlaps the gathers here too: with the arguments in the constant address space
     // the grouped kernel fits it in 162 VGPRs without spilling (it had spilled 104 B per lane with
     // the generic-pointer arguments, round 3)
@@ -1407,21 +1417,38 @@ STOMP_STAMP_ACCESSORS(cost)
 // rollout kernel's noise phase, run on a side stream while the previous iteration's weights
 // and update occupy the main one
 template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void k_pregen(NoiseArgs a)
+__device__ __forceinline__ void pregen_row(const NoiseArgs& a, int r)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_pg[];
     if (a.stop && *a.stop) return;
     const RolloutLds L = rollout_lds(a.J, a.N, 0, 0, 0, 0, 0, 0, 0);
     double* zA = (double*)lds_pg;
     double* zB = (double*)(lds_pg + (L.nzB - L.nzA));
-    rollout_normals<BLOCK>(a, blockIdx.x, zA, zB, threadIdx.x);
+    rollout_normals<BLOCK>(a, r, zA, zB, threadIdx.x);
     if (a.J <= 8) {
-        pregen_eps_ng<BLOCK, 2>(a, blockIdx.x, zA, zB, threadIdx.x);
-        pregen_meps_ng<BLOCK, 2>(a, blockIdx.x, zB, threadIdx.x);
+        pregen_eps_ng<BLOCK, 2>(a, r, zA, zB, threadIdx.x);
+        pregen_meps_ng<BLOCK, 2>(a, r, zB, threadIdx.x);
     } else {
-        pregen_eps_ng<BLOCK, 4>(a, blockIdx.x, zA, zB, threadIdx.x);
-        pregen_meps_ng<BLOCK, 4>(a, blockIdx.x, zB, threadIdx.x);
+        pregen_eps_ng<BLOCK, 4>(a, r, zA, zB, threadIdx.x);
+        pregen_meps_ng<BLOCK, 4>(a, r, zB, threadIdx.x);
     }
+}
+
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_pregen(NoiseArgs a)
+{
+    pregen_row<BLOCK>(a, blockIdx.x);
+}
+
+// k_pregen for several engines of one shape in one launch (a serve loop's turnover: the rows of
+// iteration 1 of every slot that takes a request): engine p's rows are workgroups [p rows,
+// (p + 1) rows), the arguments live in device memory, one entry per engine
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_pregen_group(const NoiseArgs* as, int rows)
+{
+    const int p = blockIdx.x / rows, r = blockIdx.x - p * rows;
+    using CArgs = const __attribute__((address_space(4))) NoiseArgs;
+    pregen_row<BLOCK>(*(const NoiseArgs*)((CArgs*)as + p), r);
 }
 
 void launch_pregen(const NoiseArgs& a, int rows, hipStream_t s)
@@ -1430,6 +1457,14 @@ void launch_pregen(const NoiseArgs& a, int rows, hipStream_t s)
     const RolloutLds L = rollout_lds(a.J, a.N, 0, 0, 0, 0, 0, 0, 0);
     const size_t lds = 2 * (L.nzB - L.nzA);
     hipLaunchKernelGGL((k_pregen<256>), dim3(rows), dim3(256), lds, s, a);
+}
+
+void launch_pregen_group(const NoiseArgs& a0, const NoiseArgs* as, int engines, int rows, hipStream_t s)
+{
+    if (engines <= 0 || rows <= 0) return;
+    const RolloutLds L = rollout_lds(a0.J, a0.N, 0, 0, 0, 0, 0, 0, 0);
+    const size_t lds = 2 * (L.nzB - L.nzA);
+    hipLaunchKernelGGL((k_pregen_group<256>), dim3(engines * rows), dim3(256), lds, s, as, rows);
 }
 
 template <bool BRICK>

@@ -625,13 +625,14 @@ __global__ __launch_bounds__(256) void k_track(DevTrack* tr, int it, int max_it_
     track_body(tr, it, max_it_cf, 0, total, cf, cs, costs, last_traj, best_traj, JN, nullptr);
 }
 
-// the bookkeeping of a group's engines in one launch: one workgroup per engine, `it` the launch's
-// (the engines run in lockstep)
+// the bookkeeping of a group's engines in one launch: one workgroup per engine, each at its entry's
+// own iteration index, or at `it`, the launch's, where the entry names none (engines in lockstep)
 __global__ __launch_bounds__(256) void k_track_group(const TrackArgs* as, int it, int JN)
 {
     using CArgs = const __attribute__((address_space(4))) TrackArgs;   // scalar loads, as a kernel argument
     const TrackArgs& a = *(const TrackArgs*)((CArgs*)as + blockIdx.x);
-    track_body(a.tr, it, a.max_it_cf, a.max_it, a.total, a.cf, a.cs, a.costs, a.last_traj, a.best_traj, JN, a.mirror);
+    track_body(a.tr, a.it >= 0 ? a.it : it, a.max_it_cf, a.max_it, a.total, a.cf, a.cs, a.costs, a.last_traj,
+               a.best_traj, JN, a.mirror);
 }
 
 __global__ void k_track_start(DevTrack* tr)
@@ -663,6 +664,51 @@ __global__ void k_track_start_group(const TrackArgs* as, int clear)
     a.mirror[0] = stop;
     a.mirror[1] = 0;
     tr->t0 = wall_clock64();
+}
+
+// A serve loop's turnover (TurnArgs, kernels.h): one workgroup per slot.  The finished request's
+// record first -- its DevTrack by thread 0, its best trajectory and the `iterations` entries of its
+// cost history by the whole block -- then, behind a barrier (every thread has read `iterations` and
+// thread 0 the whole record), the DevTrack of the next request as k_track_start_group leaves it.
+__global__ __launch_bounds__(256) void k_serve_turnover(const TurnArgs* as, int JN)
+{
+    using CArgs = const __attribute__((address_space(4))) TurnArgs;
+    const TurnArgs& a = *(const TurnArgs*)((CArgs*)as + blockIdx.x);
+    DevTrack* tr = a.t.tr;
+    if (a.out_track) {
+        const int n = min(max(tr->iterations, 0), a.t.max_it);
+        if (threadIdx.x == 0) *a.out_track = *tr;
+        for (int i = threadIdx.x; i < JN; i += blockDim.x) a.out_best[i] = a.t.best_traj[i];
+        for (int i = threadIdx.x; i < n; i += blockDim.x) a.out_costs[i] = a.t.costs[i];
+    }
+    __syncthreads();
+    if (!a.reinit || threadIdx.x != 0) return;
+    tr->stop = 0;
+    tr->cfi = 0;
+    tr->iterations = 0;
+    tr->success = 0;
+    tr->success_iteration = -1;
+    tr->collision_success_iteration = -1;
+    tr->last_improvement_iteration = -1;
+    tr->best = 0.0;
+    a.t.mirror[0] = 0;
+    a.t.mirror[1] = 0;
+    tr->t0 = wall_clock64();
+}
+
+__global__ void k_serve_flags(const FlagCopy* cs, int n)
+{
+    for (int i = threadIdx.x; i < n; i += blockDim.x) *cs[i].dst = *cs[i].src;
+}
+
+void launch_serve_turnover(const TurnArgs* as, int slots, int JN, hipStream_t s)
+{
+    if (slots > 0) hipLaunchKernelGGL(k_serve_turnover, dim3(slots), dim3(256), 0, s, as, JN);
+}
+
+void launch_serve_flags(const FlagCopy* cs, int n, hipStream_t s)
+{
+    if (n > 0) hipLaunchKernelGGL(k_serve_flags, dim3(1), dim3(64), 0, s, cs, n);
 }
 
 void launch_track_start(DevTrack* tr, hipStream_t s)

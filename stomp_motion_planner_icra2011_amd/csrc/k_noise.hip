@@ -427,7 +427,9 @@ __global__ __launch_bounds__(BLOCK) void k_noise_rows(NoiseArgs a, ReuseArgs ra)
 
 // the reuse step of a group of engines of one shape in one launch (stomp_group_run): engine p's
 // Kr reused rows are workgroups [p Kr, (p + 1) Kr); the arguments live in device memory, one entry
-// per engine
+// per engine.  An entry with ra.K == 0 is an engine that does not reuse in this step (a slot of a
+// serve loop at its generate-all iteration beside neighbours that reuse): its workgroups return
+// before they touch LDS or memory.
 template <int BLOCK, int NG>
 __global__ __launch_bounds__(BLOCK) void k_reuse_rows_group(const ReuseRowArgs* as, int Kr)
 {
@@ -436,6 +438,7 @@ __global__ __launch_bounds__(BLOCK) void k_reuse_rows_group(const ReuseRowArgs* 
     // as it does for a kernel argument (k_rollout_group)
     using CArgs = const __attribute__((address_space(4))) ReuseRowArgs;
     const ReuseRowArgs& g = *(const ReuseRowArgs*)((CArgs*)as + p);
+    if (g.ra.K == 0) return;
     noise_rows_body<BLOCK, NG, true>(g.nz, g.ra, rb);
 }
 

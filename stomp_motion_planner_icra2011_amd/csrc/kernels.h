@@ -380,6 +380,9 @@ size_t price_candidate_lds_bytes(int J, int N);
 // the theta-independent part of generateRollouts + computeProjectedNoise for rows [0, rows):
 // normals, eps = sigma L z and M eps into a.pre_eps / a.pre_meps (run ahead on a side stream)
 void launch_pregen(const NoiseArgs& a, int rows, hipStream_t s);
+// the same for several engines of a0's shape in one launch: as [engines] in device memory, `rows`
+// rows each (a serve loop's turnover)
+void launch_pregen_group(const NoiseArgs& a0, const NoiseArgs* as, int engines, int rows, hipStream_t s);
 
 // StompOptimizer::optimize bookkeeping on the device (stomp_optimizer.cpp:301-344), one launch
 // after each iteration's noiseless rollout; sets stop when the loop would break
@@ -396,8 +399,8 @@ struct DevTrack {
 void launch_track_start(DevTrack* tr, hipStream_t s);
 void launch_track(DevTrack* tr, int it, int max_it_cf, const double* total, const uint8_t* cf, const uint8_t* cs,
                   double* costs, const double* last_traj, double* best_traj, int JN, hipStream_t s);
-// the bookkeeping of a group of engines in lockstep (stomp_group_optimize): per-engine arguments
-// in device memory, one entry and one workgroup per engine.  The grouped k_track also stops an
+// the bookkeeping of a group of engines (stomp_group_optimize, stomp_group_serve): per-engine
+// arguments in device memory, one entry and one workgroup per engine.  The grouped k_track also stops an
 // engine when its own max_iterations is reached and mirrors (stop, iterations) into the group's
 // read-back array (mirror: the engine's two ints of it).
 struct TrackArgs {
@@ -410,10 +413,35 @@ struct TrackArgs {
     double* best_traj;          // [J][N]
     int max_it_cf, max_it;
     int* mirror;                // [2] (stop, iterations)
+    int it;                     // the entry's own iteration index; negative: the launch's (engines in
+                                // lockstep).  The slots of a serve loop are each at their own.
 };
 // clear = false: every engine's initial DevTrack and start stamp; true: the stop flags lowered
 void launch_track_start_group(const TrackArgs* as, int engines, bool clear, hipStream_t s);
 void launch_track_group(const TrackArgs* as, int engines, int it, int JN, hipStream_t s);
+// A serve loop's turnover (stomp_group_serve): the slots that leave a finished request and / or take
+// the next one at one chunk boundary, one entry and one workgroup per slot, in stream order behind
+// the steps already enqueued and ahead of launch_retarget and launch_pregen_group over the same
+// slots.  With out_track the finished request's DevTrack, best trajectory (JN doubles) and cost
+// history (its `iterations` doubles) are copied into the group's result slab; with reinit the
+// DevTrack is then put into the loop's initial state, stop flag lowered, with a fresh start stamp,
+// and the slot's mirror entry cleared.
+struct TurnArgs {
+    TrackArgs t;
+    DevTrack* out_track;        // the finished request's record in the slab, or null
+    double* out_best;           // [JN]
+    double* out_costs;          // [t.max_it]
+    int reinit;
+};
+void launch_serve_turnover(const TurnArgs* as, int slots, int JN, hipStream_t s);
+// The padding-collision flags k_retarget made for a turnover's slots, copied into the model list
+// entries staged (from host copies that do not know them yet) for the chunks that follow: one
+// 4-byte copy per entry, n of them, behind launch_retarget on the same stream.
+struct FlagCopy {
+    const int* src;             // the engine's own flag (RequestArgs::pad_cf)
+    int* dst;                   // DevModel::pad_collision of a staged entry
+};
+void launch_serve_flags(const FlagCopy* cs, int n, hipStream_t s);
 void launch_cost(const DevModel& m, const CostArgs& a, hipStream_t s);
 bool cost_supported(const DevModel& m);
 size_t rollout_lds_bytes(const DevModel& m, int pad_lds, int lean = 0);   // dynamic LDS of the rollout kernel
@@ -443,8 +471,9 @@ struct UpdateArgs {
     double* theta;
     const int* stop;
 };
-// npre: the blocks after an engine's rollouts, its pregen blocks and then its totals blocks
-// (CostArgs::pre_rows + tot_rows, the same for every engine of the launch)
+// nro / npre: the most rollout workgroups (num_noisy + the noiseless rollout) and the most blocks
+// after them (CostArgs::pre_rows pregen blocks, then tot_rows totals blocks) any engine of the
+// launch has; an engine's own counts are its CostArgs', and a block past them does nothing
 void launch_cost_group(const DevModel& m0, const DevModel* ms, const CostArgs* as, int engines, int nro, int npre,
                        hipStream_t s);
 // the reuse step of every engine of a group in one launch (launch_reuse_rows' kernel body, one

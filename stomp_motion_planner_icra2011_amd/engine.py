@@ -91,6 +91,10 @@ class stomp_stats(C.Structure):
                 ("collision_success_duration", C.c_double)]
 
 
+class stomp_serve_result(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("start_step", C.c_int32), ("stats", stomp_stats)]
+
+
 # stomp_group_create_flags' accept mask
 STOMP_GROUP_ACCEPT_STATE_TERMS = 1
 STOMP_GROUP_ACCEPT_CUMULATIVE = 2
@@ -119,7 +123,8 @@ EXPORTED = ["stomp_engine_create", "stomp_engine_destroy", "stomp_engine_last_er
             "stomp_engine_refresh_field", "stomp_device_selftest_trig", "stomp_engine_retarget",
             "stomp_group_retarget", "stomp_scene_create", "stomp_scene_set_static", "stomp_scene_set_dynamic",
             "stomp_scene_window", "stomp_scene_info", "stomp_scene_destroy", "stomp_engine_retarget_request",
-            "stomp_engine_model_info", "stomp_group_retarget_requests", "stomp_attached_collision_points"]
+            "stomp_engine_model_info", "stomp_group_retarget_requests", "stomp_attached_collision_points",
+            "stomp_group_serve", "stomp_group_serve_info", "stomp_serve_schedule"]
 
 _lib = None
 
@@ -215,6 +220,12 @@ def load_library(path: Optional[str] = None):
     l.stomp_group_optimize.argtypes = [C.c_void_p, C.POINTER(stomp_stats), dp, C.c_int32]
     l.stomp_group_optimize_chunk.restype = C.c_int32
     l.stomp_group_optimize_chunk.argtypes = []
+    if hasattr(l, "stomp_group_serve"):   # (a variant library named by STOMP_ENGINE_LIB may predate them)
+        ip = C.POINTER(C.c_int32)
+        l.stomp_group_serve.argtypes = [C.c_void_p, dp, dp, C.POINTER(C.c_uint64), C.c_int32,
+                                        C.POINTER(stomp_serve_result), dp, dp, C.c_int32]
+        l.stomp_group_serve_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        l.stomp_serve_schedule.argtypes = [C.c_int32, C.c_int32, ip, ip, ip, ip]
     l.stomp_group_last_error.restype = C.c_char_p
     l.stomp_group_last_error.argtypes = [C.c_void_p]
     l.stomp_group_destroy.argtypes = [C.c_void_p]
@@ -815,6 +826,50 @@ class EngineGroup:
         for p, e in enumerate(self.engines):
             e._follow(rows[p][0], rows[p][1], int(sd[p]), sph[p], ocs[p], keep[p])
 
+    def serve(self, starts, goals, seeds, costs_stride: Optional[int] = None):
+        """stomp_group_serve: a queue of n requests (rows of starts / goals, n x J; n seeds) served
+        by the group's engines as slots.  Requests are handed out in index order; a slot whose
+        request has stopped takes the next waiting one at the next chunk boundary, so no slot idles
+        until the slowest problem of a batch ends.  A request is a plain retarget: the model, the
+        field and every parameter are the slot's own.  Returns one (slot, start_step, stomp_stats,
+        costs[:iterations], best[J][N]) per request, each bit for bit what retarget + optimize() of
+        the slot's engine gives; slot and start_step are serve_schedule(P, iterations)'s.
+        Afterwards every used engine is where the retarget to the last request it planned and its
+        own optimize() leave it, and its problem attribute follows; with n < P the engines n.. are
+        untouched."""
+        e0 = self.engines[0]
+        J, N = e0.J, e0.N
+        s = np.ascontiguousarray(starts, np.float64)
+        g = np.ascontiguousarray(goals, np.float64)
+        sd = np.array([int(v) for v in seeds], np.uint64)
+        n = len(sd)
+        if n == 0 or s.size != n * J or g.size != n * J:
+            raise ValueError("starts and goals must be n x %d for n >= 1 seeds" % J)
+        s, g = s.reshape(n, J), g.reshape(n, J)
+        if costs_stride is None:
+            costs_stride = max([e.problem.params.max_iterations for e in self.engines] + [1])
+        res = (stomp_serve_result * n)()
+        best = np.zeros((n, J, N))
+        costs = np.zeros((n, max(costs_stride, 1)))
+        self._check(load_library().stomp_group_serve(self._h, _dp(s), _dp(g), sd.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                     n, res, _dp(best), _dp(costs), costs_stride))
+        for r in range(n):   # (in index order: a slot's last request is the one it keeps)
+            self.engines[res[r].slot]._follow(s[r], g[r], int(sd[r]))
+        return [(int(res[r].slot), int(res[r].start_step), res[r].stats, costs[r, : res[r].stats.iterations].copy(),
+                 best[r].copy()) for r in range(n)]
+
+    SERVE_INFO = ("steps", "occupied_slot_steps", "turnovers", "mixed_steps", "largest_idle_gap", "launches",
+                  "result_bytes", "allocations")
+
+    def serve_info(self) -> dict:
+        """stomp_group_serve_info: the last serve() call's group steps, the requests' iterations
+        summed, turnovers, steps in which two live slots ran different iteration numbers, the largest
+        idle gap (steps) between a slot's stop and its next request's iteration 1, kernel launches
+        enqueued, device bytes held for results and allocations made by the call."""
+        info = (C.c_int64 * 8)()
+        self._check(load_library().stomp_group_serve_info(self._h, info))
+        return dict(zip(self.SERVE_INFO, (int(v) for v in info)))
+
     def close(self):
         if self._h is not None and self._h.value:
             load_library().stomp_group_destroy(self._h)
@@ -822,6 +877,19 @@ class EngineGroup:
 
     def __del__(self):
         self.close()
+
+
+def serve_schedule(num_slots: int, iterations):
+    """stomp_serve_schedule, host only: the (slots, start_steps, total_steps) EngineGroup.serve()
+    produces for requests that run these numbers of iterations on num_slots slots."""
+    it = np.ascontiguousarray(iterations, np.int32).reshape(-1)
+    n = len(it)
+    slot, start = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    total = C.c_int32()
+    ip = C.POINTER(C.c_int32)
+    _check(load_library().stomp_serve_schedule(num_slots, n, it.ctypes.data_as(ip), slot.ctypes.data_as(ip),
+                                               start.ctypes.data_as(ip), C.byref(total)))
+    return [int(v) for v in slot[:n]], [int(v) for v in start[:n]], int(total.value)
 
 
 class DeviceBuffer:

@@ -321,6 +321,87 @@ bool StompOptimizer::retargetBatch(const std::vector<StompOptimizer*>& optimizer
         [&](size_t p) { optimizers[p]->followRetarget(starts[p], goals[p], seeds[p]); });
 }
 
+// A queue of requests served by the optimizers as slots (stomp_group_serve): per request the slot,
+// the statistics (no torques) and the best trajectory; every optimizer that planned a request ends
+// as after retarget(its last request) + optimize().
+bool StompOptimizer::serveBatch(const std::vector<StompOptimizer*>& optimizers,
+                                const std::vector<std::vector<double>>& starts,
+                                const std::vector<std::vector<double>>& goals, const std::vector<uint64_t>& seeds,
+                                std::vector<ServeResult>& results)
+{
+    if (optimizers.empty() || !optimizers[0]) return false;
+    StompOptimizer* first = optimizers[0];
+    const size_t n = starts.size();
+    if (n == 0 || goals.size() != n || seeds.size() != n) {
+        first->error_ = "serveBatch: one start, goal and seed per request, and at least one request";
+        return false;
+    }
+    std::vector<stomp_engine*> engines;
+    int stride = 1;
+    for (StompOptimizer* o : optimizers) {
+        if (!o || !o->engine_) {
+            first->error_ = "serveBatch: an optimizer without an engine";
+            return false;
+        }
+        engines.push_back(o->engine_);
+        stride = std::max(stride, o->parameters_->max_iterations);
+    }
+    const int J = first->J_, N = first->N_;
+    std::vector<double> s, g;
+    for (size_t r = 0; r < n; ++r) {
+        if (!retargetSizes("serveBatch", starts[r], goals[r], J, first->error_)) return false;
+        s.insert(s.end(), starts[r].begin(), starts[r].end());
+        g.insert(g.end(), goals[r].begin(), goals[r].end());
+    }
+    stomp_group* grp = nullptr;
+    if (stomp_group_create_flags(engines.data(), (int32_t)engines.size(),
+                                 STOMP_GROUP_ACCEPT_STATE_TERMS | STOMP_GROUP_ACCEPT_CUMULATIVE, -1, &grp) != 0) {
+        first->error_ = stomp_last_error();
+        return false;
+    }
+    std::vector<stomp_serve_result> res(n);
+    std::vector<double> best(n * (size_t)J * N), costs(n * (size_t)stride, 0.0);
+    const int rc = stomp_group_serve(grp, s.data(), g.data(), seeds.data(), (int32_t)n, res.data(), best.data(),
+                                     costs.data(), stride);
+    if (rc != 0) first->error_ = stomp_group_last_error(grp);
+    stomp_group_destroy(grp);
+    if (rc != 0) return false;
+    results.assign(n, ServeResult());
+    std::vector<int> last(optimizers.size(), -1);
+    for (size_t r = 0; r < n; ++r) {
+        ServeResult& out = results[r];
+        const stomp_stats& st = res[r].stats;
+        out.slot = res[r].slot;
+        out.start_step = res[r].start_step;
+        out.stats.iterations = st.iterations;
+        out.stats.success = st.success != 0;
+        out.stats.success_iteration = st.success_iteration;
+        out.stats.collision_success_iteration = st.collision_success_iteration;
+        out.stats.last_improvement_iteration = st.last_improvement_iteration;
+        out.stats.best_cost = st.best_cost;
+        out.stats.success_duration = st.success_duration;
+        out.stats.collision_success_duration = st.collision_success_duration;
+        out.stats.costs.assign(costs.begin() + r * (size_t)stride, costs.begin() + r * (size_t)stride + st.iterations);
+        out.best_trajectory.assign(J, VectorXd(N));
+        for (int j = 0; j < J; ++j)
+            for (int t = 0; t < N; ++t) out.best_trajectory[j][t] = best[(r * J + j) * (size_t)N + t];
+        last[out.slot] = (int)r;
+    }
+    // every optimizer that planned: as after retarget(its last request) + optimize()
+    for (size_t p = 0; p < optimizers.size(); ++p) {
+        if (last[p] < 0) continue;
+        StompOptimizer* o = optimizers[p];
+        const size_t r = (size_t)last[p];
+        o->followRetarget(starts[r], goals[r], seeds[r]);
+        o->stats_.costs.assign(costs.begin() + r * (size_t)stride, costs.begin() + (r + 1) * (size_t)stride);
+        if (!o->finishOptimize(res[r].stats)) {
+            if (o != first) first->error_ = o->error_;
+            return false;
+        }
+    }
+    return true;
+}
+
 // the optimizer's own copies of the collision points and the constraints (createSibling reads
 // them through desc_) after a retarget that replaced them
 void StompOptimizer::followModel(const std::vector<stomp_sphere>* collision_points, const Constraints* constraints)
