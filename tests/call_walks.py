@@ -76,8 +76,79 @@ def scene_objects(p, extra):
     return objs
 
 
+def scene_static_layer(p, which):
+    """The static layers of the scene modes.  0: the problem's boxes; 1: one more box, near another
+    sphere of the default trajectory than scene_objects' extra one."""
+    objs = scene_objects(p, False)
+    if which:
+        at = pb.sphere_positions(p.robot, p.spheres, 0.5 * (p.start + p.goal))[(2 * len(p.spheres)) // 3]
+        objs.append(pb.SceneObject(pb.SHAPE_BOX, tuple(at + np.array([-0.04, 0.03, 0.06])), (0.0, 0.0, 0.0, 1.0),
+                                   (0.08, 0.1, 0.06)))
+    return objs
+
+
+def scene_dynamic_set(p, variant):
+    """The dynamic sets of the scene modes: none; scene_objects' box beside the default trajectory; that
+    box moved; a body outside the grid (no mark lands: the static field)."""
+    name = DYNAMIC_VARIANTS[variant]
+    if name == "none":
+        return []
+    if name == "outside":
+        g = p.grid
+        far = np.array(g.origin) + (np.array(g.dims) + 40) * g.resolution
+        return [pb.SceneObject(pb.BODY_BOX, tuple(far), dims=(0.2, 0.2, 0.2))]
+    box = scene_objects(p, True)[-1]
+    if name == "moved_box":
+        box = dataclasses.replace(box, position=tuple(np.array(box.position) + np.array([0.05, 0.04, -0.03])))
+    return [box]
+
+
 def has_terms(p):
     return bool(p.orientation_constraints) or p.params.torque_cost_weight > 1e-9
+
+
+def request_spheres(p, choice):
+    """The sphere list of a request on problem p.  attach: one more sphere on the tree's last segment,
+    after that segment's own (what attached_collision_points makes of a sphere body of radius 0.05 at
+    (0.03, 0, 0.02), as test_gpu_request_model.attach does; built here from pb.Sphere so that the
+    CPU tests need no library).  radius_only: every radius and clearance changed, the layout kept."""
+    if choice == "base":
+        return list(p.spheres)
+    if choice == "radius_only":
+        cap = p.grid.max_expansion
+        return [dataclasses.replace(s, radius=s.radius * 0.8, clearance=min(s.clearance * 1.3, cap - s.radius * 0.8))
+                for s in p.spheres]
+    assert choice == "attach", choice
+    seg, radius = len(p.robot.segments) - 1, 0.05
+    clearance = min(0.05, p.grid.max_expansion - radius)
+    assert clearance > 0.0
+    new = pb.Sphere(seg, radius, clearance, (0.03, 0.0, 0.02))
+    return [s for s in p.spheres if s.segment <= seg] + [new] + [s for s in p.spheres if s.segment > seg]
+
+
+def group_request_spheres(p, choice, m):
+    """request_spheres for member m of a group: the same layouts, the attached sphere's values the
+    member's own (test_gpu_request_group.requests)"""
+    out = request_spheres(p, choice)
+    if choice == "attach":
+        i = max(i for i, s in enumerate(out) if s.segment == len(p.robot.segments) - 1)
+        out[i] = dataclasses.replace(out[i], radius=0.04 + 0.005 * m, pos=(0.03 - 0.01 * m, 0.0, 0.02),
+                                     clearance=min(0.05, p.grid.max_expansion - (0.04 + 0.005 * m)))
+    return out
+
+
+def assert_attach_matters(p):
+    """On the oracle alone (test_gpu_request_model.assert_edit_matters): the attached sphere changes
+    iteration 1's state costs, so a request that silently kept the old spheres cannot pass."""
+    a, b = po.Oracle(dataclasses.replace(p, spheres=request_spheres(p, "attach"))), po.Oracle(p)
+    a.iterate(1)
+    b.iterate(1)
+    differ = int(np.sum(np.any(a.rollouts("state_costs") != b.rollouts("state_costs"), axis=1)))
+    assert differ >= 1, "the attached sphere changes no state cost of iteration 1"
+    for choice in ("radius_only",):
+        c = po.Oracle(dataclasses.replace(p, spheres=request_spheres(p, choice)))
+        c.iterate(1)
+        assert not np.array_equal(c.rollouts("state_costs"), b.rollouts("state_costs")), choice
 
 
 # ---------------------------------------------------------------------------- modes
@@ -111,6 +182,32 @@ def _group_mixed():
 
 def _ranks():
     return mz.chain5(K=128, Kr=0, max_iterations=3, max_iterations_after_collision_free=1000)
+
+
+def _request(K, Kr, **kw):
+    """fork12 with inertias, torque weight 0 and no constraints: the terms launch starts off"""
+    return lambda: mz.TERMS_ZOO["fork12_base"](torque=0.0, constrained=False, K=K, Kr=Kr, max_iterations=4,
+                                               max_iterations_after_collision_free=1000, **kw)
+
+
+def _group_request():
+    """Three fork12 problems with inertias (no torque term, no constraints), own start / goal / seed and
+    max_iterations 3 .. 5, engine 1 with cumulative costs (test_gpu_request_group.base_problems)"""
+    p = _request(12, 5)()
+    return [dataclasses.replace(moved(p, 60 + i), params=dataclasses.replace(p.params, max_iterations=3 + i,
+                                                                             use_cumulative_costs=i == 1)) for i in range(3)]
+
+
+def _group_shelf():
+    """Four copies of the PR2 shelf fixture at the zoo's shape (test_gpu_retarget.shelf(Kr=5)), max_iterations 3 .. 6"""
+    return [pb.make_problem(waypoints=40, num_rollouts=12, num_reused_rollouts=5, max_iterations=3 + i,
+                            max_iterations_after_collision_free=2) for i in range(4)]
+
+
+def _shelf_targets():
+    """(base, A, B) of test_gpu_retarget.flag_pair: A's padding poses alone collide, B is free"""
+    from tests.test_gpu_retarget import flag_pair
+    return flag_pair()
 
 
 # kind: "single" / "group" / "ranks"; make: the problem(s); env: set before creation; expect: pieces
@@ -150,6 +247,36 @@ MODES = {
                            expect=["launch of 65 rollouts: "]),
     "ranks_gather": dict(kind="ranks", make=_ranks, env={}, shard="gather", threads=8, length=20,
                          expect=["launch of 65 rollouts: "]),
+    # ---- modes added after the 16 above were frozen (IDENTS): new op kinds belong to these alone
+    "request_reuse": dict(kind="single", make=_request(12, 5), env={}, request=True, threads=8,
+                          expect=["J 12 N 39 ", "launch of 13 rollouts: "]),
+    "request_pregen_cum": dict(kind="single", make=_request(20, 0, use_cumulative_costs=True), env={}, request=True,
+                               threads=8, expect=["J 12 N 39 ", "launch of 21 rollouts: "]),
+    "scene_linear": dict(kind="single", make=_chain5(12, 5, 4, shape=(66, 66, 66)), env={"STOMP_SDF_LAYOUT": "linear"},
+                         scene=True, expect=["brick 0,"]),
+    "scene_brick": dict(kind="single", make=_chain5(12, 5, 4, shape=(66, 66, 66)), env={"STOMP_SDF_LAYOUT": "brick"},
+                        scene=True, expect=["brick 1,"]),
+    "group_request": dict(kind="group", make=_group_request, env={}, request=True, threads=8, length=30,
+                          group=dict(state_terms=True, cumulative_costs=True),
+                          expect=["group of 3 engines J 12 N 39 K 12 ", "engines with terms 0 of 3",
+                                  "engines with cumulative costs 1 of 3"]),
+    "group_serve_reuse": dict(kind="group", make=_group_plain(12, 5), env={}, serve=True,
+                              expect=["group of 4 engines J 5 N 39 K 12 "]),
+    "group_serve_pregen": dict(kind="group", make=_group_plain(20, 0), env={}, serve=True,
+                               expect=["group of 4 engines J 5 N 39 K 20 "]),
+    "group_serve_shelf": dict(kind="group", make=_group_shelf, env={}, serve=True, targets=_shelf_targets, threads=8,
+                              length=30, info=dict(P=4, Kr=5, cums=[False] * 4, max_its=[3, 4, 5, 6]),
+                              expect=["group of 4 engines J 7 N 39 K 12 "]),
+}
+# make_script seeds its generator with a mode's ident.  The first 16 are the modes' indices in
+# sorted order at the time the walks were written, frozen: a new mode must not move an old script.
+IDENTS = {
+    "device_brick": 0, "group_mixed": 1, "group_mixed_compact": 2, "group_pregen": 3, "group_reuse": 4, "phased": 5,
+    "pregen": 6, "ranks_gather": 7, "ranks_partials": 8, "reuse_fused": 9, "reuse_no_pick_fuse": 10, "reuse_no_spec": 11,
+    "slot_loop": 12, "slot_loop_lean": 13, "terms_cum": 14, "unfused": 15,
+    "request_reuse": 16, "request_pregen_cum": 17, "scene_linear": 18, "scene_brick": 19, "group_request": 20,
+    "group_serve_reuse": 21, "group_serve_pregen": 22,
+    "group_serve_shelf": 23,
 }
 DEFAULT_LENGTH = 40
 # scripts per mode: see tests/CALL_WALKS.md for how they were found (test_call_walks.py asserts that
@@ -158,6 +285,9 @@ SEEDS = {
     "reuse_fused": 12, "reuse_no_spec": 14, "reuse_no_pick_fuse": 12, "pregen": 13, "unfused": 13, "slot_loop": 28,
     "slot_loop_lean": 25, "phased": 18, "terms_cum": 15, "device_brick": 16, "group_reuse": 5, "group_pregen": 4,
     "group_mixed": 18, "group_mixed_compact": 8, "ranks_partials": 4, "ranks_gather": 4,
+    "request_reuse": 16, "request_pregen_cum": 25, "scene_linear": 20, "scene_brick": 16, "group_request": 20,
+    "group_serve_reuse": 12, "group_serve_pregen": 21,
+    "group_serve_shelf": 22,
 }
 
 
@@ -171,6 +301,13 @@ STEP = ("pi_get_rollouts", "pi_set_rollout_costs", "pi_improve_policy", "pi_add_
 NEUTRAL = ("observe", "execute", "set_timing", "refuse")     # ops that change no state the model has
 SINGLE_KINDS = FUSED + ("synchronize", "observe", "set_theta", "execute") + STEP + ("retarget", "set_timing", "refuse")
 REFUSALS = ("nan_goal", "extra_num0", "null_sigma")
+# the request modes: retarget_request(k, keep_seed, spheres, constraints) and two more refusals
+REQUEST_REFUSALS = REFUSALS + ("unordered_spheres", "bad_segment")
+SPHERE_CHOICES = ("keep", "attach", "base", "radius_only")
+CONSTRAINT_CHOICES = ("keep", 0, 1, 2)
+# the scene modes: the field belongs to a scene of two layers on the engine's stream
+SCENE_KINDS = ("scene_dynamic", "scene_static")
+DYNAMIC_VARIANTS = ("none", "box", "moved_box", "outside")
 
 
 class Book:
@@ -187,7 +324,10 @@ class Book:
     def __init__(self, problem_info):
         self.Kr, self.cum, self.device = problem_info["Kr"], problem_info["cum"], problem_info.get("device", False)
         self.max_it = problem_info["max_it"]
-        self.kinds = SINGLE_KINDS + (("refresh_field",) if self.device else ())
+        self.request, self.scene = problem_info.get("request", False), problem_info.get("scene", False)
+        self.kinds = (SINGLE_KINDS + (("refresh_field",) if self.device else ()) + (("retarget_request",) if self.request else ())
+                      + (SCENE_KINDS if self.scene else ()))
+        self.refusals = REQUEST_REFUSALS if self.request else REFUSALS
         self.reset()
 
     def reset(self):
@@ -207,6 +347,10 @@ class Book:
             return self.phase == "costed"
         if kind == "refresh_field":
             return self.device and not self.pending
+        if kind == "scene_check":
+            return self.scene
+        if kind in SCENE_KINDS:     # (refresh_field's rule: the pending noiseless rollout would read the new field)
+            return self.scene and not self.pending
         return kind in self.kinds
 
     def _iterated(self):
@@ -255,7 +399,9 @@ class Book:
         elif kind == "pi_add_extra_rollout":
             self.pending = False
             self.valid |= set(X_KEYS)
-        elif kind == "retarget":
+        elif kind in ("retarget", "retarget_request"):
+            if kind == "retarget_request":
+                assert op[3] in SPHERE_CHOICES and op[4] in CONSTRAINT_CHOICES, op
             box = self.extra_box
             self.reset()
             self.extra_box = box
@@ -263,12 +409,21 @@ class Book:
             assert op[1] != self.extra_box, "one more or one fewer box"
             self.extra_box = op[1]
         elif kind == "refuse":
-            assert op[1] in REFUSALS
+            assert op[1] in self.refusals
+        elif kind == "scene_dynamic":
+            assert op[1] in range(len(DYNAMIC_VARIANTS)), op
+        elif kind == "scene_static":
+            assert op[1] in (0, 1), op
+        elif kind == "scene_check":     # (final_observe's: not in the alphabet)
+            assert self.scene
         else:
             assert kind in ("execute", "set_timing", "pi_reset"), kind
 
     def final_observe(self):
         return ("observe", tuple(k for k in OBS_ORDER if k in self.valid))
+
+    def final_ops(self):
+        return [self.final_observe()] + ([("scene_check",)] if self.scene else [])
 
 
 def _single_op(book, kind, rng):
@@ -301,11 +456,25 @@ def _single_op(book, kind, rng):
     if kind == "set_timing":
         return ("set_timing", bool(rng.random() < 0.5))
     if kind == "refuse":
-        return ("refuse", REFUSALS[int(rng.integers(len(REFUSALS)))])
+        return ("refuse", book.refusals[int(rng.integers(len(book.refusals)))])
+    if kind == "scene_dynamic":
+        return ("scene_dynamic", int(rng.integers(len(DYNAMIC_VARIANTS))))
+    if kind == "scene_static":
+        return ("scene_static", int(rng.integers(2)))
+    if kind == "retarget_request":
+        return ("retarget_request", int(rng.integers(1, 50)), bool(rng.random() < 0.3),
+                SPHERE_CHOICES[int(rng.integers(4))], CONSTRAINT_CHOICES[int(rng.integers(4))])
     return (kind,)
 
 
 # ---------------------------------------------------------------------------- group bookkeeping
+GROUP_REQUEST_KINDS = ("g_retarget_requests", "m_retarget_request", "g_refused_model")
+
+
+def _layout(choice):
+    """the sphere layout a request's choice gives: radius_only keeps the base list's"""
+    return "attach" if choice == "attach" else "base"
+
 GROUP_KINDS = ("g_run", "g_run_refused", "g_synchronize", "g_optimize", "g_retarget", "observe", "m_set_theta",
                "m_execute", "m_retarget", "m_iterate")
 
@@ -318,7 +487,14 @@ class GroupBook:
 
     def __init__(self, info):
         self.P, self.Kr, self.cums, self.max_its = info["P"], info["Kr"], info["cums"], info["max_its"]
-        self.kinds = GROUP_KINDS
+        self.serve = info.get("serve", False)
+        self.request = info.get("request", False)
+        self.kinds = GROUP_KINDS + (("g_serve",) if self.serve else ()) + (GROUP_REQUEST_KINDS if self.request else ())
+        # the request mode: members that replaced a list of their model on their own since the last
+        # g_retarget_requests (the group's copies of the models are behind them), and every
+        # member's sphere layout (the engines a group plans are of one shape)
+        self.stale, self.layout = set(), ["base"] * info["P"]
+        self.split = False    # a g_serve of fewer requests than slots left the members in different states
         self.sig = [(-1, -1, False) for _ in range(self.P)]     # (pending member, pre_it, reused_next = extra_added)
         self.valid = [set(ALWAYS) for _ in range(self.P)]
         self.next_it = 1
@@ -333,10 +509,16 @@ class GroupBook:
         return [m for m in range(self.P) if self.sig[m] != self.sig[self.lead[0]]] if self.lead else []
 
     def allowed(self, kind):
+        if kind == "g_refused_model":
+            return self.request and bool(self.stale)
+        if self.stale and kind in ("g_run", "g_run_refused", "g_synchronize", "g_optimize", "g_retarget", "g_serve"):
+            return False      # refused until a g_retarget_requests (g_refused_model asserts it)
+        if kind == "m_retarget_request":
+            return self.request and self.lead is None      # (as m_retarget)
         if kind == "g_run":
             return self.lockstep()
         if kind == "g_run_refused":
-            return self.lead is not None and not self.lockstep() and not self.refused
+            return (self.lead is not None or self.split) and not self.lockstep() and not self.refused
         if kind == "g_optimize":
             return self.lockstep()
         if kind == "m_iterate":
@@ -371,7 +553,22 @@ class GroupBook:
                 self.sig[m] = (-1, -1, reuse)
                 self._iterated(m)
             self.next_it, self.lead = max(self.max_its) + 1, None
-        elif kind == "g_retarget":
+        elif kind == "g_serve":
+            # slots 0 .. min(n, P) - 1 are as after g_optimize; the others keep their state
+            n = op[2]
+            assert self.serve and n >= 1, op      # (the generator draws 1 .. 2P + 2; a literal script may queue more)
+            for m in range(min(n, self.P)):
+                self.sig[m] = (-1, -1, reuse)
+                self._iterated(m)
+            self.lead, self.refused = None, False
+            if self.lockstep():
+                self.next_it = max(self.max_its) + 1
+        elif kind in ("g_retarget", "g_retarget_requests"):
+            if kind == "g_retarget_requests":
+                assert len(op[3]) == self.P and all(s in SPHERE_CHOICES and c in CONSTRAINT_CHOICES for s, c in op[3]), op
+                self.layout = [self.layout[m] if s == "keep" else _layout(s) for m, (s, _) in enumerate(op[3])]
+                assert len(set(self.layout)) == 1, (op, self.layout)
+                self.stale = set()
             self.sig = [(-1, -1, False) for _ in range(self.P)]
             self.valid = [set(ALWAYS) for _ in range(self.P)]
             self.next_it, self.lead = 1, None
@@ -383,7 +580,13 @@ class GroupBook:
                     self.sig[m] = (-1,) + self.sig[m][1:]
         elif kind == "m_set_theta":
             self.sig[op[1]] = (-1,) + self.sig[op[1]][1:]
-        elif kind == "m_retarget":
+        elif kind in ("m_retarget", "m_retarget_request"):
+            if kind == "m_retarget_request":
+                assert op[4] in SPHERE_CHOICES and op[5] in CONSTRAINT_CHOICES, op
+                if (op[4], op[5]) != ("keep", "keep"):      # (both lists kept: the plain path, no model change)
+                    self.stale.add(op[1])
+                if op[4] != "keep":
+                    self.layout[op[1]] = _layout(op[4])
             self.sig[op[1]] = (-1, -1, False)
             self.valid[op[1]] = set(ALWAYS)
         elif kind == "m_iterate":
@@ -397,12 +600,14 @@ class GroupBook:
             if self.lockstep():
                 self.next_it, self.lead = it + 1, None
         else:
-            assert kind == "m_execute", kind
+            assert kind in ("m_execute", "g_refused_model"), kind
         if self.lead is not None and self.lockstep():
             self.lead = None
+        if kind == "g_serve" or self.lockstep():
+            self.split = not self.lockstep()
 
     def final_ops(self):
-        ops = [("g_synchronize",)]
+        ops = [("g_refused_model",) if self.stale else ("g_synchronize",)]
         for m in range(self.P):
             ops.append(("observe", m, tuple(k for k in OBS_ORDER if k in self.valid[m])))
         return ops
@@ -416,6 +621,21 @@ def _group_op(book, kind, rng):
         return (kind, first, int(rng.integers(1, 5)))
     if kind == "g_retarget":
         return ("g_retarget", int(rng.integers(1, 50)), bool(rng.random() < 0.3))
+    if kind == "g_serve":
+        return ("g_serve", int(rng.integers(1 << 20)), int(rng.integers(1, 2 * P + 3)))
+    if kind == "g_retarget_requests":
+        # one layout for the group: a member may keep its list only if it has that layout already
+        attach = bool(rng.random() < 0.5)
+        choices = []
+        for i in range(P):
+            opts = ["attach"] if attach else ["base", "radius_only"]
+            if book.layout[i] == ("attach" if attach else "base"):
+                opts.append("keep")
+            choices.append((opts[int(rng.integers(len(opts)))], CONSTRAINT_CHOICES[int(rng.integers(4))]))
+        return ("g_retarget_requests", int(rng.integers(1, 50)), bool(rng.random() < 0.3), tuple(choices))
+    if kind == "m_retarget_request":
+        return ("m_retarget_request", m, int(rng.integers(1, 50)), bool(rng.random() < 0.3),
+                SPHERE_CHOICES[int(rng.integers(4))], CONSTRAINT_CHOICES[int(rng.integers(4))])
     if kind == "observe":
         who = -1 if rng.random() < 0.3 else m
         common = set.intersection(*book.valid) if who < 0 else book.valid[who]
@@ -473,14 +693,18 @@ def mode_info(mode):
     """What the bookkeeping needs of a mode's problems (built once: generation reads them only)."""
     if mode not in _INFO:
         spec = MODES[mode]
+        if "info" in spec:      # (a mode whose problems are slow to build says what its book needs)
+            _INFO[mode] = dict(spec["info"], serve=spec.get("serve", False))
+            return _INFO[mode]
         made = spec["make"]()
         if spec["kind"] == "group":
-            _INFO[mode] = dict(P=len(made), Kr=made[0].params.num_reused_rollouts,
+            _INFO[mode] = dict(serve=spec.get("serve", False), request=spec.get("request", False), P=len(made), Kr=made[0].params.num_reused_rollouts,
                                cums=[bool(p.params.use_cumulative_costs) for p in made],
                                max_its=[p.params.max_iterations for p in made])
         else:
             _INFO[mode] = dict(Kr=made.params.num_reused_rollouts, cum=bool(made.params.use_cumulative_costs),
-                               max_it=made.params.max_iterations, device=spec.get("device_field", False))
+                               max_it=made.params.max_iterations, device=spec.get("device_field", False),
+                               request=spec.get("request", False), scene=spec.get("scene", False))
     return _INFO[mode]
 
 
@@ -528,7 +752,7 @@ def make_script(mode, seed, length=None):
     the pairs of op kinds the ones before it showed (kept per process; the result depends on the
     arguments alone)."""
     length = length_of(mode) if length is None else length
-    ident = sorted(MODES).index(mode)
+    ident = IDENTS[mode]
     made, seen = _SCRIPTS.setdefault((mode, length), ([], set()))
     while len(made) <= seed:
         made.append(_walk(mode, np.random.default_rng([ident, len(made), length]), length, seen))
@@ -545,7 +769,7 @@ def final_ops(mode, script):
         return book.final_ops()
     if MODES[mode]["kind"] == "ranks":
         return [("synchronize",), book.final_observe()]
-    return [book.final_observe()]
+    return book.final_ops()
 
 
 # Ordered pairs of kinds that no valid script holds, with the rule that excludes them.  The census
@@ -557,6 +781,9 @@ def impossible_pairs(mode):
         kinds = kinds_of(mode)
         opens = ("pi_get_rollouts", "pi_set_rollout_costs")     # leave a step round open
         closes = FUSED + ("pi_improve_policy", "pi_add_extra_rollout", "retarget")   # leave it closed
+        if "retarget_request" in kinds:      # the book treats it as retarget
+            closes += ("retarget_request",)
+            out[("retarget_request", "pi_add_extra_rollout")] = "a fresh PolicyImprovement has no control cost weight yet"
         for a in opens:
             for b in FUSED + ("pi_get_rollouts", "pi_add_extra_rollout"):
                 out[(a, b)] = "between pi_get_rollouts and pi_improve_policy the oracle's rows hold no control costs yet"
@@ -567,6 +794,9 @@ def impossible_pairs(mode):
         out[("retarget", "pi_add_extra_rollout")] = "a fresh PolicyImprovement has no control cost weight yet"
         if "refresh_field" in kinds:
             out[("run", "refresh_field")] = "the pending noiseless rollout would read the new field"
+        for b in SCENE_KINDS:
+            if b in kinds:
+                out[("run", b)] = "the pending noiseless rollout would read the new field"
     elif kind == "group":
         for b in ("g_run", "g_optimize"):
             out[("g_run_refused", b)] = "the group is out of lockstep until every member has followed the leader"
@@ -575,6 +805,22 @@ def impossible_pairs(mode):
         out[("g_run_refused", "g_run_refused")] = "one refused run per excursion"
         for pair in (("g_run_refused", "m_retarget"), ("m_retarget", "g_run_refused")):
             out[pair] = "no member retargets while the others still follow a member's own iterate"
+        if "g_refused_model" in kinds_of(mode):
+            level = ("g_run", "g_synchronize", "g_optimize", "g_retarget", "g_retarget_requests")
+            for a in level:
+                out[(a, "g_refused_model")] = "the call was accepted: no member's model is ahead of the group's copy"
+            for b in ("g_run", "g_run_refused", "g_synchronize", "g_optimize", "g_retarget"):
+                out[("g_refused_model", b)] = "a member's model stays ahead of the group's copy until g_retarget_requests"
+            out[("g_run_refused", "g_refused_model")] = "a run refused for the iteration state was not refused for a model"
+            out[("g_retarget_requests", "g_run_refused")] = "a refused run needs a member ahead of the others"
+            for pair in (("g_run_refused", "m_retarget_request"), ("m_retarget_request", "g_run_refused")):
+                out[pair] = "no member retargets while the others still follow a member's own iterate"
+        if "g_serve" in kinds_of(mode):
+            # a g_serve of fewer requests than slots leaves members in different states with no
+            # leader to follow: a refused run may follow it, and a member's retarget may stand on
+            # either side of that refused run.  g_serve itself is accepted in every state, and
+            # every kind can follow one (n >= P levels the group, n < P may split it): no new pair
+            del out[("g_run_refused", "m_retarget")], out[("m_retarget", "g_run_refused")]
     return out
 
 
@@ -618,9 +864,12 @@ def _assert_execute(e, want, rows, member, terms, tag):
 class Pair:
     """One engine (None: the oracle alone, for the CPU tests) and its oracle."""
 
-    def __init__(self, problem, engine=None, threads=1, field=None):
+    def __init__(self, problem, engine=None, threads=1, field=None, scene=None, stream=None, brick=False):
         self.p0 = self.p = problem
         self.e, self.threads, self.field = engine, threads, field
+        # a scene mode: the field is the scene's, on the stream it shares with the engine
+        self.scene, self.stream, self.brick = scene, stream, brick
+        self.layer, self.dynamic, self.fields = 0, 0, {}
         self.cur_sdf = np.array(problem.sdf, np.uint16)
         self.o = self._oracle(problem)
         self.it, self.K_gen = 1, problem.params.num_rollouts
@@ -632,8 +881,12 @@ class Pair:
     def close(self):
         if self.e is not None:
             self.e.close()
+        if self.scene is not None:
+            self.scene.close()
         if self.field is not None:
             self.field.free()
+        if self.stream is not None:
+            self.stream.close()
 
     # -------------------------------------------------------------- ops
     def op_iterate(self, it):
@@ -722,12 +975,43 @@ class Pair:
             _assert_stats(self.e.optimize(), ro, "optimize")
 
     def op_retarget(self, k, keep_seed):
-        q = moved(self.p0, k)
+        # (a plain retarget keeps the model a request gave the engine)
+        q = dataclasses.replace(moved(self.p0, k), spheres=list(self.p.spheres),
+                                orientation_constraints=list(self.p.orientation_constraints))
         if keep_seed:
             q = dataclasses.replace(q, seed=self.p.seed)
         if self.e is not None:
             self.e.retarget(q.start, q.goal, None if keep_seed else q.seed)
             assert self.e.problem.seed == q.seed
+        self.p = q
+        self.o = self._oracle(q)
+        self.it, self.K_gen = 1, q.params.num_rollouts
+
+    def op_retarget_request(self, k, keep_seed, spheres, constraints):
+        q = moved(self.p0, k)
+        if keep_seed:
+            q = dataclasses.replace(q, seed=self.p.seed)
+        sph = None if spheres == "keep" else request_spheres(self.p0, spheres)
+        oc = None if constraints == "keep" else mz.fork12_constraints()[:constraints]
+        q = dataclasses.replace(q, spheres=list(self.p.spheres if sph is None else sph),
+                                orientation_constraints=list(self.p.orientation_constraints if oc is None else oc))
+        e = self.e
+        if e is not None:
+            seed = None if keep_seed else q.seed
+            if sph is None and oc is None:
+                # both lists kept: the plain path, through the request's entry point
+                s, g = np.ascontiguousarray(q.start, np.float64), np.ascontiguousarray(q.goal, np.float64)
+                req, _ = e._request(s, g, int(q.seed), None, None)
+                assert req.num_spheres == -1 and req.num_orientation_constraints == -1
+                rc = eng.load_library().stomp_engine_retarget_request(e.h, C.byref(req))
+                assert rc == 0, (rc, eng.load_library().stomp_last_error())
+                e._follow(s, g, int(q.seed))
+            else:
+                e.retarget(q.start, q.goal, seed, spheres=sph, orientation_constraints=oc)
+            info = e.model_info()
+            assert e.problem.seed == q.seed and e.S == len(q.spheres) == info["S"], (e.S, len(q.spheres), info)
+            assert info["orientation_constraints"] == len(q.orientation_constraints), info
+            assert info["terms_on"] == int(has_terms(q)), info
         self.p = q
         self.o = self._oracle(q)
         self.it, self.K_gen = 1, q.params.num_rollouts
@@ -745,6 +1029,43 @@ class Pair:
         self.cur_sdf = new.copy()
         self.o.refresh_field(new)
 
+    def scene_field(self, layer, dynamic):
+        """the oracle's full build of a static layer and a dynamic set (kept: a walk returns to them)"""
+        if (layer, dynamic) not in self.fields:
+            objs = scene_static_layer(self.p0, layer) + scene_dynamic_set(self.p0, dynamic)
+            self.fields[(layer, dynamic)] = po.sdf_build_objects(self.p0.grid, objs)[0]
+        return self.fields[(layer, dynamic)]
+
+    def _scene_changed(self, layer, dynamic):
+        # whether the field changes is known from the inputs: no mark of `none` and `outside` lands
+        empty = ("none", "outside")
+        same = layer == self.layer and (dynamic == self.dynamic or
+                                        (DYNAMIC_VARIANTS[dynamic] in empty and DYNAMIC_VARIANTS[self.dynamic] in empty))
+        new = self.scene_field(layer, dynamic)
+        assert np.array_equal(new, self.cur_sdf) == same, "the scene must change" if not same else "the scene must stay"
+        self.layer, self.dynamic = layer, dynamic
+        if self.e is not None and self.brick:
+            self.e.refresh_field()      # the header's contract: the bricked copy follows the caller's buffer
+        self.cur_sdf = new.copy()
+        self.o.refresh_field(new.copy())
+
+    def op_scene_dynamic(self, variant):
+        if self.e is not None:
+            self.scene.set_dynamic(scene_dynamic_set(self.p0, variant))      # enqueued: nothing waits
+        self._scene_changed(self.layer, variant)
+
+    def op_scene_static(self, which):
+        if self.e is not None:
+            self.scene.set_static(scene_static_layer(self.p0, which))        # drops the dynamic set
+        self._scene_changed(which, 0)
+
+    def op_scene_check(self):
+        if self.e is not None:
+            info = self.scene.info()        # waits for the scene's stream
+            assert info["stray"] == 0, info
+            np.testing.assert_array_equal(self.field.to_numpy(np.uint16, tuple(self.p0.grid.dims)), self.cur_sdf,
+                                          err_msg="the scene's buffer against the oracle's field")
+
     def op_set_timing(self, on):
         if self.e is not None:
             self.e.set_timing(on)
@@ -760,6 +1081,19 @@ class Pair:
             goal[self.p.J // 2] = np.nan
             _expect_refusal(lambda: e.retarget(self.p.start, goal), -1, "not finite")
             assert e.problem is before
+        elif what in ("unordered_spheres", "bad_segment"):
+            # a refused request: nothing of the engine is written, and the staging it shares with
+            # the plain retarget stays usable by the next accepted call of either kind
+            before, info = e.problem, e.model_info()
+            bad = list(request_spheres(self.p0, "attach"))
+            if what == "unordered_spheres":
+                bad = bad[::-1]
+                assert [s.segment for s in bad] != sorted(s.segment for s in bad)
+                _expect_refusal(lambda: e.retarget(self.p.start, self.p.goal, spheres=bad), -3, "ordered by segment")
+            else:
+                bad[3] = dataclasses.replace(bad[3], segment=len(self.p.robot.segments))
+                _expect_refusal(lambda: e.retarget(self.p.start, self.p.goal, spheres=bad), -1, "bad segment")
+            assert e.problem is before and e.model_info() == info
         elif what == "extra_num0":
             th = np.ascontiguousarray(self.o.theta())
             assert l.stomp_pi_add_extra_rollouts(e.h, 0, eng._dp(th), eng._dp(np.zeros(self.p.N))) == -1
@@ -783,10 +1117,13 @@ class Pair:
 class GroupPair:
     """A group on one stream, twins that make the equivalent single-engine calls, and the oracles."""
 
-    def __init__(self, problems, threads=1, **group_kw):
+    def __init__(self, problems, threads=1, targets=None, **group_kw):
         self.ps0 = list(problems)
         self.ps = list(problems)
         self.threads = threads
+        self.targets = targets      # problems whose start / goal every retarget and request draws from (None: moved())
+        self.served = None          # the last g_serve's (requests, results)
+        self.stale = set()          # members that replaced a list of their model on their own
         self.g = gu.Group(self.ps, **group_kw)
         self.twins = gu.twins_of(self.ps)
         self.os = [po.Oracle(p, threads=threads) for p in self.ps]
@@ -823,8 +1160,109 @@ class GroupPair:
             _assert_stats(r, t.optimize(), f"engine {i} against its twin,")
 
     def _moved(self, m, k, keep_seed):
-        q = moved(self.ps0[m], k + 50 * m)
+        if self.targets:
+            t = self.targets[(k + m) % len(self.targets)]
+            q = dataclasses.replace(self.ps0[m], start=t.start.copy(), goal=t.goal.copy(), seed=t.seed + 2000 + k + 50 * m)
+        else:
+            q = moved(self.ps0[m], k + 50 * m)
+        # (a plain retarget keeps the model a request gave the engine)
+        q = dataclasses.replace(q, spheres=list(self.ps[m].spheres), orientation_constraints=list(self.ps[m].orientation_constraints))
         return dataclasses.replace(q, seed=self.ps[m].seed) if keep_seed else q
+
+    def _queue(self, seed, n, which):
+        """n requests as (start, goal, seed), drawn from the op's seed (which: the targets' indices given)"""
+        rng = np.random.default_rng(seed)
+        out = []
+        for r in range(n):
+            if self.targets:
+                t = self.targets[int(rng.integers(len(self.targets))) if which is None else which[r]]
+                out.append((t.start.copy(), t.goal.copy(), int(t.seed + rng.integers(1, 1 << 16))))
+            else:
+                q = moved(self.ps0[r % len(self.ps0)], int(rng.integers(1, 1000)))
+                out.append((q.start, q.goal, int(q.seed)))
+        return out
+
+    def _lists(self, m, spheres, constraints):
+        """(sphere list, constraint list) of a request's choices for member m; None: kept"""
+        sph = None if spheres == "keep" else group_request_spheres(self.ps0[m], spheres, m)
+        oc = None if constraints == "keep" else mz.fork12_constraints()[:constraints]
+        return sph, oc
+
+    def _requested(self, m, k, keep_seed, sph, oc):
+        q = self._moved(m, k, keep_seed)
+        return dataclasses.replace(q, spheres=list(q.spheres if sph is None else sph),
+                                   orientation_constraints=list(q.orientation_constraints if oc is None else oc))
+
+    def _assert_model(self, m, q):
+        for x, tag in ((self.g.engines[m], "engine"), (self.twins[m], "twin")):
+            info = x.model_info()
+            assert x.problem.seed == q.seed and x.S == len(q.spheres) == info["S"], (tag, m, info)
+            assert info["orientation_constraints"] == len(q.orientation_constraints), (tag, m, info)
+            assert info["terms_on"] == int(has_terms(q)), (tag, m, info)
+
+    def op_g_retarget_requests(self, k, keep_seed, choices):
+        P = len(self.ps)
+        lists = [self._lists(m, *choices[m]) for m in range(P)]
+        qs = [self._requested(m, k, keep_seed, *lists[m]) for m in range(P)]
+        # (lists of None entries, never None itself: every request through stomp_group_retarget_requests)
+        self.g.group.retarget([q.start for q in qs], [q.goal for q in qs], None if keep_seed else [q.seed for q in qs],
+                              spheres=[l[0] for l in lists], orientation_constraints=[l[1] for l in lists])
+        for m, q in enumerate(qs):
+            self.twins[m].retarget(q.start, q.goal, q.seed, spheres=lists[m][0], orientation_constraints=lists[m][1])
+            self._assert_model(m, q)
+            self.os[m] = po.Oracle(q, threads=self.threads)
+        self.ps = qs
+        self.stale = set()
+
+    def op_m_retarget_request(self, m, k, keep_seed, spheres, constraints):
+        sph, oc = self._lists(m, spheres, constraints)
+        q = self._requested(m, k, keep_seed, sph, oc)
+        for x in (self.g.engines[m], self.twins[m]):
+            x.retarget(q.start, q.goal, None if keep_seed else q.seed, spheres=sph, orientation_constraints=oc)
+        self._assert_model(m, q)
+        self.os[m] = po.Oracle(q, threads=self.threads)
+        self.ps[m] = q
+        if sph is not None or oc is not None:
+            self.stale.add(m)
+
+    def op_g_refused_model(self):
+        assert self.stale
+        first = min(self.stale)
+        ps = self.ps
+        calls = [lambda: self.g.group.run(1, 1), self.g.group.synchronize, self.g.group.optimize,
+                 lambda: self.g.group.retarget([p.start for p in ps], [p.goal for p in ps])]
+        for call in calls:
+            _expect_refusal(call, -1, f"engine {first} of the group")
+        for m, p in enumerate(ps):      # (the refused plain retarget followed nothing)
+            assert self.g.engines[m].problem.seed == p.seed
+
+    def op_g_serve(self, seed, n, which=None):
+        P = len(self.ps)
+        assert which is None or len(which) == n
+        reqs = self._queue(seed, n, which)
+        results = self.g.group.serve([r[0] for r in reqs], [r[1] for r in reqs], [r[2] for r in reqs])
+        assert len(results) == n
+        its, last = [], {}
+        for r, (res, (start, goal, sd)) in enumerate(zip(results, reqs)):
+            slot = res[0]
+            assert 0 <= slot < P, (r, slot)
+            # the planning slot's problem: its own model and parameters, the request's start, goal and seed
+            q = dataclasses.replace(self.ps0[slot], start=start.copy(), goal=goal.copy(), seed=sd)
+            o = po.Oracle(q, threads=self.threads)
+            _assert_stats((res[2], res[3]), o.optimize(), f"request {r} on slot {slot} against its oracle,")
+            np.testing.assert_array_equal(res[4], o.best_trajectory(), err_msg=f"request {r} on slot {slot}: best trajectory")
+            its.append(int(res[2].iterations))
+            last[slot] = (q, o)
+        want_slot, want_start, _ = eng.serve_schedule(P, its)
+        assert [res[0] for res in results] == want_slot, ([res[0] for res in results], want_slot, its)
+        assert [res[1] for res in results] == want_start, ([res[1] for res in results], want_start, its)
+        assert sorted(last) == list(range(min(n, P))), sorted(last)
+        for slot, (q, o) in last.items():
+            assert self.g.engines[slot].problem.seed == q.seed
+            self.twins[slot].retarget(q.start, q.goal, q.seed)
+            self.twins[slot].optimize()
+            self.os[slot], self.ps[slot] = o, q
+        self.served = (reqs, results)
 
     def op_g_retarget(self, k, keep_seed):
         qs = [self._moved(m, k, keep_seed) for m in range(len(self.ps))]

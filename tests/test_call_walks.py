@@ -3,6 +3,8 @@ deterministic and stays inside its mode's alphabet and bookkeeping; the census t
 from hiding a gap holds over exactly the seeds tests/test_gpu_call_walks.py runs; and every
 single-engine script leaves the oracle in one state with and without its observe ops.
 tests/CALL_WALKS.md holds the numbers."""
+import hashlib
+
 import numpy as np
 import pytest
 
@@ -12,6 +14,37 @@ ALL_MODES = list(cw.MODES)
 PURITY_MODES = [m for m, s in cw.MODES.items() if s["kind"] == "single" and s.get("purity", True)]
 # ops that change no state of the model: an observe after them reads what the op before them left
 STATELESS = ("observe", "execute", "m_execute", "set_timing", "refuse", "g_run_refused")
+
+
+# sha256 over repr(make_script(mode, s)) for s in range(SEEDS[mode]), first 16 hex digits, of the 16
+# modes that existed before IDENTS was frozen, taken from the module as it stood then
+FROZEN = {
+    "reuse_fused": (12, "551ed103eb57069c"), "reuse_no_spec": (14, "f72724523517a58b"),
+    "reuse_no_pick_fuse": (12, "ca78c028a041468c"), "pregen": (13, "3d7ccbc5272ae295"), "unfused": (13, "709b0847a262bc79"),
+    "slot_loop": (28, "8e86eba3f0bbe99a"), "slot_loop_lean": (25, "96775fc24c2ccc39"), "phased": (18, "80c970bb6c9bd8a3"),
+    "terms_cum": (15, "18cae7079647691b"), "device_brick": (16, "bf08661dfbc87845"), "group_reuse": (5, "93118209f64a2177"),
+    "group_pregen": (4, "46c1002411977521"), "group_mixed": (18, "d678ad55031ad205"),
+    "group_mixed_compact": (8, "668f442d07b844f8"), "ranks_partials": (4, "f250a29a5c3c51d4"),
+    "ranks_gather": (4, "9ba975cd67205712"),
+}
+
+
+@pytest.mark.parametrize("mode", list(FROZEN))
+def test_existing_scripts_have_not_moved(mode):
+    seeds, digest = FROZEN[mode]
+    assert cw.SEEDS[mode] == seeds and cw.IDENTS[mode] == sorted(FROZEN).index(mode)
+    h = hashlib.sha256()
+    for s in range(seeds):
+        h.update(repr(cw.make_script(mode, s)).encode())
+    assert h.hexdigest()[:16] == digest
+    new = {k for m in cw.MODES if m not in FROZEN for k in cw.kinds_of(m)} - {k for m in FROZEN for k in cw.kinds_of(m)}
+    assert not (new & set(cw.kinds_of(mode))), sorted(new & set(cw.kinds_of(mode)))
+
+
+def test_new_modes_have_idents_from_16_up():
+    new = [m for m in cw.MODES if m not in FROZEN]
+    assert set(cw.IDENTS) == set(cw.MODES) and all(cw.IDENTS[m] >= 16 for m in new)
+    assert len(set(cw.IDENTS.values())) == len(cw.IDENTS)
 
 
 def scripts(mode, seeds=None):
@@ -74,7 +107,12 @@ def test_census(mode):
 
 
 def run_on_oracle(mode, script):
-    pair = cw.Pair(cw.MODES[mode]["make"](), engine=None, threads=cw.MODES[mode].get("threads", 1))
+    made = cw.MODES[mode]["make"]()
+    if cw.MODES[mode].get("request"):
+        cw.assert_attach_matters(made)
+    if cw.MODES[mode].get("scene"):      # the field the scene's static layer gives
+        made.sdf = cw.po.sdf_build_objects(made.grid, cw.scene_static_layer(made, 0))[0]
+    pair = cw.Pair(made, engine=None, threads=cw.MODES[mode].get("threads", 1))
     cw.replay(mode, script, pair)
     return pair.full_state()
 

@@ -6,7 +6,8 @@ read would have repaired stays visible to the next call.  Every comparison is bi
 ends with a full observe of everything both sides define (groups and ranks: after a synchronize).
 
 tests/CALL_WALKS.md holds the alphabet, the modes, the census and what the walks found; the scripts
-that showed a bug stand below the walks as named regression tests.
+that showed a bug stand below the walks as named regression tests, and after them the literal script
+that turns the padding-collision flag through a serve call.
 """
 import numpy as np
 import pytest
@@ -43,11 +44,26 @@ def make_pair(mode, monkeypatch, capfd):
             buf = eng.DeviceBuffer(2 * made.grid.cells)
             eng.sdf_build_objects_device(made.grid, cw.scene_objects(made, False), buf.ptr)
             made.sdf = buf.to_numpy(np.uint16, tuple(made.grid.dims))
-        e = eng.Engine(made, sdf_device_ptr=buf.ptr if buf else None)
+        if spec.get("request"):     # on the oracle alone, before any engine exists
+            cw.assert_attach_matters(made)
+        scene = stream = None
+        if spec.get("scene"):
+            # the field belongs to a scene on a stream it shares with the engine
+            stream = eng.Stream()
+            buf = eng.DeviceBuffer(2 * made.grid.cells)
+            scene = eng.Scene(made.grid, buf.ptr, stream=stream.ptr)
+            scene.set_static(cw.scene_static_layer(made, 0))
+            assert scene.info()["stray"] == 0
+            made.sdf = buf.to_numpy(np.uint16, tuple(made.grid.dims))
+        e = eng.Engine(made, sdf_device_ptr=buf.ptr if buf else None, stream=stream.ptr if stream else None)
         got = lines(capfd, "stomp: model ")[-1:]
-        pair = cw.Pair(made, e, threads=threads, field=buf)
+        pair = cw.Pair(made, e, threads=threads, field=buf, scene=scene, stream=stream,
+                       brick=spec["env"].get("STOMP_SDF_LAYOUT") == "brick")
+        if scene is not None:
+            np.testing.assert_array_equal(made.sdf, pair.scene_field(0, 0), err_msg="the static layer against the oracle's build")
     elif spec["kind"] == "group":
-        pair = cw.GroupPair(made, threads=threads, **spec.get("group", {}))
+        targets = spec["targets"]() if "targets" in spec else None
+        pair = cw.GroupPair(made, threads=threads, targets=targets, **spec.get("group", {}))
         got = lines(capfd, "stomp: group ")
     else:
         ranks = ru.make_ranks(made, 2, spec["shard"], monkeypatch)
@@ -59,10 +75,16 @@ def make_pair(mode, monkeypatch, capfd):
     return pair
 
 
-def walk(mode, script, monkeypatch, capfd, seed=None):
+def walk(mode, script, monkeypatch, capfd, seed=None, after=None):
+    """after(pair, i, op): called behind every op of the script (a literal test's own assertions)"""
     pair = make_pair(mode, monkeypatch, capfd)
     try:
-        cw.replay(mode, script, pair, seed)
+        if after is None:
+            cw.replay(mode, script, pair, seed)
+        else:
+            for i, op in enumerate(script):
+                cw.replay(mode, [op], pair, seed, start=i)
+                after(pair, i, op)
         cw.replay(mode, cw.final_ops(mode, script), pair, seed, start=len(script))
     finally:
         pair.close()
@@ -95,3 +117,33 @@ def test_extra_rollout_after_a_fused_iteration_is_priced_with_its_weight(monkeyp
     script = [("pi_get_rollouts", 1), ("pi_set_rollout_costs", 2), ("pi_improve_policy",), fused,
               ("pi_add_extra_rollout", None), ("observe", ("x_control",))]
     walk(mode, script, monkeypatch, capfd)
+
+
+# ---------------------------------------------------------------------------- the padding flag through a serve
+def test_serve_turns_the_padding_flag_both_ways(monkeypatch, capfd):
+    # A queue alternating flag_pair's A (only its padding poses collide) and B (free): the slots'
+    # padding-collision flags change at the turnovers (k_serve_flags) and the call's end brings the
+    # last ones back to the three host copies.  flag_pair asserts on the oracle that the flag alone
+    # decides A's result, so a flag that stayed behind shows: in the requests' results, in the
+    # execute(member 0) of every slot straight after the serve (the engine's own copy), and in the
+    # grouped run after them (the group's copy and the model's).
+    A, B = 1, 2
+    # A B A B, B A B A, ...: the slots of this group turn together, so the order flips every P requests
+    which = tuple(A if (r + r // 4) % 2 == 0 else B for r in range(16))
+    script = [("g_serve", 77, len(which), which)]
+    script += [("m_execute", m, 300 + m, 2, 0) for m in range(4)]
+    script += [("g_run", 7, 2)]
+
+    def after(pair, i, op):
+        if op[0] != "g_serve":
+            return
+        reqs, results = pair.served
+        by_slot = {}
+        for r, res in enumerate(results):
+            by_slot.setdefault(res[0], []).append(which[r])
+        turns = {(a, b) for seq in by_slot.values() for a, b in zip(seq, seq[1:])}
+        print("requests per slot:", by_slot)
+        assert (A, B) in turns and (B, A) in turns, by_slot
+        assert all(A in seq and B in seq for seq in by_slot.values()) and len(by_slot) == 4, by_slot
+
+    walk("group_serve_shelf", script, monkeypatch, capfd, after=after)
