@@ -301,6 +301,75 @@ int stomp_engine_retarget_request(stomp_engine* e, const stomp_request* r);
  * allocates nothing).  Host only. */
 int stomp_engine_model_info(stomp_engine* e, int64_t info[12]);
 
+/* The state query: per-sphere clearance and per-link costs of a batch of M joint states -- what a
+ * node asks before and after every plan (is this state in collision, which link, by how much).  The
+ * reference declares the capability and never built it: srv/GetStateCost.srv (link names and a robot
+ * state in, per-link costs out) and srv/GetChompCollisionCost.srv (per-link costs and in_collision).
+ * For sphere s of state m (S spheres, the engine's current collision points, in their order):
+ *   positions        the sphere centre, the planner's own forward kinematics of the state;
+ *   distances        the field distance at the centre, sqrt(d2) * resolution, metres; a centre whose
+ *                    cell is outside the valid cells [1, n - 2] reads 0, as in the planner's lookup;
+ *   potentials       the collision potential (stomp_collision_space.h:193-228) of that distance;
+ *   sphere_collides  distance <= radius (the planner's collision test).
+ * Per state, every sum sequential in ascending sphere index from 0.0:
+ *   state_cost       the sum of the potentials;
+ *   link_costs       [l]: the sum over the spheres on segment links[l] (0.0 for a segment without
+ *                    spheres; a segment may be listed more than once);
+ *   min_clearance    the least distance - radius, and min_sphere the first sphere that attains it
+ *                    (with no spheres: +infinity and -1);
+ *   in_collision     some sphere collides;
+ *   limits_violated  some joint with limits is outside [min, max].  The state is never clipped: this
+ *                    is a query, not handleJointLimits.
+ * There is no velocity factor (a robot standing still has a cost here, unlike stomp_engine_eval's
+ * waypoint costs) and no gradient: getDistanceGradient's gradient belongs to the third-party
+ * distance_field package, which the reference tree does not hold, and only the CHOMP path reads it.
+ * An output pointer that is NULL is not computed.
+ * Model and field: the model the engine holds now (after a retarget request with other collision
+ * points S is the new S, stomp_engine_model_info info[0]) and the field it reads now (after
+ * stomp_engine_refresh_field or a scene update; the bricked copy where the engine has one).
+ * The work is enqueued on the engine's stream behind everything already there, and the call waits
+ * for it.  The arrays are the caller's, in host memory.  The staging, device and pinned, is the
+ * engine's and held with a capacity: a repeated call of the same size allocates nothing.  A large M
+ * goes through in chunks of at most 48 MiB of device staging; STOMP_DEBUG_QUERY_CHUNK (read per call)
+ * sets the states per chunk instead; the results do not depend on the chunks.
+ * Nothing else of the engine changes: theta, the rollout rows, the reuse state, a pending noiseless
+ * rollout (not flushed), rows made ahead, the step API's state, the timers, the model-change counter
+ * and group membership are as before, and a group's next call is unaffected.  A sharded engine
+ * (world_size > 1) may be asked: every rank holds the whole model and field, no collective runs.
+ * STOMP_E_INVALID, before any device is touched and with no output written: NULL engine, query or
+ * states; a struct_size other than sizeof(stomp_state_query); num_states < 1; num_links < 0, or
+ * >= 1 without links; link_costs with num_links 0; a link outside the tree; a state value that is
+ * not finite; an engine inside its optimize loop (read from the loop's atomic flag, so another host
+ * thread may ask).  The NULL and struct_size refusals come before the engine is read (a machine
+ * without a GPU can make these calls).  A refusal writes nothing of the engine; stomp_last_error()
+ * has the message. */
+typedef struct stomp_state_query {
+    int32_t struct_size;            /* sizeof(stomp_state_query) */
+    int32_t num_states;             /* M >= 1 */
+    const double* states;           /* [M][J] */
+    int32_t num_links;              /* L >= 0 */
+    const int32_t* links;           /* [L] segment indices (GetStateCost.srv link_names) */
+    /* outputs; each may be NULL (not computed) */
+    double*  positions;             /* [M][S][3] */
+    double*  distances;             /* [M][S] field distance at the sphere centre, metres */
+    double*  potentials;            /* [M][S] */
+    uint8_t* sphere_collides;       /* [M][S] */
+    double*  link_costs;            /* [M][L] */
+    double*  state_cost;            /* [M] */
+    double*  min_clearance;         /* [M] */
+    int32_t* min_sphere;            /* [M] */
+    uint8_t* in_collision;          /* [M] */
+    uint8_t* limits_violated;       /* [M] */
+} stomp_state_query;
+int stomp_engine_query_states(stomp_engine* e, const stomp_state_query* q);
+/* The last query call, for tests and tables: info[0] its chunks, [1] its kernel launches (the query
+ * and the transposes of its per-sphere outputs), [2] device or pinned allocations made inside query
+ * calls so far, [3] its states per chunk.  Host only. */
+int stomp_engine_query_info(stomp_engine* e, int64_t info[4]);
+/* Device time of the last query call's launches, milliseconds (events around each chunk's launches,
+ * summed; the copies are outside).  Host only. */
+int stomp_engine_query_time(stomp_engine* e, double* kernel_ms);
+
 int stomp_engine_get_theta(stomp_engine* e, double* theta);
 int stomp_engine_set_theta(stomp_engine* e, const double* theta);
 

@@ -393,6 +393,15 @@ struct STOMPStatistics {   // msg/STOMPStatistics.msg without the ROS header
     std::vector<double> torques;   // per free waypoint, sum |tau| of the best trajectory (empty without inertias)
 };
 
+// GetStateCost.srv's response for one state (StompOptimizer::getStateCosts)
+struct StateCost {
+    bool valid = false;
+    std::vector<double> costs;
+    bool in_collision = false;
+    double min_clearance = 0.0;
+    int min_sphere = -1;
+};
+
 class StompOptimizer : public Task {
 public:
     // stomp_optimizer.cpp:50-70 (the ROS publishers are not taken, see the file header)
@@ -487,6 +496,18 @@ public:
                            const std::vector<std::vector<double>>& goals, const std::vector<uint64_t>& seeds,
                            std::vector<ServeResult>& results);
     const STOMPStatistics& getStatistics() const { return stats_; }
+
+    // The reference's GetStateCost.srv (declared there, never implemented): the per-link collision
+    // costs of robot states against the optimizer's current collision points and field
+    // (stomp_engine_query_states).  states[m]: num_joints values; link_segments: the segments whose
+    // costs are wanted (the service's link_names, resolved by the caller), may be empty.  out[m]:
+    // costs[l] the summed potentials of the collision points on link_segments[l]; valid: every
+    // limited joint inside its limits (the state is not clipped); in_collision; min_clearance and
+    // min_sphere: the least distance - radius over the collision points and the first point that
+    // attains it.  No gradient (the third-party distance_field's, not in the reference tree).  The
+    // optimizer is otherwise untouched.  false with lastError() when refused; out is unchanged then.
+    bool getStateCosts(const std::vector<std::vector<double>>& states, const std::vector<int>& link_segments,
+                       std::vector<StateCost>& out);
 
     // Task (stomp_optimizer.cpp:1063-1165, 1167-1182)
     bool initialize(int num_time_steps) override;

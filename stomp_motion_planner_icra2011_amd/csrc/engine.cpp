@@ -41,6 +41,10 @@ void release(stomp_engine* e)
     if (e->h_stall) hipHostFree(e->h_stall);
     if (e->h_rq) hipHostFree(e->h_rq);
     if (e->d_rq) hipFree(e->d_rq);
+    if (e->h_qs) hipHostFree(e->h_qs);
+    if (e->d_qs) hipFree(e->d_qs);
+    for (hipEvent_t ev : e->q_ev)
+        if (ev) hipEventDestroy(ev);
     for (auto& r : e->coll_ring)
         if (r.ev) hipEventDestroy(r.ev);
     comm_destroy(e);

@@ -12,6 +12,8 @@
 //                        the next request; stomp_serve_schedule, its decisions as a host-only function
 //   engine_retarget.cpp  the one retarget path (validate, plan, stage, launch, commit) behind
 //                        stomp_engine_retarget, stomp_engine_retarget_request and the two group calls
+//   engine_query.cpp     stomp_engine_query_states: a batch of joint states against the engine's
+//                        current model and field (k_query.hip), chunked through one staging block
 //   sdf_build.cpp        the distance-field builders (does not include this header)
 //   scene.cpp            stomp_scene: the field kept in a static and a dynamic layer (uses fail and
 //                        DeviceGuard only)
@@ -158,6 +160,14 @@ struct stomp_engine {
     // model changes so far (a group compares it with the epoch it last saw), and the device or
     // pinned allocations made inside retarget calls of either kind (the staging's included)
     long long model_epoch = 0, rq_allocs = 0;
+    // the state query (engine_query.cpp): one chunk's staging, pinned and on the device, held with a
+    // capacity; the events around a chunk's launches; the last call's chunks, launches, states per
+    // chunk and device time (ms), and the allocations made inside query calls so far
+    unsigned char *h_qs = nullptr, *d_qs = nullptr;
+    size_t qs_cap = 0;
+    hipEvent_t q_ev[2] = {nullptr, nullptr};
+    long long q_chunks = 0, q_launches = 0, q_allocs = 0, q_chunk_states = 0;
+    double q_kernel_ms = 0.0;
     std::vector<void*> allocs;
     double *d_theta = nullptr, *d_LT = nullptr, *d_MT = nullptr, *d_QT = nullptr;
     double *d_params = nullptr, *d_noise = nullptr, *d_control = nullptr, *d_prob = nullptr, *d_state = nullptr;

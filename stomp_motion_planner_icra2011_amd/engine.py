@@ -58,6 +58,16 @@ class stomp_request(C.Structure):
                 ("orientation_constraints", C.POINTER(stomp_orientation_constraint))]
 
 
+class stomp_state_query(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("num_states", C.c_int32), ("states", C.POINTER(C.c_double)),
+                ("num_links", C.c_int32), ("links", C.POINTER(C.c_int32)),
+                ("positions", C.POINTER(C.c_double)), ("distances", C.POINTER(C.c_double)),
+                ("potentials", C.POINTER(C.c_double)), ("sphere_collides", C.POINTER(C.c_uint8)),
+                ("link_costs", C.POINTER(C.c_double)), ("state_cost", C.POINTER(C.c_double)),
+                ("min_clearance", C.POINTER(C.c_double)), ("min_sphere", C.POINTER(C.c_int32)),
+                ("in_collision", C.POINTER(C.c_uint8)), ("limits_violated", C.POINTER(C.c_uint8))]
+
+
 class stomp_attached_body(C.Structure):
     _fields_ = [("segment", C.c_int32), ("shape", stomp_shape)]
 
@@ -124,7 +134,8 @@ EXPORTED = ["stomp_engine_create", "stomp_engine_destroy", "stomp_engine_last_er
             "stomp_group_retarget", "stomp_scene_create", "stomp_scene_set_static", "stomp_scene_set_dynamic",
             "stomp_scene_window", "stomp_scene_info", "stomp_scene_destroy", "stomp_engine_retarget_request",
             "stomp_engine_model_info", "stomp_group_retarget_requests", "stomp_attached_collision_points",
-            "stomp_group_serve", "stomp_group_serve_info", "stomp_serve_schedule"]
+            "stomp_group_serve", "stomp_group_serve_info", "stomp_serve_schedule", "stomp_engine_query_states",
+            "stomp_engine_query_info", "stomp_engine_query_time"]
 
 _lib = None
 
@@ -226,6 +237,10 @@ def load_library(path: Optional[str] = None):
                                         C.POINTER(stomp_serve_result), dp, dp, C.c_int32]
         l.stomp_group_serve_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         l.stomp_serve_schedule.argtypes = [C.c_int32, C.c_int32, ip, ip, ip, ip]
+    if hasattr(l, "stomp_engine_query_states"):   # (a variant library named by STOMP_ENGINE_LIB may predate them)
+        l.stomp_engine_query_states.argtypes = [P, C.POINTER(stomp_state_query)]
+        l.stomp_engine_query_info.argtypes = [P, C.POINTER(C.c_int64)]
+        l.stomp_engine_query_time.argtypes = [P, dp]
     l.stomp_group_last_error.restype = C.c_char_p
     l.stomp_group_last_error.argtypes = [C.c_void_p]
     l.stomp_group_destroy.argtypes = [C.c_void_p]
@@ -407,6 +422,12 @@ def attached_collision_points(spheres, bodies, clearance: float):
     _check(l.stomp_attached_collision_points(base, len(spheres), att, len(bodies), float(clearance), out, cap,
                                              C.byref(n)))
     return [Sphere(out[i].segment, out[i].radius, out[i].clearance, tuple(out[i].pos)) for i in range(n.value)]
+
+
+class StateQueryResult:
+    """Engine.query_states' arrays, one attribute per output of stomp_state_query (None: not asked for)."""
+    positions = distances = potentials = sphere_collides = link_costs = state_cost = None
+    min_clearance = min_sphere = in_collision = limits_violated = None
 
 
 class Engine:
@@ -600,6 +621,77 @@ class Engine:
         v = (C.c_int64 * 12)()
         _check(load_library().stomp_engine_model_info(self.h, v), self.h)
         return dict(zip(self.MODEL_INFO, [int(x) for x in v]))
+
+    # stomp_state_query's outputs: name -> (dtype, shape of one state; S spheres, L links)
+    QUERY_OUTPUTS = dict(positions=(np.float64, "S3"), distances=(np.float64, "S"), potentials=(np.float64, "S"),
+                         sphere_collides=(np.uint8, "S"), link_costs=(np.float64, "L"), state_cost=(np.float64, ""),
+                         min_clearance=(np.float64, ""), min_sphere=(np.int32, ""), in_collision=(np.uint8, ""),
+                         limits_violated=(np.uint8, ""))
+    QUERY_DEFAULT = tuple(k for k in QUERY_OUTPUTS if k != "positions")
+    QUERY_INFO = ("chunks", "launches", "allocations", "chunk_states")
+
+    def query_states(self, states, links=None, want=QUERY_DEFAULT, fill=None):
+        """stomp_engine_query_states: the M joint states (M x J, or one state of J values) against the
+        engine's current model and field.  links: segment indices or link names (resolved through
+        problem.robot.segments) whose costs are wanted; want: the names of stomp_state_query's
+        outputs to compute (default: all but positions; link_costs only with links).  Returns a
+        StateQueryResult whose attributes are numpy arrays (None where not asked for); the flags are
+        bool arrays.  fill: a value every output array holds before the call (tests of refusals:
+        the arrays of a refused call are attached to the exception as .outputs)."""
+        q = np.ascontiguousarray(states, np.float64)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        if q.ndim != 2 or q.shape[1] != self.J:
+            raise ValueError(f"states must be M x {self.J}")
+        M = q.shape[0]
+        names = [s.name for s in self.problem.robot.segments]
+        idx = [names.index(v) if isinstance(v, str) else int(v) for v in (links if links is not None else [])]
+        L = len(idx)
+        lk = np.ascontiguousarray(idx, np.int32)
+        unknown = [k for k in want if k not in self.QUERY_OUTPUTS]
+        if unknown:
+            raise KeyError(f"no such query outputs: {unknown}")
+        S = self.S
+        dims = {"S3": (S, 3), "S": (S,), "L": (L,), "": ()}
+        out = {}
+        for k in want:
+            if k == "link_costs" and links is None:
+                continue
+            dt, shp = self.QUERY_OUTPUTS[k]
+            out[k] = np.zeros((M,) + dims[shp], dt) if fill is None else np.full((M,) + dims[shp], fill, dt)
+        sq = stomp_state_query()
+        sq.struct_size = C.sizeof(stomp_state_query)
+        sq.num_states = M
+        sq.states = _dp(q)
+        sq.num_links = L
+        sq.links = lk.ctypes.data_as(C.POINTER(C.c_int32)) if L else None
+        ctype = {np.float64: C.c_double, np.uint8: C.c_uint8, np.int32: C.c_int32}
+        for k, a in out.items():
+            setattr(sq, k, a.ctypes.data_as(C.POINTER(ctype[self.QUERY_OUTPUTS[k][0]])))
+        # (a refusal writes nothing of the engine, not even its message: the thread's last error has it)
+        rc = load_library().stomp_engine_query_states(self.h, C.byref(sq))
+        if rc != 0:
+            try:
+                _check(rc)
+            except RuntimeError as err:
+                err.outputs = out
+                raise
+        res = StateQueryResult()
+        for k in self.QUERY_OUTPUTS:
+            a = out.get(k)
+            if a is not None and k in ("sphere_collides", "in_collision", "limits_violated"):
+                a = a.astype(bool)
+            setattr(res, k, a)
+        return res
+
+    def query_info(self) -> dict:
+        """stomp_engine_query_info: the last query call's chunks, launches and states per chunk, and
+        the allocations made inside query calls so far; kernel_ms: its launches' device time."""
+        v = (C.c_int64 * 4)()
+        _check(load_library().stomp_engine_query_info(self.h, v), self.h)
+        ms = C.c_double()
+        _check(load_library().stomp_engine_query_time(self.h, C.byref(ms)), self.h)
+        return dict(zip(self.QUERY_INFO, [int(x) for x in v]), kernel_ms=ms.value)
 
     def execute(self, params, iteration_member: int = 1):
         prm = np.ascontiguousarray(params, np.float64)

@@ -446,6 +446,57 @@ bool StompOptimizer::retarget(const std::vector<double>& start, const std::vecto
     return true;
 }
 
+// GetStateCost.srv over stomp_engine_query_states: one call for all states
+bool StompOptimizer::getStateCosts(const std::vector<std::vector<double>>& states, const std::vector<int>& link_segments,
+                                   std::vector<StateCost>& out)
+{
+    if (!engine_) return false;
+    const size_t M = states.size(), L = link_segments.size();
+    if (M == 0) {
+        error_ = "getStateCosts: no states";
+        return false;
+    }
+    std::vector<double> q;
+    for (const auto& s : states) {
+        if ((int)s.size() != J_) {
+            error_ = "getStateCosts: a state must hold num_joints values";
+            return false;
+        }
+        q.insert(q.end(), s.begin(), s.end());
+    }
+    const std::vector<int32_t> links(link_segments.begin(), link_segments.end());
+    std::vector<double> costs(M * L), clearance(M);
+    std::vector<int32_t> min_sphere(M);
+    std::vector<uint8_t> collision(M), limits(M);
+    stomp_state_query sq{};
+    sq.struct_size = (int32_t)sizeof sq;
+    sq.num_states = (int32_t)M;
+    sq.states = q.data();
+    sq.num_links = (int32_t)L;
+    sq.links = L ? links.data() : nullptr;
+    sq.link_costs = L ? costs.data() : nullptr;
+    sq.min_clearance = clearance.data();
+    sq.min_sphere = min_sphere.data();
+    sq.in_collision = collision.data();
+    sq.limits_violated = limits.data();
+    const int rc = stomp_engine_query_states(engine_, &sq);
+    if (rc != 0) {
+        // (a refusal writes nothing of the engine, not even its message: the thread's last error has it)
+        error_ = engine_error(rc == STOMP_E_INVALID ? nullptr : engine_, rc);
+        return false;
+    }
+    out.assign(M, StateCost());
+    for (size_t m = 0; m < M; ++m) {
+        StateCost& c = out[m];
+        c.valid = limits[m] == 0;
+        c.costs.assign(costs.begin() + m * L, costs.begin() + (m + 1) * L);
+        c.in_collision = collision[m] != 0;
+        c.min_clearance = clearance[m];
+        c.min_sphere = min_sphere[m];
+    }
+    return true;
+}
+
 bool StompOptimizer::retargetBatch(const std::vector<StompOptimizer*>& optimizers,
                                    const std::vector<std::vector<double>>& starts,
                                    const std::vector<std::vector<double>>& goals, const std::vector<uint64_t>& seeds,
