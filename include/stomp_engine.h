@@ -758,6 +758,90 @@ int stomp_serve_schedule(int32_t num_slots, int32_t num_requests, const int32_t*
 const char* stomp_group_last_error(const stomp_group* g);
 void stomp_group_destroy(stomp_group* g);
 
+/* CHOMP mode: the reference's covariant gradient descent (use_chomp; StompOptimizer::
+ * doChompOptimization, stomp_optimizer.cpp:208-247, in the loop of optimize(), :249-382) on the
+ * model, field and cost of a live engine.  A stomp_chomp borrows the engine (which must outlive it)
+ * and holds B independent descents between the engine's start and goal, from B initial trajectories
+ * (multi-start); every kernel works on (descent, waypoint) or (descent, joint), so the batch is what
+ * fills the device.
+ * One step is, per descent: the smoothness increments -(quad_cost_full_i (2 x_i)) over the free
+ * block (:403-411), the collision increments (:413-470: per free waypoint the spheres in ascending
+ * order, a sphere with potential <= 1e-10 skipped, the fold ended after the first colliding sphere,
+ * whose own term is included; J^T g, or J^T (J J^T + ridge I)^-1 g with use_pseudo_inverse, the 3 x 3
+ * inverse by cofactors over the determinant), learning_rate Qinv_i (smoothness_cost_weight s_i +
+ * obstacle_cost_weight c_i) (:472-486), the per-joint scale min(1, limit / |max|, limit / |min|) of
+ * addIncrementsToTrajectory (:488-506), handleJointLimits, the forward kinematics and the cost
+ * (:233-246: per waypoint a prefix sum of prefix sums of potential * vel_mag over the spheres, times
+ * obstacle_cost_weight).  A zero vel_mag divides as IEEE 754 says, as in the reference; nothing guards it.
+ * The field gradient is the third-party distance_field package's getDistanceGradient, which the
+ * reference tree does not hold; this definition follows that package as its maintainers know it and
+ * is stated from knowledge, not from a file: at the nearest cell g, component a is
+ * (dist(g + e_a) - dist(g - e_a)) * (1 / (2 resolution)) with dist = sqrt(double(d2)) * resolution; a
+ * centre whose cell is outside [1, n - 2] on any axis reads distance 0 and gradient 0 (the window of
+ * the distance lookup, so the neighbours at 0 and n - 1 are always readable).  field_bias is added to
+ * it before the potential's gradient is formed (stomp_collision_space.h:202-204).
+ * Joint origins and axes are world-frame quantities of the same FK: the frame's translation of the
+ * segment the joint drives, and that frame's rotation times the stored axis; a joint that drives no
+ * segment reads zeros and has a zero Jacobian column, as has every joint off the path from the root
+ * to the sphere's segment (fixed segments and branches included).
+ * Taken from the engine: obstacle_cost_weight, max_iterations, max_iterations_after_collision_free,
+ * the discretization, the joints' limits, start, goal, the model and the field (the bricked copy where
+ * the engine has one), all as the engine holds them at the last stomp_chomp_reset.
+ * reset: the descents' trajectories (NULL: every descent starts at the engine's policy parameters as
+ *   they are on its stream, copyPolicyToGroupTrajectory of :268 -- theta_0 on an engine that has not
+ *   iterated since its creation or last retarget), then optimize()'s pass before its loop (:267-271, iteration_ = 0): joint
+ *   limits and FK.  The buffers are held with a capacity: a reset of a B not above an earlier one
+ *   allocates nothing.
+ * step: `count` iterations enqueued on the engine's stream behind what is there, no host wait; the
+ *   first step after a reset runs with iteration_ = 0 (the padding's collisions count), the others with
+ *   their own index.  optimize: the loop of :284-359 with its bookkeeping on the device, from a fresh
+ *   reset; each descent stops on its own (its rows stay as they were when it stopped, later steps leave
+ *   it out); the host reads the stop flags once per chunk of STOMP_GROUP_OPTIMIZE_CHUNK iterations, one
+ *   chunk behind, and returns when all descents have stopped.  stats[b].success_duration and
+ *   collision_success_duration are 0 (no clock is read).
+ * get: one of "trajectory", "smoothness_increments", "collision_increments", "final_increments"
+ *   ([B][J][N]), "scales" ([B][J]), "sphere_positions" ([B][N + 12][S][3], padding waypoints included),
+ *   "distances", "potentials", "vel_mags" ([B][N][S]), "field_gradients" (without the bias),
+ *   "potential_gradients", "velocities", "accelerations" ([B][N][S][3]), "joint_origins", "joint_axes"
+ *   ([B][N][J][3]), "costs" ([B][N]), "cost", "collision_free" ([B]); waits for the stream.
+ * info: [0] B, [1] iterations stepped since the reset, [2] kernel launches of the last reset / step /
+ *   optimize call, [3] device and pinned allocations so far, [4..7] LDS bytes per workgroup of the FK,
+ *   gradient (increments and velocities), update and bookkeeping kernels.
+ * The CHOMP object changes nothing of the engine: theta, the rollout rows, the reuse state, a pending
+ * noiseless rollout, the step API's state, the timers and group membership are untouched.
+ * After stomp_engine_retarget (either kind, through a group too) or stomp_engine_refresh_field the next
+ * step / optimize / get returns STOMP_E_INVALID naming the reason, until reset is called again (a field
+ * read in place that a scene update rewrites without a refresh call cannot be noticed).
+ * STOMP_E_INVALID, before any device is touched: NULL arguments; a struct_size other than
+ * sizeof(stomp_chomp_params); num_trajectories < 1; a parameter or trajectory value that is not
+ * finite; an update limit that is not positive; costs_stride below max_iterations (with costs); an
+ * engine inside its optimize loop; optimize without a fresh reset.  STOMP_E_UNSUPPORTED: a sharded
+ * engine (world_size > 1), use_hamiltonian_monte_carlo (the reference's HMC updates, :219-226, are not
+ * built), N > 256, a kernel over its LDS limit.  The NULL and struct_size refusals come before the
+ * engine is read (a machine without a GPU can make these calls). */
+typedef struct stomp_chomp_params {
+    int32_t struct_size;                  /* sizeof(stomp_chomp_params) */
+    double learning_rate;                 /* 0.01 (stomp_parameters.cpp:60) */
+    double smoothness_cost_weight;        /* 0.1  (:56) */
+    int32_t use_pseudo_inverse;           /* 0    (:71) */
+    double pseudo_inverse_ridge_factor;   /* 1e-4 (:72) */
+    double field_bias[3];                 /* 0 */
+    const double* joint_update_limits;    /* J; stomp_joints_[i].joint_update_limit_, 0.05 (stomp_robot_model.cpp:78) */
+    int32_t use_hamiltonian_monte_carlo;  /* must be 0 */
+} stomp_chomp_params;
+typedef struct stomp_chomp stomp_chomp;
+int stomp_chomp_create(stomp_engine* e, const stomp_chomp_params* p, stomp_chomp** out);
+int stomp_chomp_reset(stomp_chomp* c, int32_t num_trajectories /* B >= 1 */,
+                      const double* trajectories /* [B][J][N] or NULL: theta_0 */);
+int stomp_chomp_step(stomp_chomp* c, int32_t count);      /* enqueue, no host sync */
+int stomp_chomp_synchronize(stomp_chomp* c);
+int stomp_chomp_optimize(stomp_chomp* c, stomp_stats* stats /* [B] */, double* costs /* [B][stride] or NULL */,
+                         int32_t costs_stride, double* best_trajectories /* [B][J][N] or NULL */);
+int stomp_chomp_get(stomp_chomp* c, const char* which, double* out);
+int stomp_chomp_info(stomp_chomp* c, int64_t info[8]);
+const char* stomp_chomp_last_error(const stomp_chomp* c);
+void stomp_chomp_destroy(stomp_chomp* c);
+
 /* Device buffers for callers without a HIP runtime of their own (bench, tests). */
 int stomp_device_alloc(int32_t device, uint64_t bytes, void** out);
 int stomp_device_free(void* p);

@@ -129,6 +129,16 @@ struct StompParameters {
     std::vector<double> noise_stddev;   // per joint (policy_improvement_loop.cpp:99-100)
     std::vector<double> noise_decay;    // per joint
     uint64_t seed = 0x53544F4D50000000ull;
+    // CHOMP mode (stomp_parameters.cpp:56-75): with use_chomp StompOptimizer::optimize() runs the
+    // covariant gradient descent of doChompOptimization in place of the policy-improvement
+    // iterations (stomp_optimizer.cpp:289-299).  The descent reads smoothness_cost_weight above, as
+    // the reference reads one parameter for both optimizers (its own default is 0.1,
+    // stomp_parameters.cpp:56; this struct's 1e-6 is params.yaml's value for STOMP).
+    bool use_chomp = false;
+    double learning_rate = 0.01;
+    bool use_pseudo_inverse = false;
+    double pseudo_inverse_ridge_factor = 1e-4;
+    bool use_hamiltonian_monte_carlo = false;   // not built: optimize() fails with STOMP_E_UNSUPPORTED's message
 };
 
 // StompRobotModel::StompPlanningGroup as the engine needs it: the kinematic tree in DFS
@@ -137,6 +147,11 @@ struct StompRobotModel {
     std::vector<stomp_segment> segments;
     std::vector<stomp_joint> joints;          // planning-group joints, J
     std::vector<stomp_sphere> collision_points;
+    // StompJoint::joint_update_limit_ per planning-group joint (CHOMP mode's per-iteration bound on a
+    // joint's increments); empty: 0.05 for every joint, the reference's default
+    // (stomp_robot_model.cpp:78, the "joint_update_limit" parameter).  Kept beside `joints` because
+    // stomp_joint is a struct of the C ABI, which does not grow.
+    std::vector<double> joint_update_limits;
     // inverse dynamics of the torque term (stomp_robot_model.cpp:185-189): segment inertias
     // and the chain torque_root (exclusive) -> torque_tip (inclusive); needed only when
     // torque_cost_weight > 1e-9
@@ -557,6 +572,7 @@ private:
     friend class CovariantTrajectoryPolicy;
     bool check(int rc);
     bool finishOptimize(const stomp_stats& st);
+    bool optimizeChomp();
     void followRetarget(const std::vector<double>& start, const std::vector<double>& goal, uint64_t seed);
     void followModel(const std::vector<stomp_sphere>* collision_points, const Constraints* constraints);
     stomp_request request(const std::vector<double>& start, const std::vector<double>& goal, uint64_t seed,
@@ -579,6 +595,7 @@ private:
     std::vector<stomp_sphere> spheres_;
     std::vector<stomp_inertia> inertias_;
     std::vector<double> noise_stddev_, noise_decay_, start_, goal_;
+    std::vector<double> update_limits_;   // StompRobotModel::joint_update_limits at construction
     stomp_engine* engine_ = nullptr;
     std::shared_ptr<Policy> policy_;
     int J_ = 0, N_ = 0;

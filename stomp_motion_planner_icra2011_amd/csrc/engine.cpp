@@ -400,6 +400,7 @@ int stomp_engine_refresh_field(stomp_engine* e)
     if (!e) return fail(nullptr, STOMP_E_INVALID, "null engine");
     if (!e->d_sdf_caller)
         return fail(e, STOMP_E_UNSUPPORTED, "the distance field was uploaded from the host at creation (data_on_device = 0)");
+    ++e->target_epoch;
     if (!e->model.brick) return 0;   // read in place
     DeviceGuard dg(e->device);
     launch_sdf_bricks(e->d_sdf_caller, e->d_sdf, e->grid_n[0], e->grid_n[1], e->grid_n[2], e->stream);

@@ -160,6 +160,9 @@ struct stomp_engine {
     // model changes so far (a group compares it with the epoch it last saw), and the device or
     // pinned allocations made inside retarget calls of either kind (the staging's included)
     long long model_epoch = 0, rq_allocs = 0;
+    // retargets of either kind and stomp_engine_refresh_field calls so far: with model_epoch, what a
+    // CHOMP object (engine_chomp.cpp) compares with the values of its last reset
+    long long target_epoch = 0;
     // the state query (engine_query.cpp): one chunk's staging, pinned and on the device, held with a
     // capacity; the events around a chunk's launches; the last call's chunks, launches, states per
     // chunk and device time (ms), and the allocations made inside query calls so far

@@ -24,6 +24,7 @@ void retarget_host_state(stomp_engine* e, const double* start, const double* goa
     if (seed) e->seed = *seed;
     e->model.pad_collision = flag;
     e->pad_collision = flag;
+    ++e->target_epoch;
     // made with the old theta, start, goal and seed: the noiseless rollout not evaluated yet,
     // the rows made ahead, the reuse ranking's inputs (which row set is written next is the
     // engine's own and stays), the step API's state (stomp_pi_reset's, and its weight)

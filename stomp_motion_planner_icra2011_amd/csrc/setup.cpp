@@ -129,6 +129,7 @@ std::string compute_setup(const SetupInput& in, SetupOutput& out)
 
     // StompCost: Q = sum_i (w_i * disc^(i+1)) D_i^T D_i + ridge I with raw stencils
     out.Qinv.assign((size_t)J * N * N, 0.0);
+    out.Qband.assign((size_t)J * Nall * 13, 0.0);
     double max_scale = 0.0;
     std::vector<double> Qfull, Qfree((size_t)N * N), Qi;
     for (int jt = 0; jt < J; ++jt) {
@@ -150,9 +151,15 @@ std::string compute_setup(const SetupInput& in, SetupOutput& out)
             if (Qi[k] > mx) mx = Qi[k];
         if (max_scale < mx) max_scale = mx;
         std::memcpy(out.Qinv.data() + (size_t)jt * N * N, Qi.data(), sizeof(double) * N * N);
+        for (int r = 0; r < Nall; ++r)
+            for (int c = 0; c < 13; ++c) {
+                const int col = r - 6 + c;
+                out.Qband[((size_t)jt * Nall + r) * 13 + c] = col >= 0 && col < Nall ? Qfull[(size_t)r * Nall + col] : 0.0;
+            }
     }
     double inv_scale = 1.0 / max_scale;
     for (double& v : out.Qinv) v *= inv_scale;
+    for (double& v : out.Qband) v *= max_scale;
 
     out.theta.assign((size_t)J * N, 0.0);
     std::vector<double> lin(N);

@@ -39,6 +39,10 @@ struct SetupOutput {
     std::vector<double> Rall;                         // Nall x Nall
     std::vector<double> Rinv, L, M;                   // N x N (row-major)
     std::vector<double> Qinv;                         // J x N x N (scaled)
+    // StompCost::quad_cost_full_ after scale() (stomp_cost.cpp:52-63, 99-104), per joint, as its
+    // band: entry (r, r - 6 + c) at [j][r][c], c < 13, zero outside the matrix (the 7-tap rules
+    // squared reach 6 columns).  Read by the CHOMP path's smoothness increments only.
+    std::vector<double> Qband;                        // J x Nall x 13 (scaled)
     std::vector<double> theta;                        // J x N
 };
 

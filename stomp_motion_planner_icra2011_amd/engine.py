@@ -105,6 +105,13 @@ class stomp_serve_result(C.Structure):
     _fields_ = [("slot", C.c_int32), ("start_step", C.c_int32), ("stats", stomp_stats)]
 
 
+class stomp_chomp_params(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("learning_rate", C.c_double), ("smoothness_cost_weight", C.c_double),
+                ("use_pseudo_inverse", C.c_int32), ("pseudo_inverse_ridge_factor", C.c_double),
+                ("field_bias", C.c_double * 3), ("joint_update_limits", C.POINTER(C.c_double)),
+                ("use_hamiltonian_monte_carlo", C.c_int32)]
+
+
 # stomp_group_create_flags' accept mask
 STOMP_GROUP_ACCEPT_STATE_TERMS = 1
 STOMP_GROUP_ACCEPT_CUMULATIVE = 2
@@ -135,7 +142,9 @@ EXPORTED = ["stomp_engine_create", "stomp_engine_destroy", "stomp_engine_last_er
             "stomp_scene_window", "stomp_scene_info", "stomp_scene_destroy", "stomp_engine_retarget_request",
             "stomp_engine_model_info", "stomp_group_retarget_requests", "stomp_attached_collision_points",
             "stomp_group_serve", "stomp_group_serve_info", "stomp_serve_schedule", "stomp_engine_query_states",
-            "stomp_engine_query_info", "stomp_engine_query_time"]
+            "stomp_engine_query_info", "stomp_engine_query_time", "stomp_chomp_create", "stomp_chomp_reset",
+            "stomp_chomp_step", "stomp_chomp_synchronize", "stomp_chomp_optimize", "stomp_chomp_get",
+            "stomp_chomp_info", "stomp_chomp_last_error", "stomp_chomp_destroy"]
 
 _lib = None
 
@@ -241,6 +250,18 @@ def load_library(path: Optional[str] = None):
         l.stomp_engine_query_states.argtypes = [P, C.POINTER(stomp_state_query)]
         l.stomp_engine_query_info.argtypes = [P, C.POINTER(C.c_int64)]
         l.stomp_engine_query_time.argtypes = [P, dp]
+    if hasattr(l, "stomp_chomp_create"):   # (a variant library named by STOMP_ENGINE_LIB may predate them)
+        l.stomp_chomp_create.argtypes = [P, C.POINTER(stomp_chomp_params), C.POINTER(C.c_void_p)]
+        l.stomp_chomp_reset.argtypes = [P, C.c_int32, dp]
+        l.stomp_chomp_step.argtypes = [P, C.c_int32]
+        l.stomp_chomp_synchronize.argtypes = [P]
+        l.stomp_chomp_optimize.argtypes = [P, C.POINTER(stomp_stats), dp, C.c_int32, dp]
+        l.stomp_chomp_get.argtypes = [P, C.c_char_p, dp]
+        l.stomp_chomp_info.argtypes = [P, C.POINTER(C.c_int64)]
+        l.stomp_chomp_last_error.restype = C.c_char_p
+        l.stomp_chomp_last_error.argtypes = [P]
+        l.stomp_chomp_destroy.argtypes = [P]
+        l.stomp_chomp_destroy.restype = None
     l.stomp_group_last_error.restype = C.c_char_p
     l.stomp_group_last_error.argtypes = [C.c_void_p]
     l.stomp_group_destroy.argtypes = [C.c_void_p]
@@ -791,6 +812,97 @@ class Engine:
         t, n = C.c_double(), C.c_int32()
         _check(load_library().stomp_engine_get_timing(self.h, name.encode(), C.byref(t), C.byref(n)), self.h)
         return t.value, n.value
+
+
+class Chomp:
+    """CHOMP mode on a live engine (stomp_chomp_*): B independent covariant gradient descents between
+    the engine's start and goal, on its model, field and cost.  The engine must outlive the object;
+    nothing of the engine changes.  The defaults are the reference's (stomp_parameters.cpp:56-72,
+    stomp_robot_model.cpp:78)."""
+
+    # per-descent shapes of get()'s arrays from (J, N, S)
+    SHAPES = dict(trajectory="JN", smoothness_increments="JN", collision_increments="JN", final_increments="JN",
+                  scales="J", sphere_positions="AS3", distances="NS", field_gradients="NS3", potentials="NS",
+                  potential_gradients="NS3", velocities="NS3", accelerations="NS3", vel_mags="NS",
+                  joint_origins="NJ3", joint_axes="NJ3", costs="N", cost="", collision_free="")
+    INFO = ("B", "iterations", "launches", "allocations", "lds_fk", "lds_gradient", "lds_update", "lds_bookkeeping")
+
+    def __init__(self, engine, learning_rate: float = 0.01, smoothness_cost_weight: float = 0.1,
+                 use_pseudo_inverse: bool = False, pseudo_inverse_ridge_factor: float = 1e-4,
+                 field_bias=(0.0, 0.0, 0.0), joint_update_limits=None, use_hamiltonian_monte_carlo: bool = False):
+        self.engine = engine
+        self.J, self.N = engine.J, engine.N
+        self.B = 0
+        lim = np.full(self.J, 0.05) if joint_update_limits is None else np.ascontiguousarray(joint_update_limits,
+                                                                                              np.float64)
+        if lim.shape != (self.J,):
+            raise ValueError(f"joint_update_limits has shape {lim.shape} for {self.J} joints")
+        prm = stomp_chomp_params(C.sizeof(stomp_chomp_params), learning_rate, smoothness_cost_weight,
+                                 int(use_pseudo_inverse), pseudo_inverse_ridge_factor,
+                                 (C.c_double * 3)(*[float(v) for v in field_bias]), _dp(lim),
+                                 int(use_hamiltonian_monte_carlo))
+        h = C.c_void_p()
+        _check(load_library().stomp_chomp_create(engine.h, C.byref(prm), C.byref(h)))
+        self.h = h
+
+    def _check(self, rc):
+        if rc != 0:
+            raise RuntimeError(f"stomp engine error {rc}: {load_library().stomp_chomp_last_error(self.h).decode()}")
+
+    def reset(self, trajectories=None, num_trajectories: int = 1):
+        """trajectories: [B][J][N] (or [J][N]: one descent); None: num_trajectories descents from the
+        engine's policy parameters"""
+        if trajectories is None:
+            B, ptr = int(num_trajectories), None
+        else:
+            t = np.ascontiguousarray(trajectories, np.float64).reshape(-1, self.J, self.N)
+            B, ptr = len(t), _dp(t)
+        self._check(load_library().stomp_chomp_reset(self.h, B, ptr))
+        self.B = B
+
+    def step(self, count: int = 1):
+        self._check(load_library().stomp_chomp_step(self.h, count))
+
+    def synchronize(self):
+        self._check(load_library().stomp_chomp_synchronize(self.h))
+
+    def optimize(self):
+        """per descent (stomp_stats, costs[:iterations], best trajectory)"""
+        B = max(self.B, 1)
+        stride = max(self.engine.problem.params.max_iterations, 1)
+        st = (stomp_stats * B)()
+        costs = np.zeros((B, stride))
+        best = np.zeros((B, self.J, self.N))
+        self._check(load_library().stomp_chomp_optimize(self.h, st, _dp(costs), stride, _dp(best)))
+        return [(st[b], costs[b, :st[b].iterations].copy(), best[b].copy()) for b in range(self.B)]
+
+    def get(self, name: str) -> np.ndarray:
+        if name not in self.SHAPES:
+            raise KeyError(name)
+        info = self.info()
+        dims = dict(J=self.J, N=self.N, A=self.N + 12, S=info["S"])
+        shape = (self.B,) + tuple(3 if ch == "3" else dims[ch] for ch in self.SHAPES[name])
+        out = np.zeros(shape)
+        self._check(load_library().stomp_chomp_get(self.h, name.encode(), _dp(out)))
+        return out
+
+    def info(self) -> dict:
+        v = (C.c_int64 * 8)()
+        self._check(load_library().stomp_chomp_info(self.h, v))
+        d = dict(zip(self.INFO, [int(x) for x in v]))
+        d["S"] = self.engine.S
+        return d
+
+    def close(self):
+        if getattr(self, "h", None):
+            load_library().stomp_chomp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Stream:

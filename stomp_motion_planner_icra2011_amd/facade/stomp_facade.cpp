@@ -60,6 +60,7 @@ StompOptimizer::StompOptimizer(StompTrajectory* trajectory, const StompRobotMode
     // the descriptor's tables: copies owned here (createSibling reads them any time later)
     segments_ = robot_model->segments;
     joints_ = robot_model->joints;
+    update_limits_ = robot_model->joint_update_limits;
     spheres_ = robot_model->collision_points;
     inertias_ = robot_model->inertias;
     noise_stddev_ = p.noise_stddev;
@@ -151,11 +152,66 @@ stomp_engine* StompOptimizer::createSibling(int num_rollouts, int num_reused_rol
 bool StompOptimizer::optimize()
 {
     if (!engine_) return false;
+    if (parameters_->use_chomp) return optimizeChomp();   // stomp_optimizer.cpp:289-299
     stats_ = STOMPStatistics();
     stats_.costs.assign(parameters_->max_iterations > 0 ? parameters_->max_iterations : 1, 0.0);
     stomp_stats st{};
     if (!check(stomp_engine_optimize(engine_, &st, stats_.costs.data()))) return false;
     return finishOptimize(st);
+}
+
+// optimize() with use_chomp: one descent from the policy's parameters (copyPolicyToGroupTrajectory,
+// stomp_optimizer.cpp:268) on the engine's model, field and cost (stomp_chomp_*); the statistics and
+// the best trajectory are written back as the STOMP path writes them.  No torques: the engine's
+// torque read-back is of its own best trajectory, which this mode does not touch.
+bool StompOptimizer::optimizeChomp()
+{
+    const StompParameters& pr = *parameters_;
+    std::vector<double> limits = update_limits_;
+    if (limits.empty()) limits.assign(J_, 0.05);   // stomp_robot_model.cpp:78
+    if ((int)limits.size() != J_) {
+        error_ = "joint_update_limits needs one entry per planning-group joint";
+        return false;
+    }
+    stomp_chomp_params cp{};
+    cp.struct_size = (int32_t)sizeof cp;
+    cp.learning_rate = pr.learning_rate;
+    cp.smoothness_cost_weight = pr.smoothness_cost_weight;
+    cp.use_pseudo_inverse = pr.use_pseudo_inverse ? 1 : 0;
+    cp.pseudo_inverse_ridge_factor = pr.pseudo_inverse_ridge_factor;
+    cp.joint_update_limits = limits.data();
+    cp.use_hamiltonian_monte_carlo = pr.use_hamiltonian_monte_carlo ? 1 : 0;
+    stomp_chomp* c = nullptr;
+    if (stomp_chomp_create(engine_, &cp, &c) != 0) {
+        error_ = stomp_last_error();
+        return false;
+    }
+    stats_ = STOMPStatistics();
+    const int stride = pr.max_iterations > 0 ? pr.max_iterations : 1;
+    stats_.costs.assign(stride, 0.0);
+    stomp_stats st{};
+    std::vector<double> best((size_t)J_ * N_);
+    double cost = 0.0, cf = 0.0;
+    const bool ok = stomp_chomp_reset(c, 1, nullptr) == 0 &&
+                    stomp_chomp_optimize(c, &st, stats_.costs.data(), stride, best.data()) == 0 &&
+                    stomp_chomp_get(c, "cost", &cost) == 0 && stomp_chomp_get(c, "collision_free", &cf) == 0;
+    if (!ok) error_ = stomp_chomp_last_error(c);
+    stomp_chomp_destroy(c);
+    if (!ok) return false;
+    stats_.iterations = st.iterations;
+    stats_.success = st.success != 0;
+    stats_.success_iteration = st.success_iteration;
+    stats_.collision_success_iteration = st.collision_success_iteration;
+    stats_.last_improvement_iteration = st.last_improvement_iteration;
+    stats_.best_cost = st.best_cost;
+    stats_.costs.resize(st.iterations);
+    last_cost_ = cost;
+    last_cf_ = cf != 0.0;
+    last_cs_ = true;   // stomp_optimizer.cpp:231
+    trajectory_->free.assign(J_, VectorXd(N_));
+    for (int j = 0; j < J_; ++j)
+        for (int t = 0; t < N_; ++t) trajectory_->free[j][t] = best[(size_t)j * N_ + t];
+    return true;
 }
 
 // the statistics of a finished loop (stats_.costs holds the cost history) and the best trajectory
