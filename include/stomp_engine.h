@@ -323,6 +323,8 @@ int stomp_engine_model_info(stomp_engine* e, int64_t info[12]);
  * There is no velocity factor (a robot standing still has a cost here, unlike stomp_engine_eval's
  * waypoint costs) and no gradient: getDistanceGradient's gradient belongs to the third-party
  * distance_field package, which the reference tree does not hold, and only the CHOMP path reads it.
+ * (Since CHOMP mode that gradient has a stated definition here, and stomp_engine_query_gradients
+ * below answers with it; this call stays as it is.)
  * An output pointer that is NULL is not computed.
  * Model and field: the model the engine holds now (after a retarget request with other collision
  * points S is the new S, stomp_engine_model_info info[0]) and the field it reads now (after
@@ -369,6 +371,70 @@ int stomp_engine_query_info(stomp_engine* e, int64_t info[4]);
 /* Device time of the last query call's launches, milliseconds (events around each chunk's launches,
  * summed; the copies are outside).  Host only. */
 int stomp_engine_query_time(stomp_engine* e, double* kernel_ms);
+
+/* The gradient query: srv/GetChompCollisionCost.srv whole -- per link the cost and "the joint velocity
+ * that will move the link away from collisions" (msg/JointVelocityArray.msg), and in_collision -- for a
+ * batch of M joint states against the engine's current model and field.  Every sum is sequential from
+ * 0.0 in the stated order, everything fp64 with one rounding per operation (tests/CHOMP.md's rules).
+ * For state m and sphere s (the engine's current collision points, in their order):
+ *   the centre p is stomp_engine_query_states' positions;
+ *   (dist, fg) is the field gradient of the CHOMP section below: the nearest-cell rule, then the
+ *     central differences of sqrt(d2) * resolution over the six neighbours times 1 / (2 resolution); a
+ *     cell outside [1, n - 2] on any axis reads distance 0 and gradient (0, 0, 0);
+ *   fgb = fg + field_bias per component (StompCollisionSpace::field_bias_*, CHOMP's parameter);
+ *   the potential and its gradient pg are stomp_collision_space.h:206-227 with d = dist - radius:
+ *     d >= clearance: 0 and (0, 0, 0); 0 <= d < clearance: diff = d - clearance, gm = diff *
+ *     inv_clearance, 0.5 * gm * diff and gm * fgb; d < 0: -d + 0.5 * clearance and fgb.  The sphere
+ *     collides when dist <= radius.  The bias does not enter the potential;
+ *   the Jacobian column of joint k is axis x (p - origin) with the joint's world-frame origin and axis
+ *     (CHOMP section; tests/CHOMP.md "Joint origin and axis", "Jacobian column") for a joint on the path
+ *     from the root to the sphere's segment, three zeros otherwise (a joint that drives no segment
+ *     included);
+ *   the sphere's joint term is t_k = 0; t_k += J(r, k) * pg_r for r = 0, 1, 2.
+ * Outputs:
+ *   field_gradients      fg, before the bias;       potential_gradients  pg;
+ *   link_gradients       [l][k]: a = 0; a -= t_k(s) over the spheres on segment links[l] in ascending
+ *                        s (0.0 for a segment without spheres; a segment may be listed more than once).
+ *                        The sign is CHOMP's collision_increments -= J^T g: a joint velocity that
+ *                        lowers the potential;
+ *   state_gradient       [k]: the same fold over all spheres;
+ *   link_costs, state_cost, in_collision   stomp_engine_query_states' values, with the same bits.
+ * Every sphere takes part in the folds: the descent's skip of a sphere with potential <= 1e-10 and its
+ * break after the first colliding sphere (stomp_optimizer.cpp:430-431, :451-460) are rules of CHOMP's
+ * fold, not of this service.  States are never clipped.  An output pointer that is NULL is not computed.
+ * The sign inside an obstacle: in the clearance band (0 <= d < clearance) gm < 0 turns the field
+ * gradient round and the velocity leads away from the obstacle; for d < 0 the reference takes the field
+ * gradient as it is (stomp_collision_space.h:222-226) although the potential there falls along it, so
+ * the velocity leads further in.  The call keeps the reference's sign, as CHOMP mode does; a caller
+ * that wants the way out of a penetration negates the gradient of a link whose spheres penetrate.
+ * Around the call everything is as stomp_engine_query_states: the engine's current model and field
+ * (the bricked copy where there is one), the engine's stream and a wait, host arrays, the same staging
+ * held with a capacity (a repeated call of the same size allocates nothing), the same 48 MiB chunks and
+ * STOMP_DEBUG_QUERY_CHUNK; stomp_engine_query_info / _time report the last query call of either kind
+ * (one launch per chunk here: the outputs leave the kernel in the caller's shape).  Nothing else of
+ * the engine changes, and a sharded engine may be asked.
+ * STOMP_E_INVALID, before any device is touched and with no output written: the refusals of
+ * stomp_engine_query_states (link_gradients without links as link_costs) and a field_bias that is not
+ * finite; the NULL and struct_size refusals come before the engine is read.  STOMP_E_UNSUPPORTED: a
+ * field with fewer than 3 cells on an axis (as CHOMP mode), a model whose frames and terms need more
+ * than 64 KiB of LDS. */
+typedef struct stomp_gradient_query {
+    int32_t struct_size;            /* sizeof(stomp_gradient_query) */
+    int32_t num_states;             /* M >= 1 */
+    const double* states;           /* [M][J] */
+    int32_t num_links;              /* L >= 0 */
+    const int32_t* links;           /* [L] segment indices */
+    double field_bias[3];           /* 0 */
+    /* outputs; each may be NULL (not computed) */
+    double*  field_gradients;       /* [M][S][3] */
+    double*  potential_gradients;   /* [M][S][3] */
+    double*  link_costs;            /* [M][L] */
+    double*  link_gradients;        /* [M][L][J] */
+    double*  state_cost;            /* [M] */
+    double*  state_gradient;        /* [M][J] */
+    uint8_t* in_collision;          /* [M] */
+} stomp_gradient_query;
+int stomp_engine_query_gradients(stomp_engine* e, const stomp_gradient_query* q);
 
 int stomp_engine_get_theta(stomp_engine* e, double* theta);
 int stomp_engine_set_theta(stomp_engine* e, const double* theta);

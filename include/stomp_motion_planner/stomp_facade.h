@@ -417,6 +417,14 @@ struct StateCost {
     int min_sphere = -1;
 };
 
+// GetChompCollisionCost.srv's response for one state (StompOptimizer::getChompCollisionCost)
+struct ChompCollisionCost {
+    bool valid = false;
+    std::vector<double> costs;                   // [L]
+    std::vector<std::vector<double>> gradient;   // [L][num_joints] (msg/JointVelocityArray.msg per link)
+    bool in_collision = false;
+};
+
 class StompOptimizer : public Task {
 public:
     // stomp_optimizer.cpp:50-70 (the ROS publishers are not taken, see the file header)
@@ -523,6 +531,17 @@ public:
     // optimizer is otherwise untouched.  false with lastError() when refused; out is unchanged then.
     bool getStateCosts(const std::vector<std::vector<double>>& states, const std::vector<int>& link_segments,
                        std::vector<StateCost>& out);
+    // The reference's GetChompCollisionCost.srv (declared there, never implemented), over
+    // stomp_engine_query_gradients: out[m].costs[l] as getStateCosts gives them, gradient[l] "the joint
+    // velocity that will move the link away from collisions" -- minus J^T times the potential's
+    // gradient, summed over the collision points on link_segments[l] (every point takes part; the
+    // sign and the penetrating branch are the reference's, see stomp_engine.h) --, in_collision, and
+    // valid: every limited joint inside its limits (the state is not clipped).  field_bias: 3 values,
+    // StompCollisionSpace::field_bias_x_/y_/z_ of the reference; nullptr: zeros, as the descent of
+    // optimize() with use_chomp takes them (this facade holds no bias of its own).  The optimizer is
+    // otherwise untouched.  false with lastError() when refused; out is unchanged then.
+    bool getChompCollisionCost(const std::vector<std::vector<double>>& states, const std::vector<int>& link_segments,
+                               std::vector<ChompCollisionCost>& out, const double* field_bias = nullptr);
 
     // Task (stomp_optimizer.cpp:1063-1165, 1167-1182)
     bool initialize(int num_time_steps) override;

@@ -17,10 +17,10 @@ LIB = os.path.join(PKG, "libstomp_engine.so")
 BUILD = os.path.join(ROOT, "build")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-SOURCES = ["k_noise.hip", "k_cost.hip", "k_terms.hip", "k_weights.hip", "k_misc.hip", "k_query.hip", "k_chomp.hip", "k_sdf.hip", "selftest.hip", "engine.cpp", "engine_create.cpp",
-           "engine_exchange.cpp", "engine_group.cpp", "engine_serve.cpp", "engine_retarget.cpp", "engine_query.cpp", "engine_chomp.cpp", "sdf_build.cpp", "scene.cpp", "setup.cpp"]
+SOURCES = ["k_noise.hip", "k_cost.hip", "k_terms.hip", "k_weights.hip", "k_misc.hip", "k_query.hip", "k_query_grad.hip", "k_chomp.hip", "k_sdf.hip", "selftest.hip", "engine.cpp", "engine_create.cpp",
+           "engine_exchange.cpp", "engine_group.cpp", "engine_serve.cpp", "engine_retarget.cpp", "engine_query.cpp", "engine_query_grad.cpp", "engine_chomp.cpp", "sdf_build.cpp", "scene.cpp", "setup.cpp"]
 HEADERS = ["engine_internal.h", "engine_group.h", "kernels.h", "setup.h", "stomp_math.h", "device_fk.h", "stamps.h", "noise_device.h", "limits_device.h", "update_device.h",
-           "sdf_lattice.h", "query.h", "chomp.h"]
+           "sdf_lattice.h", "query.h", "chomp.h", "field_gradient.h", "query_grad.h", "query_grad_host.h"]
 
 # One rounding per operation on host and device (parity with the oracle's FP contract).
 COMMON = ["-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-Wall",

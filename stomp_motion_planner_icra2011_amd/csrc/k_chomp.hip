@@ -22,50 +22,12 @@
 
 #include "chomp.h"
 #include "device_fk.h"
+#include "field_gradient.h"
 #include "limits_device.h"
 
 namespace stomp {
 
 namespace {
-
-// the voxel (ix, iy, iz) in the layout of the field (sdf_cell's two index rules)
-template <bool BRICK>
-__device__ __forceinline__ unsigned voxel_index(const DevModel& m, int ix, int iy, int iz)
-{
-    if constexpr (BRICK) {
-        const unsigned b = (((unsigned)ix >> 2) * (unsigned)m.nby + ((unsigned)iy >> 2)) * (unsigned)m.nbz +
-                           ((unsigned)iz >> 2);
-        return (b << 6) | (((unsigned)ix & 3u) << 4) | (((unsigned)iy & 3u) << 2) | ((unsigned)iz & 3u);
-    } else {
-        return ((unsigned)ix * (unsigned)m.ny + (unsigned)iy) * (unsigned)m.nz + (unsigned)iz;
-    }
-}
-
-// distance_field getDistanceGradient (third party; the definition is in stomp_engine.h and
-// DESIGN.md): the distance at the nearest cell and the central differences of sqrt(d2) res over
-// its six neighbours; a centre whose cell is outside [1, n - 2] on an axis reads 0 and (0, 0, 0).
-// The cell rule is sdf_cell's.  The seven loads go out together; a lane outside reads cell 0.
-template <bool BRICK>
-__device__ __forceinline__ double field_gradient(const DevModel& m, const double* p, double* g)
-{
-    const int ix = (int)((p[0] - m.ox) * m.inv_res + 0.5);
-    const int iy = (int)((p[1] - m.oy) * m.inv_res + 0.5);
-    const int iz = (int)((p[2] - m.oz) * m.inv_res + 0.5);
-    const bool ok = ix >= 1 && iy >= 1 && iz >= 1 && ix <= m.nx - 2 && iy <= m.ny - 2 && iz <= m.nz - 2;
-    const int cx = ok ? ix : 1, cy = ok ? iy : 1, cz = ok ? iz : 1;   // (a grid has at least 3 cells per axis)
-    const unsigned c = m.sdf[voxel_index<BRICK>(m, cx, cy, cz)];
-    const unsigned xp = m.sdf[voxel_index<BRICK>(m, cx + 1, cy, cz)], xm = m.sdf[voxel_index<BRICK>(m, cx - 1, cy, cz)];
-    const unsigned yp = m.sdf[voxel_index<BRICK>(m, cx, cy + 1, cz)], ym = m.sdf[voxel_index<BRICK>(m, cx, cy - 1, cz)];
-    const unsigned zp = m.sdf[voxel_index<BRICK>(m, cx, cy, cz + 1)], zm = m.sdf[voxel_index<BRICK>(m, cx, cy, cz - 1)];
-    const double inv_twice = 1.0 / (2.0 * m.res);
-    const double gx = (sdf_metres(m, xp) - sdf_metres(m, xm)) * inv_twice;
-    const double gy = (sdf_metres(m, yp) - sdf_metres(m, ym)) * inv_twice;
-    const double gz = (sdf_metres(m, zp) - sdf_metres(m, zm)) * inv_twice;
-    g[0] = ok ? gx : 0.0;
-    g[1] = ok ? gy : 0.0;
-    g[2] = ok ? gz : 0.0;
-    return ok ? sdf_metres(m, c) : 0.0;
-}
 
 // the centre of sphere s at waypoint i of the whole trajectory (0 .. N + 11) of descent b: the
 // padding waypoints' centres do not depend on the descent (the model's pad_pos, [12][S][3])
@@ -120,12 +82,7 @@ __global__ __launch_bounds__(kChompBlock) void k_chomp_fk(DevModel m, ChompArgs 
         const int sgi = a.joint_seg[k];
         if (sgi >= 0) {
             const Frame f = fr[sgi];
-            const DevSegment sg = m.segs[sgi];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                o[i] = f.p[i];
-                ax[i] = f.R[3 * i + 0] * sg.axis[0] + f.R[3 * i + 1] * sg.axis[1] + f.R[3 * i + 2] * sg.axis[2];
-            }
+            joint_origin_axis(f, m.segs[sgi], o, ax);
         }
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
@@ -147,23 +104,7 @@ __global__ __launch_bounds__(kChompBlock) void k_chomp_fk(DevModel m, ChompArgs 
             a.fgrad[3 * e + i] = fg[i];
             fg[i] += a.bias[i];       // stomp_collision_space.h:202-204
         }
-        // getCollisionPointPotentialGradient (stomp_collision_space.h:206-227)
-        const double d = dist - sp.radius;
-        double pot;
-        if (d >= sp.clearance) {
-            pot = 0.0;
-            pg[0] = pg[1] = pg[2] = 0.0;
-        } else if (d >= 0.0) {
-            const double diff = d - sp.clearance;
-            const double gm = diff * sp.inv_clearance;
-            pot = 0.5 * gm * diff;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) pg[i] = gm * fg[i];
-        } else {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) pg[i] = fg[i];
-            pot = -d + 0.5 * sp.clearance;
-        }
+        const double pot = potential_gradient(sp, dist, fg, pg);   // stomp_collision_space.h:206-227
         const int col = dist <= sp.radius ? 1 : 0;
         any |= col;
         a.dist[e] = dist;
@@ -219,16 +160,7 @@ __global__ __launch_bounds__(kChompBlock) void k_chomp_vel(DevModel m, ChompArgs
 __device__ __forceinline__ void jac_column(const ChompArgs& a, size_t w, unsigned mask, int k, const double* p,
                                            double* c)
 {
-    if (!((mask >> k) & 1u)) {
-        c[0] = c[1] = c[2] = 0.0;
-        return;
-    }
-    const double* o = a.jorg + (w * a.J + k) * 3;
-    const double* ax = a.jax + (w * a.J + k) * 3;
-    const double d0 = p[0] - o[0], d1 = p[1] - o[1], d2 = p[2] - o[2];
-    c[0] = ax[1] * d2 - ax[2] * d1;
-    c[1] = ax[2] * d0 - ax[0] * d2;
-    c[2] = ax[0] * d1 - ax[1] * d0;
+    jacobian_column((mask >> k) & 1u, a.jorg + (w * a.J + k) * 3, a.jax + (w * a.J + k) * 3, p, c);
 }
 
 // LDS: each sphere's term per joint [S][J], then each sphere's flags [S] (1: it has a term, 2: it collides)

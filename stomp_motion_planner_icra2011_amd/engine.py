@@ -68,6 +68,15 @@ class stomp_state_query(C.Structure):
                 ("in_collision", C.POINTER(C.c_uint8)), ("limits_violated", C.POINTER(C.c_uint8))]
 
 
+class stomp_gradient_query(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("num_states", C.c_int32), ("states", C.POINTER(C.c_double)),
+                ("num_links", C.c_int32), ("links", C.POINTER(C.c_int32)), ("field_bias", C.c_double * 3),
+                ("field_gradients", C.POINTER(C.c_double)), ("potential_gradients", C.POINTER(C.c_double)),
+                ("link_costs", C.POINTER(C.c_double)), ("link_gradients", C.POINTER(C.c_double)),
+                ("state_cost", C.POINTER(C.c_double)), ("state_gradient", C.POINTER(C.c_double)),
+                ("in_collision", C.POINTER(C.c_uint8))]
+
+
 class stomp_attached_body(C.Structure):
     _fields_ = [("segment", C.c_int32), ("shape", stomp_shape)]
 
@@ -144,7 +153,7 @@ EXPORTED = ["stomp_engine_create", "stomp_engine_destroy", "stomp_engine_last_er
             "stomp_group_serve", "stomp_group_serve_info", "stomp_serve_schedule", "stomp_engine_query_states",
             "stomp_engine_query_info", "stomp_engine_query_time", "stomp_chomp_create", "stomp_chomp_reset",
             "stomp_chomp_step", "stomp_chomp_synchronize", "stomp_chomp_optimize", "stomp_chomp_get",
-            "stomp_chomp_info", "stomp_chomp_last_error", "stomp_chomp_destroy"]
+            "stomp_chomp_info", "stomp_chomp_last_error", "stomp_chomp_destroy", "stomp_engine_query_gradients"]
 
 _lib = None
 
@@ -250,6 +259,8 @@ def load_library(path: Optional[str] = None):
         l.stomp_engine_query_states.argtypes = [P, C.POINTER(stomp_state_query)]
         l.stomp_engine_query_info.argtypes = [P, C.POINTER(C.c_int64)]
         l.stomp_engine_query_time.argtypes = [P, dp]
+    if hasattr(l, "stomp_engine_query_gradients"):
+        l.stomp_engine_query_gradients.argtypes = [P, C.POINTER(stomp_gradient_query)]
     if hasattr(l, "stomp_chomp_create"):   # (a variant library named by STOMP_ENGINE_LIB may predate them)
         l.stomp_chomp_create.argtypes = [P, C.POINTER(stomp_chomp_params), C.POINTER(C.c_void_p)]
         l.stomp_chomp_reset.argtypes = [P, C.c_int32, dp]
@@ -449,6 +460,12 @@ class StateQueryResult:
     """Engine.query_states' arrays, one attribute per output of stomp_state_query (None: not asked for)."""
     positions = distances = potentials = sphere_collides = link_costs = state_cost = None
     min_clearance = min_sphere = in_collision = limits_violated = None
+
+
+class GradientQueryResult:
+    """Engine.query_gradients' arrays, one attribute per output of stomp_gradient_query (None: not asked for)."""
+    field_gradients = potential_gradients = link_costs = link_gradients = None
+    state_cost = state_gradient = in_collision = None
 
 
 class Engine:
@@ -701,6 +718,66 @@ class Engine:
         for k in self.QUERY_OUTPUTS:
             a = out.get(k)
             if a is not None and k in ("sphere_collides", "in_collision", "limits_violated"):
+                a = a.astype(bool)
+            setattr(res, k, a)
+        return res
+
+    # stomp_gradient_query's outputs: name -> (dtype, shape of one state; S spheres, L links, J joints)
+    GRADIENT_OUTPUTS = dict(field_gradients=(np.float64, "S3"), potential_gradients=(np.float64, "S3"),
+                            link_costs=(np.float64, "L"), link_gradients=(np.float64, "LJ"),
+                            state_cost=(np.float64, ""), state_gradient=(np.float64, "J"),
+                            in_collision=(np.uint8, ""))
+    GRADIENT_DEFAULT = ("link_costs", "link_gradients", "state_cost", "state_gradient", "in_collision")
+
+    def query_gradients(self, states, links=None, field_bias=(0.0, 0.0, 0.0), want=GRADIENT_DEFAULT, fill=None):
+        """stomp_engine_query_gradients (srv/GetChompCollisionCost.srv): the M joint states (M x J, or
+        one state of J values) against the engine's current model and field.  links: segment indices
+        or link names; field_bias: CHOMP's field_bias; want: the names of stomp_gradient_query's
+        outputs to compute (default: the per-link and per-state ones; the per-link ones only with
+        links).  Returns a GradientQueryResult of numpy arrays (None where not asked for;
+        in_collision is a bool array).  fill: as in query_states."""
+        q = np.ascontiguousarray(states, np.float64)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        if q.ndim != 2 or q.shape[1] != self.J:
+            raise ValueError(f"states must be M x {self.J}")
+        M = q.shape[0]
+        names = [s.name for s in self.problem.robot.segments]
+        idx = [names.index(v) if isinstance(v, str) else int(v) for v in (links if links is not None else [])]
+        L = len(idx)
+        lk = np.ascontiguousarray(idx, np.int32)
+        unknown = [k for k in want if k not in self.GRADIENT_OUTPUTS]
+        if unknown:
+            raise KeyError(f"no such gradient query outputs: {unknown}")
+        S = self.S
+        dims = {"S3": (S, 3), "L": (L,), "LJ": (L, self.J), "J": (self.J,), "": ()}
+        out = {}
+        for k in want:
+            if k in ("link_costs", "link_gradients") and links is None:
+                continue
+            dt, shp = self.GRADIENT_OUTPUTS[k]
+            out[k] = np.zeros((M,) + dims[shp], dt) if fill is None else np.full((M,) + dims[shp], fill, dt)
+        gq = stomp_gradient_query()
+        gq.struct_size = C.sizeof(stomp_gradient_query)
+        gq.num_states = M
+        gq.states = _dp(q)
+        gq.num_links = L
+        gq.links = lk.ctypes.data_as(C.POINTER(C.c_int32)) if L else None
+        gq.field_bias = (C.c_double * 3)(*[float(v) for v in field_bias])
+        for k, a in out.items():
+            ct = C.c_uint8 if self.GRADIENT_OUTPUTS[k][0] is np.uint8 else C.c_double
+            setattr(gq, k, a.ctypes.data_as(C.POINTER(ct)))
+        rc = load_library().stomp_engine_query_gradients(self.h, C.byref(gq))
+        if rc != 0:
+            try:
+                _check(rc)
+            except RuntimeError as err:
+                err.outputs = out
+                raise
+        res = GradientQueryResult()
+        for k in self.GRADIENT_OUTPUTS:
+            a = out.get(k)
+            if a is not None and k == "in_collision":
                 a = a.astype(bool)
             setattr(res, k, a)
         return res

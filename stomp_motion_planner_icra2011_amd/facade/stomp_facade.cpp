@@ -553,6 +553,62 @@ bool StompOptimizer::getStateCosts(const std::vector<std::vector<double>>& state
     return true;
 }
 
+// GetChompCollisionCost.srv over stomp_engine_query_gradients: one call for all states
+bool StompOptimizer::getChompCollisionCost(const std::vector<std::vector<double>>& states,
+                                           const std::vector<int>& link_segments,
+                                           std::vector<ChompCollisionCost>& out, const double* field_bias)
+{
+    if (!engine_) return false;
+    const size_t M = states.size(), L = link_segments.size(), J = (size_t)J_;
+    if (M == 0) {
+        error_ = "getChompCollisionCost: no states";
+        return false;
+    }
+    std::vector<double> q;
+    for (const auto& s : states) {
+        if (s.size() != J) {
+            error_ = "getChompCollisionCost: a state must hold num_joints values";
+            return false;
+        }
+        q.insert(q.end(), s.begin(), s.end());
+    }
+    const std::vector<int32_t> links(link_segments.begin(), link_segments.end());
+    std::vector<double> costs(M * L), grads(M * L * J);
+    std::vector<uint8_t> collision(M);
+    stomp_gradient_query gq{};
+    gq.struct_size = (int32_t)sizeof gq;
+    gq.num_states = (int32_t)M;
+    gq.states = q.data();
+    gq.num_links = (int32_t)L;
+    gq.links = L ? links.data() : nullptr;
+    for (int k = 0; k < 3; ++k) gq.field_bias[k] = field_bias ? field_bias[k] : 0.0;
+    gq.link_costs = L ? costs.data() : nullptr;
+    gq.link_gradients = L ? grads.data() : nullptr;
+    gq.in_collision = collision.data();
+    const int rc = stomp_engine_query_gradients(engine_, &gq);
+    if (rc != 0) {
+        // (a refusal writes nothing of the engine, not even its message: the thread's last error has it)
+        error_ = engine_error(rc == STOMP_E_DEVICE ? engine_ : nullptr, rc);
+        return false;
+    }
+    out.assign(M, ChompCollisionCost());
+    for (size_t m = 0; m < M; ++m) {
+        ChompCollisionCost& c = out[m];
+        c.valid = true;
+        for (size_t j = 0; j < J; ++j) {
+            const stomp_joint& jt = joints_[j];
+            const double x = states[m][j];
+            if (jt.has_limits && !(jt.min <= x && x <= jt.max)) c.valid = false;
+        }
+        c.costs.assign(costs.begin() + m * L, costs.begin() + (m + 1) * L);
+        c.gradient.resize(L);
+        for (size_t l = 0; l < L; ++l)
+            c.gradient[l].assign(grads.begin() + (m * L + l) * J, grads.begin() + (m * L + l + 1) * J);
+        c.in_collision = collision[m] != 0;
+    }
+    return true;
+}
+
 bool StompOptimizer::retargetBatch(const std::vector<StompOptimizer*>& optimizers,
                                    const std::vector<std::vector<double>>& starts,
                                    const std::vector<std::vector<double>>& goals, const std::vector<uint64_t>& seeds,
