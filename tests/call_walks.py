@@ -9,6 +9,10 @@ is biased towards ordered pairs of op kinds that the scripts of the seeds before
 so a mode's census (tests/test_call_walks.py) closes in few seeds: make_script(mode, s) therefore
 walks the seeds 0 .. s in turn and returns the last script.
 
+The ask modes (third round) add calls that must leave an engine as it was: state queries, gradient
+queries and one CHOMP object per pair (class Asks).  The books track the descent's state only; an ask
+changes nothing else of a book, and the oracle side of a pair never hears of one.
+
 replay(mode, script, pair) runs a literal script.  A pair compares only what an op returns
 (assert_array_equal / ==, no tolerance); state is read by the `observe` ops alone, at the random
 points where the walk put them.  Every assertion message carries the mode, the failing op's index
@@ -22,9 +26,12 @@ import numpy as np
 
 from oracle import pyoracle as po
 from stomp_motion_planner_icra2011_amd import problem as pb
+from tests import chomp_util as cu
+from tests import gradient_query_util as gqu
 from tests import group_util as gu
 from tests import model_zoo as mz
 from tests import pi_steps_util as su
+from tests import state_query_util as squ
 
 try:   # the CPU tests make scripts and run oracles without the engine library
     from stomp_motion_planner_icra2011_amd import engine as eng
@@ -151,6 +158,70 @@ def assert_attach_matters(p):
         assert not np.array_equal(c.rollouts("state_costs"), b.rollouts("state_costs")), choice
 
 
+_MATTERS = set()
+
+
+def assert_asks_matter(mode, made=None):
+    """On the references alone, before any device is touched (once per process and mode): what the
+    walk changes under an ask changes what the ask must return, so an ask answered from a stale
+    problem, model, field or theta cannot pass."""
+    if mode in _MATTERS:
+        return
+    spec = MODES[mode]
+    made = spec["make"]() if made is None else made
+    p = made[DESCENT_MEMBER] if spec["kind"] == "group" else made
+    if spec.get("scene"):
+        p = dataclasses.replace(p, sdf=po.sdf_build_objects(p.grid, scene_static_layer(p, 0))[0])
+    prm = spec.get("chomp", _CHOMP_PLAIN)
+    links = list(range(len(p.robot.segments)))
+    assert mode_info(mode).get("nseg") == len(links), (mode, mode_info(mode), len(links))   # the books draw links from it
+    q = squ.make_states(p, 65, 0)
+
+    def first(problem, start=None):
+        r = cu.ChompRef(problem, prm)
+        r.reset(start)
+        return r.snapshot()
+
+    # some drawn query state has a potential and a link gradient that are not zero
+    g = gqu.reference(p, q, links)
+    assert g.potentials.any() and g.link_gradients.any(), mode
+    if spec["kind"] == "ranks":
+        _MATTERS.add(mode)
+        return
+    # the mode's retarget changes the descent's first snapshot (beyond the trajectory itself)
+    base = first(p)
+    if spec["kind"] == "group":
+        t = spec["targets"]()
+        moved_p = dataclasses.replace(p, start=t[1].start.copy(), goal=t[1].goal.copy())
+    else:
+        moved_p = moved(p, 1)
+    assert not np.array_equal(first(moved_p)["potentials"], base["potentials"]), mode
+    if spec.get("request"):
+        # the attached sphere has a query potential and a descent potential of its own
+        att = dataclasses.replace(p, spheres=request_spheres(p, "attach"))
+        at = max(i for i, s in enumerate(att.spheres) if s.segment == len(p.robot.segments) - 1)
+        assert squ.reference(att, q, links).potentials[:, at].any(), mode
+        assert first(att)["potentials"][:, at].any(), mode
+        rad = dataclasses.replace(p, spheres=request_spheres(p, "radius_only"))
+        assert not np.array_equal(first(rad)["potentials"], base["potentials"]), mode
+    if spec.get("scene"):
+        # every change of the dynamic set that the pair calls a change (none -> box -> moved_box)
+        # and of the static layer changes a query distance and a descent's distances
+        fields = [po.sdf_build_objects(p.grid, scene_static_layer(p, l) + scene_dynamic_set(p, v))[0]
+                  for l, v in ((0, 0), (0, 1), (0, 2), (1, 0))]
+        for a, b in ((0, 1), (1, 2), (0, 2), (0, 3)):
+            pa, pb_ = dataclasses.replace(p, sdf=fields[a]), dataclasses.replace(p, sdf=fields[b])
+            assert not np.array_equal(squ.reference(pa, q, []).distances, squ.reference(pb_, q, []).distances), (mode, a, b)
+            assert not np.array_equal(first(pa)["distances"], first(pb_)["distances"]), (mode, a, b)
+    if spec["kind"] == "group":
+        # a reset from theta after an iteration is not a reset from theta_0
+        o = po.Oracle(p, threads=spec.get("threads", 1))
+        o.iterate(1)
+        after = first(p, o.theta())
+        assert not np.array_equal(after["trajectory"], base["trajectory"]) and after["cost"] != base["cost"], mode
+    _MATTERS.add(mode)
+
+
 # ---------------------------------------------------------------------------- modes
 def _chain5(K, Kr, max_iterations, **kw):
     return lambda: mz.chain5(K=K, Kr=Kr, max_iterations=max_iterations, max_iterations_after_collision_free=1000, **kw)
@@ -210,6 +281,11 @@ def _shelf_targets():
     return flag_pair()
 
 
+# the CHOMP parameters of the ask modes: the reference's defaults with learning_rate 0.05; ask_request
+# with the pseudo-inverse and a field bias
+_CHOMP_PLAIN = cu.ChompParams(learning_rate=0.05)
+_CHOMP_PINV_BIAS = cu.ChompParams(learning_rate=0.05, use_pseudo_inverse=True, field_bias=gqu.BIAS)
+
 # kind: "single" / "group" / "ranks"; make: the problem(s); env: set before creation; expect: pieces
 # the engine's own `stomp: model` line (STOMP_DEBUG_LEAN_PRINT) must hold; length: ops per script;
 # seeds: scripts per mode, the smallest count at which the census of tests/test_call_walks.py holds
@@ -267,6 +343,24 @@ MODES = {
     "group_serve_shelf": dict(kind="group", make=_group_shelf, env={}, serve=True, targets=_shelf_targets, threads=8,
                               length=30, info=dict(P=4, Kr=5, cums=[False] * 4, max_its=[3, 4, 5, 6]),
                               expect=["group of 4 engines J 7 N 39 K 12 "]),
+    # ---- the third round: state queries, gradient queries and CHOMP descents among the calls above
+    "ask_reuse": dict(kind="single", make=_chain5(12, 5, 4), env={"STOMP_DEBUG_NO_SPEC": "0", "STOMP_DEBUG_NO_PICK_FUSE": "0"},
+                      ask=True, chomp=_CHOMP_PLAIN,
+                      expect=["J 5 N 39 ", "pregen 1 fused_noise 1 brick 0", "launch of 13 rollouts: split,"]),
+    "ask_pregen": dict(kind="single", make=_chain5(20, 0, 6), env={}, ask=True, chomp=_CHOMP_PLAIN,
+                       expect=["pregen 1 fused_noise 1", "launch of 21 rollouts: "]),
+    "ask_request": dict(kind="single", make=_request(12, 5), env={}, request=True, threads=8, ask=True,
+                        chomp=_CHOMP_PINV_BIAS, expect=["J 12 N 39 ", "launch of 13 rollouts: "]),
+    "ask_scene_linear": dict(kind="single", make=_chain5(12, 5, 4, shape=(66, 66, 66)), env={"STOMP_SDF_LAYOUT": "linear"},
+                             scene=True, ask=True, chomp=_CHOMP_PLAIN, expect=["brick 0,"]),
+    "ask_scene_brick": dict(kind="single", make=_chain5(12, 5, 4, shape=(66, 66, 66)), env={"STOMP_SDF_LAYOUT": "brick"},
+                            scene=True, ask=True, chomp=_CHOMP_PLAIN, expect=["brick 1,"]),
+    "ask_group": dict(kind="group", make=_group_shelf, env={}, serve=True, targets=_shelf_targets, threads=8, length=30,
+                      ask=True, chomp=_CHOMP_PLAIN,
+                      info=dict(P=4, Kr=5, cums=[False] * 4, max_its=[3, 4, 5, 6], nseg=17),
+                      expect=["group of 4 engines J 7 N 39 K 12 "]),
+    "ask_ranks": dict(kind="ranks", make=_ranks, env={}, shard="partials", threads=8, length=20, ask=True,
+                      expect=["launch of 65 rollouts: "]),
 }
 # make_script seeds its generator with a mode's ident.  The first 16 are the modes' indices in
 # sorted order at the time the walks were written, frozen: a new mode must not move an old script.
@@ -277,6 +371,8 @@ IDENTS = {
     "request_reuse": 16, "request_pregen_cum": 17, "scene_linear": 18, "scene_brick": 19, "group_request": 20,
     "group_serve_reuse": 21, "group_serve_pregen": 22,
     "group_serve_shelf": 23,
+    "ask_reuse": 24, "ask_pregen": 25, "ask_request": 26, "ask_scene_linear": 27, "ask_scene_brick": 28, "ask_group": 29,
+    "ask_ranks": 30,
 }
 DEFAULT_LENGTH = 40
 # scripts per mode: see tests/CALL_WALKS.md for how they were found (test_call_walks.py asserts that
@@ -288,6 +384,8 @@ SEEDS = {
     "request_reuse": 16, "request_pregen_cum": 25, "scene_linear": 20, "scene_brick": 16, "group_request": 20,
     "group_serve_reuse": 12, "group_serve_pregen": 21,
     "group_serve_shelf": 22,
+    "ask_reuse": 24, "ask_pregen": 44, "ask_request": 38, "ask_scene_linear": 34, "ask_scene_brick": 64, "ask_group": 31,
+    "ask_ranks": 8,
 }
 
 
@@ -308,6 +406,95 @@ CONSTRAINT_CHOICES = ("keep", 0, 1, 2)
 # the scene modes: the field belongs to a scene of two layers on the engine's stream
 SCENE_KINDS = ("scene_dynamic", "scene_static")
 DYNAMIC_VARIANTS = ("none", "box", "moved_box", "outside")
+# the ask modes: calls that must leave the engine as it was -- the two queries and a CHOMP descent
+ASK_QUERIES = ("query_states", "query_gradients")
+DESCENT_KINDS = ("chomp_reset", "chomp_step", "chomp_get", "chomp_optimize", "chomp_refused")
+ASK_KINDS = ASK_QUERIES + DESCENT_KINDS
+GROUP_ASK_QUERIES = ("m_query_states", "m_query_gradients")
+ASKS = ASK_KINDS + GROUP_ASK_QUERIES
+CHOMP_REFUSALS = ("no_reset", "stale_target", "stale_model", "needs_fresh_reset")
+QUERY_M = (1, 63, 64, 65, 130)          # one state, a wave's edges, two waves and a partial one
+QS_OUTPUTS = ("positions", "distances", "potentials", "sphere_collides", "link_costs", "state_cost", "min_clearance",
+              "min_sphere", "in_collision", "limits_violated")
+GQ_OUTPUTS = gqu.OUTPUTS
+CHOMP_NAMES = tuple(cu.NAMES)
+DESCENT_MEMBER = 1                      # the group member whose engine the ask_group mode's descent borrows
+
+# The descent's state in a book: none (no reset yet) / fresh / stepped / optimized / stale_silent /
+# stale_target / stale_model.  A staling op leaves `none` as it is (the "no reset" refusal comes
+# first in check_live) and never lowers a stale state: the model's reason wins over the target's, and
+# both over stale_silent -- a field read in place that a scene op rewrote, which the library cannot
+# notice: no descent op but chomp_reset is drawn then, and no refusal, since none would come.
+_STALE_RANK = {"stale_silent": 1, "stale_target": 2, "stale_model": 3}
+_REFUSAL_OF = {"none": "no_reset", "stale_target": "stale_target", "stale_model": "stale_model",
+               "stepped": "needs_fresh_reset", "optimized": "needs_fresh_reset"}
+
+
+def descent_allows(state, kind):
+    if kind == "chomp_step":
+        return state in ("fresh", "stepped")
+    if kind == "chomp_get":
+        return state in ("fresh", "stepped", "optimized")
+    if kind == "chomp_optimize":
+        return state == "fresh"
+    if kind == "chomp_refused":
+        return state in _REFUSAL_OF
+    return True
+
+
+def descent_staled(state, reason):
+    new = "stale_" + reason
+    return state if state == "none" or _STALE_RANK.get(state, 0) >= _STALE_RANK[new] else new
+
+
+def descent_after(state, op):
+    kind = op[0]
+    assert descent_allows(state, kind), (op, state)
+    if kind == "chomp_reset":
+        assert 1 <= op[1] <= 3, op
+        return "fresh"
+    if kind == "chomp_step":
+        assert 1 <= op[1] <= 3, op
+        return "stepped"
+    if kind == "chomp_optimize":
+        return "optimized"
+    if kind == "chomp_get":
+        assert 1 <= len(op[1]) and set(op[1]) <= set(CHOMP_NAMES), op
+    if kind == "chomp_refused":
+        assert op[1] == _REFUSAL_OF[state], (op, state)
+    return state
+
+
+def _check_query(op, nseg):
+    """a query op's arguments (after a group's member index): seed, M, links, want[, biased]"""
+    kind, (seed, M, links, want) = op[0], op[1:5]
+    names = QS_OUTPUTS if kind.endswith("query_states") else GQ_OUTPUTS
+    assert M in QUERY_M and all(0 <= g < nseg for g in links) and len(set(links)) == len(links), op
+    assert want and set(want) <= set(names), op
+    assert links or not (set(want) & {"link_costs", "link_gradients"}), op
+
+
+def _ask_op(kind, state, nseg, rng):
+    """an ask of `kind` (a query without its member or rank) from seeds, small ints and names"""
+    if kind in ASK_QUERIES:
+        M = QUERY_M[int(rng.integers(len(QUERY_M)))]
+        links = tuple(g for g in range(nseg) if rng.random() < 0.4) if rng.random() < 0.8 else ()
+        names = QS_OUTPUTS if kind == "query_states" else GQ_OUTPUTS
+        ok = [n for n in names if links or n not in ("link_costs", "link_gradients")]
+        want = tuple(n for n in ok if rng.random() < 0.4) or (ok[int(rng.integers(len(ok)))],)
+        op = (kind, int(rng.integers(1 << 20)), M, links, want)
+        return op + (bool(rng.random() < 0.5),) if kind == "query_gradients" else op
+    if kind == "chomp_reset":
+        return ("chomp_reset", int(rng.integers(1, 4)), None if rng.random() < 0.5 else int(rng.integers(1 << 20)))
+    if kind == "chomp_step":
+        return ("chomp_step", int(rng.integers(1, 4)))
+    if kind == "chomp_get":
+        pick = sorted(rng.permutation(len(CHOMP_NAMES))[: int(rng.integers(1, 5))].tolist())
+        return ("chomp_get", tuple(CHOMP_NAMES[i] for i in pick))
+    if kind == "chomp_refused":
+        return ("chomp_refused", _REFUSAL_OF[state])
+    assert kind == "chomp_optimize", kind
+    return (kind,)
 
 
 class Book:
@@ -325,8 +512,10 @@ class Book:
         self.Kr, self.cum, self.device = problem_info["Kr"], problem_info["cum"], problem_info.get("device", False)
         self.max_it = problem_info["max_it"]
         self.request, self.scene = problem_info.get("request", False), problem_info.get("scene", False)
+        self.ask, self.nseg, self.brick = problem_info.get("ask", False), problem_info.get("nseg", 0), problem_info.get("brick", False)
         self.kinds = (SINGLE_KINDS + (("refresh_field",) if self.device else ()) + (("retarget_request",) if self.request else ())
-                      + (SCENE_KINDS if self.scene else ()))
+                      + (SCENE_KINDS if self.scene else ()) + (ASK_KINDS if self.ask else ()))
+        self.descent = "none"       # (outside reset(): a retarget makes a descent stale, it does not forget it)
         self.refusals = REQUEST_REFUSALS if self.request else REFUSALS
         self.reset()
 
@@ -337,6 +526,8 @@ class Book:
 
     def allowed(self, kind):
         closed = self.phase == "closed"
+        if kind in DESCENT_KINDS:
+            return self.ask and descent_allows(self.descent, kind)
         if kind in FUSED or kind == "pi_get_rollouts":
             return closed
         if kind == "pi_add_extra_rollout":
@@ -416,17 +607,33 @@ class Book:
             assert op[1] in (0, 1), op
         elif kind == "scene_check":     # (final_observe's: not in the alphabet)
             assert self.scene
+        elif kind in ASK_QUERIES:       # the asks change nothing above: that is the claim under test
+            assert self.ask
+            _check_query(op, self.nseg)
+        elif kind in DESCENT_KINDS:
+            self.descent = descent_after(self.descent, op)
         else:
             assert kind in ("execute", "set_timing", "pi_reset"), kind
+        # what makes a descent stale
+        if kind in ("retarget", "refresh_field"):
+            self.descent = descent_staled(self.descent, "target")
+        elif kind == "retarget_request":     # a replaced list changes the model, radius_only included
+            self.descent = descent_staled(self.descent, "target" if (op[3], op[4]) == ("keep", "keep") else "model")
+        elif kind in SCENE_KINDS:            # the bricked copy follows by a refresh call; a field read in place by none
+            self.descent = descent_staled(self.descent, "target" if self.brick else "silent")
 
     def final_observe(self):
         return ("observe", tuple(k for k in OBS_ORDER if k in self.valid))
 
     def final_ops(self):
-        return [self.final_observe()] + ([("scene_check",)] if self.scene else [])
+        live = self.ask and descent_allows(self.descent, "chomp_get")
+        return ([self.final_observe()] + ([("scene_check",)] if self.scene else [])
+                + ([("chomp_get", ("trajectory", "final_increments", "cost"))] if live else []))
 
 
 def _single_op(book, kind, rng):
+    if kind in ASK_KINDS:
+        return _ask_op(kind, book.descent, book.nseg, rng)
     if kind == "iterate":
         r = rng.random()
         nxt = book.next_it
@@ -489,7 +696,10 @@ class GroupBook:
         self.P, self.Kr, self.cums, self.max_its = info["P"], info["Kr"], info["cums"], info["max_its"]
         self.serve = info.get("serve", False)
         self.request = info.get("request", False)
-        self.kinds = GROUP_KINDS + (("g_serve",) if self.serve else ()) + (GROUP_REQUEST_KINDS if self.request else ())
+        self.ask, self.nseg = info.get("ask", False), info.get("nseg", 0)
+        self.kinds = (GROUP_KINDS + (("g_serve",) if self.serve else ()) + (GROUP_REQUEST_KINDS if self.request else ())
+                      + (GROUP_ASK_QUERIES + DESCENT_KINDS if self.ask else ()))
+        self.descent = "none"       # of the descent on member DESCENT_MEMBER's engine
         # the request mode: members that replaced a list of their model on their own since the last
         # g_retarget_requests (the group's copies of the models are behind them), and every
         # member's sphere layout (the engines a group plans are of one shape)
@@ -509,6 +719,8 @@ class GroupBook:
         return [m for m in range(self.P) if self.sig[m] != self.sig[self.lead[0]]] if self.lead else []
 
     def allowed(self, kind):
+        if kind in DESCENT_KINDS:
+            return self.ask and descent_allows(self.descent, kind)
         if kind == "g_refused_model":
             return self.request and bool(self.stale)
         if self.stale and kind in ("g_run", "g_run_refused", "g_synchronize", "g_optimize", "g_retarget", "g_serve"):
@@ -599,8 +811,17 @@ class GroupBook:
             self._iterated(m)
             if self.lockstep():
                 self.next_it, self.lead = it + 1, None
+        elif kind in GROUP_ASK_QUERIES:
+            assert self.ask and 0 <= op[1] < self.P, op
+            _check_query(op[:1] + op[2:], self.nseg)
+        elif kind in DESCENT_KINDS:
+            self.descent = descent_after(self.descent, op)
         else:
             assert kind in ("m_execute", "g_refused_model"), kind
+        # what makes the descent stale: a retarget of its member, a serve whose turnovers reach its slot
+        if (kind in ("g_retarget", "g_retarget_requests") or (kind in ("m_retarget", "m_retarget_request") and op[1] == DESCENT_MEMBER)
+                or (kind == "g_serve" and min(op[2], self.P) > DESCENT_MEMBER)):
+            self.descent = descent_staled(self.descent, "target")
         if self.lead is not None and self.lockstep():
             self.lead = None
         if kind == "g_serve" or self.lockstep():
@@ -610,12 +831,19 @@ class GroupBook:
         ops = [("g_refused_model",) if self.stale else ("g_synchronize",)]
         for m in range(self.P):
             ops.append(("observe", m, tuple(k for k in OBS_ORDER if k in self.valid[m])))
+        if self.ask and descent_allows(self.descent, "chomp_get"):
+            ops.append(("chomp_get", ("trajectory", "final_increments", "cost")))
         return ops
 
 
 def _group_op(book, kind, rng):
     P = book.P
     m = int(rng.integers(P))
+    if kind in GROUP_ASK_QUERIES:
+        op = _ask_op(kind[2:], book.descent, book.nseg, rng)
+        return (kind, m) + op[1:]
+    if kind in DESCENT_KINDS:
+        return _ask_op(kind, book.descent, book.nseg, rng)
     if kind in ("g_run", "g_run_refused"):
         first = book.next_it if rng.random() < 0.8 else max(book.next_it + int(rng.integers(-1, 2)), 1)
         return (kind, first, int(rng.integers(1, 5)))
@@ -667,21 +895,27 @@ class RankBook(Book):
 
     def __init__(self, info):
         super().__init__(info)
-        self.kinds = RANK_KINDS
+        self.kinds = RANK_KINDS + (ASK_QUERIES if self.ask else ())
+        self.refusals = RANK_REFUSALS + (("chomp_create",) if self.ask else ())
 
     def allowed(self, kind):
         return kind in self.kinds
 
     def apply(self, op):
         if op[0] == "refuse":
-            assert op[1] in RANK_REFUSALS
+            assert op[1] in self.refusals
+        elif op[0] in ASK_QUERIES:      # the last argument: the rank that answers
+            assert self.ask and op[-1] in (0, 1), op
+            _check_query(op[:-1], self.nseg)
         else:
             super().apply(op)
 
 
 def _rank_op(book, kind, rng):
     if kind == "refuse":
-        return ("refuse", RANK_REFUSALS[int(rng.integers(len(RANK_REFUSALS)))])
+        return ("refuse", book.refusals[int(rng.integers(len(book.refusals)))])
+    if kind in ASK_QUERIES:
+        return _ask_op(kind, "none", book.nseg, rng) + (int(rng.integers(2)),)
     return _single_op(book, kind, rng)
 
 
@@ -694,7 +928,7 @@ def mode_info(mode):
     if mode not in _INFO:
         spec = MODES[mode]
         if "info" in spec:      # (a mode whose problems are slow to build says what its book needs)
-            _INFO[mode] = dict(spec["info"], serve=spec.get("serve", False))
+            _INFO[mode] = dict(spec["info"], serve=spec.get("serve", False), ask=spec.get("ask", False))
             return _INFO[mode]
         made = spec["make"]()
         if spec["kind"] == "group":
@@ -704,7 +938,9 @@ def mode_info(mode):
         else:
             _INFO[mode] = dict(Kr=made.params.num_reused_rollouts, cum=bool(made.params.use_cumulative_costs),
                                max_it=made.params.max_iterations, device=spec.get("device_field", False),
-                               request=spec.get("request", False), scene=spec.get("scene", False))
+                               request=spec.get("request", False), scene=spec.get("scene", False),
+                               ask=spec.get("ask", False), nseg=len(made.robot.segments),
+                               brick=spec["env"].get("STOMP_SDF_LAYOUT") == "brick")
     return _INFO[mode]
 
 
@@ -753,7 +989,12 @@ def make_script(mode, seed, length=None):
     arguments alone)."""
     length = length_of(mode) if length is None else length
     ident = IDENTS[mode]
-    made, seen = _SCRIPTS.setdefault((mode, length), ([], set()))
+    if (mode, length) not in _SCRIPTS:
+        # an ask mode's walks are steered to the pairs its census counts: those with an ask.  Pairs
+        # of two old kinds are the old modes' business and count as shown from the start.
+        old = [k for k in kinds_of(mode) if k not in ASKS] if MODES[mode].get("ask") else []
+        _SCRIPTS[(mode, length)] = ([], {(a, b) for a in old for b in old})
+    made, seen = _SCRIPTS[(mode, length)]
     while len(made) <= seed:
         made.append(_walk(mode, np.random.default_rng([ident, len(made), length]), length, seen))
     return list(made[seed])
@@ -821,6 +1062,20 @@ def impossible_pairs(mode):
             # either side of that refused run.  g_serve itself is accepted in every state, and
             # every kind can follow one (n >= P levels the group, n < P may split it): no new pair
             del out[("g_run_refused", "m_retarget")], out[("m_retarget", "g_run_refused")]
+    if "chomp_reset" in kinds_of(mode):
+        # ops after which the descent is stale whatever their arguments (a member's own retarget
+        # and a serve stale it only when they reach its member)
+        staling = {"single": ("retarget", "retarget_request") + SCENE_KINDS, "group": ("g_retarget",)}[kind]
+        for a in staling:
+            if a in kinds_of(mode):
+                for b in ("chomp_step", "chomp_get", "chomp_optimize"):
+                    out[(a, b)] = "the descent is stale: only chomp_refused and chomp_reset may follow"
+        out[("chomp_reset", "chomp_refused")] = "a fresh descent refuses nothing"
+        out[("chomp_refused", "chomp_optimize")] = "no refusal leaves a fresh descent"
+        for a in ("chomp_step", "chomp_optimize"):
+            out[(a, "chomp_optimize")] = "the loop starts from a fresh reset (chomp_refused asserts the refusal)"
+        out[("chomp_optimize", "chomp_step")] = ("tests/chomp_ref.c restates one descent, and its cr_step knows no stopped "
+                                                 "descent: stepping behind a loop has no reference")
     return out
 
 
@@ -861,7 +1116,130 @@ def _assert_execute(e, want, rows, member, terms, tag):
         np.testing.assert_array_equal(e.last_constraints_satisfied, want[3], err_msg=f"{tag} constraints flags")
 
 
-class Pair:
+def _subset(res, ref, want, tag):
+    for k in want:
+        a, b = getattr(res, k), getattr(ref, k)
+        assert a is not None and a.shape == b.shape, (tag, k, None if a is None else a.shape, b.shape)
+        np.testing.assert_array_equal(a, b, err_msg=f"{tag} {k}")
+
+
+class Asks:
+    """The asks of a pair: state queries, gradient queries and one CHOMP object that lives through
+    the walk.  Each takes the engine asked, that engine's current problem with its current field, and
+    (a reset from theta) its oracle; the oracle side of the pair never hears of an ask.  With no
+    engine (the CPU tests) an ask does nothing."""
+    chomp_params = _CHOMP_PLAIN
+    ch = None
+
+    def ask_query_states(self, e, p, seed, M, links, want, tag=""):
+        if e is None:
+            return
+        q = squ.make_states(p, M, seed)
+        res = e.query_states(q, links=list(links) or None, want=want)
+        _subset(res, squ.reference(p, q, list(links)), want, f"{tag}query_states")
+        for k in QS_OUTPUTS:      # and nothing that was not asked for
+            assert k in want or getattr(res, k) is None, k
+
+    def ask_query_gradients(self, e, p, seed, M, links, want, biased, tag=""):
+        if e is None:
+            return
+        q = squ.make_states(p, M, seed)
+        bias = gqu.BIAS if biased else (0.0, 0.0, 0.0)
+        res = e.query_gradients(q, links=list(links) or None, field_bias=bias, want=want)
+        _subset(res, gqu.reference(p, q, list(links), bias), want, f"{tag}query_gradients")
+        for k in GQ_OUTPUTS:
+            assert k in want or getattr(res, k) is None, k
+
+    def _chomp(self, e):
+        if self.ch is None:
+            prm = self.chomp_params
+            self.ch = eng.Chomp(e, learning_rate=prm.learning_rate, smoothness_cost_weight=prm.smoothness_cost_weight,
+                                use_pseudo_inverse=prm.use_pseudo_inverse,
+                                pseudo_inverse_ridge_factor=prm.pseudo_inverse_ridge_factor, field_bias=prm.field_bias,
+                                joint_update_limits=prm.limits(e.J))
+            self.ch_sizes, self.refs = [], []
+        assert self.ch.engine is e
+        return self.ch
+
+    def close_chomp(self):
+        if self.ch is not None:
+            self.ch.close()
+            self.ch = None
+
+    def ask_chomp_reset(self, e, p, o, B, source):
+        if e is None:
+            return
+        ch = self._chomp(e)
+        # the reference: a new ChompRef of the current problem and field per descent; a reset from
+        # theta starts at the ORACLE's theta, which is what "as they are on its stream" must equal
+        starts = [o.theta() if source is None else cu.noisy_start(p, source + b) for b in range(B)]
+        self.refs = []
+        for t in starts:
+            r = cu.ChompRef(p, self.chomp_params)
+            r.reset(t)
+            self.refs.append(r)
+        before = ch.info()["allocations"]
+        if source is None:
+            ch.reset(None, num_trajectories=B)
+        else:
+            ch.reset(np.stack(starts))
+        # the capacity rule: the slabs grow with B and S alone (J, N, the segments and max_iterations
+        # stay), so a reset that an earlier one covers in both allocates nothing
+        S = len(p.spheres)
+        assert e.S == S, (e.S, S)
+        if any(B <= b and S <= s for b, s in self.ch_sizes):
+            assert ch.info()["allocations"] == before, (B, S, self.ch_sizes, before, ch.info())
+        self.ch_sizes.append((B, S))
+        assert ch.info()["B"] == B and ch.info()["iterations"] == 0
+
+    def ask_chomp_step(self, e, count):
+        if e is None:
+            return
+        self.ch.step(count)      # enqueued: nothing waits
+        for r in self.refs:
+            r.step(count)
+
+    def ask_chomp_get(self, e, names):
+        if e is None:
+            return
+        for name in names:
+            got = self.ch.get(name)
+            assert len(got) == len(self.refs), (name, got.shape, len(self.refs))
+            for b, r in enumerate(self.refs):
+                ref = r.get(name)
+                assert got[b].shape == np.shape(ref), (name, got[b].shape, np.shape(ref))
+                np.testing.assert_array_equal(got[b], ref, err_msg=f"chomp_get descent {b} {name}")
+
+    def ask_chomp_optimize(self, e):
+        if e is None:
+            return
+        out = self.ch.optimize()
+        assert len(out) == len(self.refs)
+        for b, ((st, costs, best), r) in enumerate(zip(out, self.refs)):
+            rst, rcosts, rbest = r.optimize()
+            assert cu.stats_tuple(st) == cu.stats_tuple(rst), (b, cu.stats_tuple(st), cu.stats_tuple(rst))
+            np.testing.assert_array_equal(costs, rcosts, err_msg=f"chomp_optimize descent {b} cost history")
+            np.testing.assert_array_equal(best, rbest, err_msg=f"chomp_optimize descent {b} best trajectory")
+
+    def ask_chomp_refused(self, e, why):
+        if e is None:
+            return
+        ch = self._chomp(e)
+        word = {"no_reset": "no reset", "stale_target": "retargeted or its field refreshed", "stale_model": "model changed",
+                "needs_fresh_reset": "fresh reset"}[why]
+        if why == "needs_fresh_reset":
+            _expect_refusal(ch.optimize, -1, word)
+            return
+        for call in (lambda: ch.step(1), ch.optimize, lambda: ch.get("cost")):
+            _expect_refusal(call, -1, word)
+        # and get wrote nothing
+        out = np.full(max(ch.B, 1) * e.J * e.N, -7.25)
+        l = eng.load_library()
+        assert l.stomp_chomp_get(ch.h, b"trajectory", eng._dp(out)) == -1 and word.encode() in l.stomp_chomp_last_error(ch.h)
+        assert (out == -7.25).all()
+
+
+class Pair(Asks):
     """One engine (None: the oracle alone, for the CPU tests) and its oracle."""
 
     def __init__(self, problem, engine=None, threads=1, field=None, scene=None, stream=None, brick=False):
@@ -879,6 +1257,7 @@ class Pair:
         return po.Oracle(dataclasses.replace(p, sdf=self.cur_sdf.copy()), threads=self.threads)
 
     def close(self):
+        self.close_chomp()      # it borrows the engine
         if self.e is not None:
             self.e.close()
         if self.scene is not None:
@@ -1104,6 +1483,33 @@ class Pair:
             assert l.stomp_pi_get_rollouts(e.h, self.it + 1, None, eng._dp(out), C.byref(n)) == -1
             assert b"null noise_stddev" in l.stomp_engine_last_error(e.h) and n.value == -7 and not out.any()
 
+    # -------------------------------------------------------------- asks
+    def _asked(self):
+        """the engine's current problem with its current field: after every retarget, request,
+        refresh_field and scene op so far"""
+        return dataclasses.replace(self.p, sdf=self.cur_sdf)
+
+    def op_query_states(self, seed, M, links, want):
+        self.ask_query_states(self.e, self._asked(), seed, M, links, want)
+
+    def op_query_gradients(self, seed, M, links, want, biased):
+        self.ask_query_gradients(self.e, self._asked(), seed, M, links, want, biased)
+
+    def op_chomp_reset(self, B, source):
+        self.ask_chomp_reset(self.e, self._asked(), self.o, B, source)
+
+    def op_chomp_step(self, count):
+        self.ask_chomp_step(self.e, count)
+
+    def op_chomp_get(self, names):
+        self.ask_chomp_get(self.e, names)
+
+    def op_chomp_optimize(self):
+        self.ask_chomp_optimize(self.e)
+
+    def op_chomp_refused(self, why):
+        self.ask_chomp_refused(self.e, why)
+
     def apply(self, op):
         getattr(self, "op_" + op[0])(*op[1:])
 
@@ -1114,8 +1520,9 @@ class Pair:
         return st
 
 
-class GroupPair:
-    """A group on one stream, twins that make the equivalent single-engine calls, and the oracles."""
+class GroupPair(Asks):
+    """A group on one stream, twins that make the equivalent single-engine calls, and the oracles.
+    The asks go to the group's engines alone: the twins and the oracles never hear of them."""
 
     def __init__(self, problems, threads=1, targets=None, **group_kw):
         self.ps0 = list(problems)
@@ -1129,6 +1536,7 @@ class GroupPair:
         self.os = [po.Oracle(p, threads=threads) for p in self.ps]
 
     def close(self):
+        self.close_chomp()      # it borrows member DESCENT_MEMBER's engine
         gu.close_all(self.g, self.twins)
 
     def _refused_run(self, first, count):
@@ -1312,11 +1720,34 @@ class GroupPair:
         assert self.g.engines[m].iterate(it) == ro, f"engine {m}"
         assert self.twins[m].iterate(it) == ro, f"twin {m}"
 
+    # -------------------------------------------------------------- asks
+    def op_m_query_states(self, m, seed, M, links, want):
+        self.ask_query_states(self.g.engines[m], self.ps[m], seed, M, links, want, f"engine {m} ")
+
+    def op_m_query_gradients(self, m, seed, M, links, want, biased):
+        self.ask_query_gradients(self.g.engines[m], self.ps[m], seed, M, links, want, biased, f"engine {m} ")
+
+    def op_chomp_reset(self, B, source):
+        m = DESCENT_MEMBER
+        self.ask_chomp_reset(self.g.engines[m], self.ps[m], self.os[m], B, source)
+
+    def op_chomp_step(self, count):
+        self.ask_chomp_step(self.g.engines[DESCENT_MEMBER], count)
+
+    def op_chomp_get(self, names):
+        self.ask_chomp_get(self.g.engines[DESCENT_MEMBER], names)
+
+    def op_chomp_optimize(self):
+        self.ask_chomp_optimize(self.g.engines[DESCENT_MEMBER])
+
+    def op_chomp_refused(self, why):
+        self.ask_chomp_refused(self.g.engines[DESCENT_MEMBER], why)
+
     def apply(self, op):
         getattr(self, "op_" + op[0])(*op[1:])
 
 
-class RankPair:
+class RankPair(Asks):
     """Two in-process ranks of one problem (tests/rank_util.py) beside one oracle of the whole K.
     Every rank makes every call on a thread of its own and asserts nothing there: what the calls
     returned is compared after the threads joined."""
@@ -1386,8 +1817,19 @@ class RankPair:
                      pi_reset=lambda e: e.pi_reset(),
                      retarget=lambda e: e.retarget(p.start, p.goal, p.seed + 1))
         for e in self.ranks:   # refused on the host before anything is posted: no thread needed
+            if what == "chomp_create":
+                _expect_refusal(lambda: eng.Chomp(e), -3, "sharded")
+                continue
             _expect_refusal(lambda: calls[what](e), -3, "single-rank")
             assert e.problem is p
+
+    # one rank answers at a time, from the main thread, between the collective calls: every rank
+    # holds the whole model and field, and no collective runs
+    def op_query_states(self, seed, M, links, want, rank):
+        self.ask_query_states(self.ranks[rank], self.p, seed, M, links, want, f"rank {rank} ")
+
+    def op_query_gradients(self, seed, M, links, want, biased, rank):
+        self.ask_query_gradients(self.ranks[rank], self.p, seed, M, links, want, biased, f"rank {rank} ")
 
     def apply(self, op):
         getattr(self, "op_" + op[0])(*op[1:])

@@ -5,9 +5,14 @@ every call, so a stale pregen iteration, a dropped pending rollout or an unswapp
 read would have repaired stays visible to the next call.  Every comparison is bitwise.  Each case
 ends with a full observe of everything both sides define (groups and ranks: after a synchronize).
 
+The ask modes put state queries, gradient queries and a CHOMP descent among those calls: each is
+compared with its own CPU reference on the pair's current problem and field, and the oracle side never
+hears of them, so an ask that touched the engine shows in what the next calls return.
+
 tests/CALL_WALKS.md holds the alphabet, the modes, the census and what the walks found; the scripts
-that showed a bug stand below the walks as named regression tests, and after them the literal script
-that turns the padding-collision flag through a serve call.
+that showed a bug stand below the walks as named regression tests, and after them the literal scripts:
+the padding-collision flag turned through a serve call, and a descent on a group member that a short
+serve leaves alone and a full one makes stale.
 """
 import numpy as np
 import pytest
@@ -36,6 +41,8 @@ def make_pair(mode, monkeypatch, capfd):
     for k, v in spec["env"].items():
         monkeypatch.setenv(k, v)
     threads = spec.get("threads", 1)
+    if spec.get("ask"):     # on the references alone, before any device is touched
+        cw.assert_asks_matter(mode)
     made = spec["make"]()
     capfd.readouterr()
     if spec["kind"] == "single":
@@ -72,6 +79,8 @@ def make_pair(mode, monkeypatch, capfd):
         assert [e.shard_mode for e in ranks] == [spec["shard"]] * 2 and [e.K_loc for e in ranks] == [64, 64]
     for piece in spec["expect"]:
         assert any(piece in l for l in got), (piece, got)
+    if "chomp" in spec:     # the parameters of the mode's one CHOMP object
+        pair.chomp_params = spec["chomp"]
     return pair
 
 
@@ -147,3 +156,24 @@ def test_serve_turns_the_padding_flag_both_ways(monkeypatch, capfd):
         assert all(A in seq and B in seq for seq in by_slot.values()) and len(by_slot) == 4, by_slot
 
     walk("group_serve_shelf", script, monkeypatch, capfd, after=after)
+
+
+# ---------------------------------------------------------------------------- a descent under a serve
+def test_descent_survives_a_short_serve(monkeypatch, capfd):
+    # The descent borrows member 1's engine.  A serve of one request turns slot 0 alone: the descent
+    # stays live and goes on bit for bit, its steps enqueued behind the serve with no wait.  A serve of
+    # P requests turns every slot: step, optimize and get are each refused for the retarget, get writes
+    # nothing, and a reset from member 1's theta (the oracle's, after the slot's last request) brings
+    # the descent back.
+    P = 4
+    script = [("chomp_reset", 2, 41), ("g_serve", 5, 1), ("chomp_step", 2),
+              ("chomp_get", ("trajectory", "collision_increments", "potentials", "cost")),
+              ("g_serve", 6, P), ("chomp_refused", "stale_target"), ("chomp_reset", 1, None),
+              ("chomp_get", ("trajectory", "distances", "costs", "collision_free"))]
+    book = cw.new_book("ask_group")
+    states = []
+    for op in script:
+        book.apply(op)
+        states.append(book.descent)
+    assert states == ["fresh", "fresh", "stepped", "stepped", "stale_target", "stale_target", "fresh", "fresh"], states
+    walk("ask_group", script, monkeypatch, capfd)
